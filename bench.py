@@ -23,6 +23,19 @@ prints ONE JSON line; `roofline` is measured live with HIP events on the launch
 stream, `cpu_baseline` times the reference's own main.train (a staged, git-ignored copy
 of its module files, oracle/reference_runner.py) and the CPU oracle (the port)
 on a bounded sample on this host's cores.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value,
+unit, higher_is_better, dtype, ms_per_step and the configuration).  Everything else -
+the other arithmetics, the other BASELINE configurations and variants, the fresh-batch
+loop, the roofline / per-launch timings, the exposed collective time at N > 1, the
+scaling projection and the CPU baseline - runs only with --full.
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR
+
+--dump-outputs DIR writes what the timed path left after its last step as float32
+DIR/<name>.npy (dump_outputs); inputs, weights and dropout seeds are seeded, so two
+runs with the same arguments (on two builds) can be compared array for array.
 """
 import argparse
 import gc
@@ -188,6 +201,43 @@ def scaling_projection(step_ms_by_config):
     return {"model": "efficiency = t_1gpu / (t_1gpu + gradient-norm pass + all-reduce), the all-reduce fully exposed; [pessimistic (ring), "
                      "optimistic (direct reduce-scatter + all-gather over the mesh)], link efficiency 0.65 of 153 GB/s; the driver's N = 2, 4, 8 runs test it",
             "configs": out}
+
+
+DUMP_BYTES = 63 * 10 ** 6      # all arrays of --dump-outputs together (a 64 MB limit, less the .npy headers)
+
+
+def dump_outputs(engs, path):
+    """--dump-outputs: what a caller of the timed path holds after its last step, one float32 DIR/<name>.npy per array - per model
+    (prefix `stream<k>.` when there are two) the state after the last update (`param.<state_dict key>`), the last step's forward
+    outputs (`out` = class logits, `attn`, `pred_*`, `feat_*`) and its loss terms (`losses`: loss, loss_c, loss_adv_rel,
+    loss_adv_vid, loss_adv_frm, loss_e).  Where the whole would exceed DUMP_BYTES (configs[4]'s two models), every array longer
+    than a common cap keeps a fixed seeded sample of that many elements (the same indices on every run), flattened."""
+    import numpy as np
+    arrays = {}
+    for k, e in enumerate(engs):
+        pre = f"stream{k}." if len(engs) > 1 else ""
+        for name, v in e.state_dict().items():
+            arrays[f"{pre}param.{name}"] = v
+        for name, v in e.outputs().items():
+            arrays[pre + name] = v
+        arrays[pre + "losses"] = torch.tensor(list(e.losses().values()))
+    arrays = {n: v.detach().float().cpu().numpy() for n, v in arrays.items()}
+    cap = max(a.size for a in arrays.values())
+    if 4 * sum(a.size for a in arrays.values()) > DUMP_BYTES:
+        lo, hi = 1, cap          # the largest cap whose capped total fits
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if 4 * sum(min(a.size, mid) for a in arrays.values()) <= DUMP_BYTES else (lo, mid - 1)
+        cap = lo
+    os.makedirs(path, exist_ok=True)
+    sampled = 0
+    for name, a in arrays.items():
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+            sampled += 1
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays under {path}" + (f" ({sampled} sampled to {cap} elements)" if sampled else ""),
+          file=sys.stderr, flush=True)
 
 
 def cpu_baseline(conf=None, seconds=12.0, max_steps=400):
@@ -499,7 +549,14 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="do not add the 20-step timings of configs[0] / [3] / [4] to the line")
     ap.add_argument("--no-fresh-batch", action="store_true", help="skip the second timed loop with a new device-gathered batch per step")
     ap.add_argument("--phase-reps", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: the other "
+                    "arithmetics, configurations and variants, the fresh-batch loop, roofline and per-launch timings, the exposed collective "
+                    "time (N > 1), the scaling projection and the CPU baseline (the --skip-* / --no-* / --single-dtype options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in "
+                    "its last step (parameters after the update, forward outputs, loss terms) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("[bench] --steps must be >= 1 and --warmup >= 0")
     conf = CONFIGS[args.config]
     SH = conf["shape"]
     if args.dtype is None:
@@ -534,9 +591,10 @@ def main():
             torch.distributed.barrier()
             torch.cuda.synchronize(dev)
 
-    def run(dtype, steps, warmup, conf=conf, brief=False):
+    def run(dtype, steps, warmup, conf=conf, brief=False, dump=None):
         """Build the engine(s) for one arithmetic, time `steps` train steps after `warmup`; returns the numbers of the JSON line.
-        brief: only the step time and the whole-step bound (the other BASELINE configurations inside the default line)."""
+        brief: only the step time and the whole-step bound (the other BASELINE configurations inside the --full line).
+        dump: directory for dump_outputs, written right after the timed steps (before any further measurement touches the engines)."""
         SH = conf["shape"]
         n_streams = conf["streams"]
         headline = conf is CONFIGS[2] or conf is CONFIGS[3]
@@ -679,7 +737,10 @@ def main():
             elapsed = t.item()
         # a two-stream step processes each video through both models: videos/s counts videos, not model passes
         res = {"ms_per_step": 1e3 * elapsed / steps, "value": (SH["Bs"] + SH["Bt"]) * world * steps / elapsed}
-        if batched and two is None and not brief and world == 1 and not selftest and eng.can_batch_steps() and not args.no_fresh_batch:
+        if dump is not None and rank == 0:
+            dump_outputs(engs, dump)
+        if (args.full and batched and two is None and not brief and world == 1 and not selftest and eng.can_batch_steps()
+                and not args.no_fresh_batch):
             try:
                 # The same K steps once more with a DIFFERENT batch every step: a synthetic dataset resident in HBM
                 # as a packed feature store (ta3n_amd/feature_store.py: 640 videos x 16-47 frames), random video ids per step, each step's
@@ -713,7 +774,7 @@ def main():
                 del store, rows, ids
             except Exception as ex:      # noqa: BLE001 - an extra figure must not cost the line (nor, at N > 1, the scaling run)
                 res["fresh_batch_error"] = f"{type(ex).__name__}: {ex}"[:200]
-        if (world > 1 or selftest) and not brief:
+        if args.full and (world > 1 or selftest) and not brief:
             # what the gradient exchange costs per step: the same loop once more WITHOUT the collective (every rank skips it; the
             # numbers it trains on are then wrong, the timing is what is wanted) - the difference is the exposed collective time
             eng.skip_collective = True
@@ -735,9 +796,10 @@ def main():
                                  "what": "the timed loop repeated with the all-reduce skipped on every rank; exposed = difference per step"}
         if rank != 0:
             return res
-        wsb = whole_step_bound(conf, dtype, eng)
-        res["whole_step"] = {**wsb, "frac": wsb["bound_us"] / (1e3 * res["ms_per_step"]),
-                             "what": "SURVEY.md 8(d): max(algorithmic FLOPs / MFMA peak, algorithmic bytes / 6.3 TB/s) per step, divided by the measured step time"}
+        if args.full:
+            wsb = whole_step_bound(conf, dtype, eng)
+            res["whole_step"] = {**wsb, "frac": wsb["bound_us"] / (1e3 * res["ms_per_step"]),
+                                 "what": "SURVEY.md 8(d): max(algorithmic FLOPs / MFMA peak, algorithmic bytes / 6.3 TB/s) per step, divided by the measured step time"}
         if brief:
             if eng.fused and conf["agg"] == "trn-m":      # per-launch figures of the tile-list GEMM for the other configurations too
                 res["gemm_launches"] = gemm_launch_table(eng, eng.time_phases(max(3, args.phase_reps // 2)), bf16, split)
@@ -768,6 +830,12 @@ def main():
         res["batched"] = batched
         res["pipelined"] = pipelined
         res["fused"] = eng.fused
+        # tile code per GEMM launch as the plan built it: WM WN WK + 1000 x (LDS stages, + 16: reads bf16 twins) + 100000 x blocking
+        # (1: 2 row blocks per wave, 2: 2 column blocks, 3: 2 x 2 - 128x64 / 64x128 / 128x128 tiles)
+        res["phase_tiles"] = [ph["tile"] + 100000 * ((ph.get("rm", 1) > 1) + 2 * (ph.get("rn", 1) > 1))
+                              for ph in eng.plan.description["phases"] if ph["kind"] == 0 and ph["group"] != 5]
+        if not args.full:
+            return res
         # live per-launch timing of the dominant kernel (the tile-list GEMM), HIP events on the launch stream
         phases = eng.time_phases(args.phase_reps)
         gemm_plain_ms = sum(p[3] for p in phases if p[0] == 0)       # the six GEMM launches without the update riding in the first
@@ -829,15 +897,11 @@ def main():
         res["roofline"]["whole_step"] = res["whole_step"]
         if eng.fused:
             res["roofline"]["gemm_launches"] = gemm_launch_table(eng, [p for p in eng.time_phases(args.phase_reps)], bf16, split)
-        # tile code per GEMM launch as the plan built it: WM WN WK + 1000 x (LDS stages, + 16: reads bf16 twins) + 100000 x blocking
-        # (1: 2 row blocks per wave, 2: 2 column blocks, 3: 2 x 2 - 128x64 / 64x128 / 128x128 tiles)
-        res["phase_tiles"] = [ph["tile"] + 100000 * ((ph.get("rm", 1) > 1) + 2 * (ph.get("rn", 1) > 1))
-                              for ph in eng.plan.description["phases"] if ph["kind"] == 0 and ph["group"] != 5]
         return res
 
-    main_res = run(args.dtype, args.steps, args.warmup)
+    main_res = run(args.dtype, args.steps, args.warmup, dump=args.dump_outputs)
     other, third = None, None
-    if headline and not args.single_dtype and not selftest:   # the other arithmetic, same process (all ranks): at N > 1 the fp32 line is BASELINE configs[2]
+    if args.full and headline and not args.single_dtype and not selftest:   # the other arithmetic, same process (all ranks): at N > 1 the fp32 line is BASELINE configs[2]
         other = run("f32" if args.dtype == "bf16" else "bf16", max(50, args.steps // 2), max(10, args.warmup // 2))
         if args.dtype != "f32x3" and world == 1:               # and the fp32-grade split arithmetic (same fp32 parity tests as "f32")
             try:
@@ -845,10 +909,10 @@ def main():
             except Exception as ex:      # noqa: BLE001 - an extra line must not cost the headline line
                 print(f"[bench] split-arithmetic run failed: {type(ex).__name__}: {ex}", file=sys.stderr, flush=True)
 
-    # the other BASELINE configurations, bounded (20 steps after 5: well under 2 s each), so that the default line carries
-    # driver-visible timings of configs[0] / [3] / [4] with their SURVEY 8(d) bounds
+    # the other BASELINE configurations, bounded (20 steps after 5: well under 2 s each), so that the --full line carries
+    # timings of configs[0] / [3] / [4] with their SURVEY 8(d) bounds
     configs_line = None
-    if headline and world == 1 and not args.single_dtype and not selftest and not args.no_other_configs:
+    if args.full and headline and world == 1 and not args.single_dtype and not selftest and not args.no_other_configs:
         configs_line = {}
         for cnum in (1, 4, 5):
             cf = CONFIGS[cnum]
@@ -872,7 +936,7 @@ def main():
     # SURVEY 8(f)4 on the fused path (round 6): the headline step with use_bn AdaBN - two BatchNorm launches inside ta3n_train_step, 10 launches
     # instead of 8, the running statistics tracked by the BatchNorm launch itself (K steps from one library call, like the headline)
     variants = None
-    if headline and world == 1 and not args.single_dtype and not selftest and not args.no_other_configs:
+    if args.full and headline and world == 1 and not args.single_dtype and not selftest and not args.no_other_configs:
         variants = {}
         try:
             cf = dict(CONFIGS[2], use_bn="AdaBN", name=CONFIGS[2]["name"] + ", use_bn AdaBN (domain BatchNorm behind the shared frame FC) inside the fused step")
@@ -953,8 +1017,9 @@ def main():
                        "exchange_probe": main_res.get("exchange_probe"),
                        "collective": main_res.get("collective"),
                        "phase_tiles": main_res["phase_tiles"]},
-            "roofline": main_res["roofline"],
         }
+        if args.full:
+            out["roofline"] = main_res["roofline"]
         if other is not None:
             o_dtype = "f32" if args.dtype == "bf16" else "bf16"
             o = {"dtype": o_dtype, "what": arith[o_dtype], "value": other["value"], "unit": "videos/s", "ms_per_step": other["ms_per_step"],
@@ -994,14 +1059,14 @@ def main():
                         t1[int(k_[8:-1]) + 1] = v_["ms_per_step"]
             elif main_res.get("collective"):
                 t1[args.config] = main_res["collective"]["step_without_collective_ms"]
-            if t1:
+            if args.full and t1:
                 out["config"]["scaling_projection"] = scaling_projection(t1)
                 if world > 1:
                     out["config"]["scaling_projection"]["measured_here"] = {"n_gpus": world, "ms_per_step": main_res["ms_per_step"],
                                                                            "exposed_collective_us": main_res["collective"]["exposed_us_per_step"]}
         except Exception as ex:      # noqa: BLE001 - an extra entry must not cost the line
             out["config"]["scaling_projection"] = {"error": f"{type(ex).__name__}: {ex}"[:200]}
-        if not args.skip_cpu_baseline and world == 1:       # the CPU path is timed on rank 0 at N = 1 only
+        if args.full and not args.skip_cpu_baseline and world == 1:       # the CPU path is timed on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(conf)
         # ONE JSON line on stdout and nothing else: libraries print there too (RCCL's version banner sits in the C stdio buffer until the
         # process exits and would land BEHIND the line), so file descriptor 1 was pointed at stderr for the whole run (_stdout_to_stderr);

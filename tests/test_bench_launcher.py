@@ -63,3 +63,11 @@ def test_single_rank_launch_test_line():
     r = subprocess.run([sys.executable, BENCH], cwd=ROOT, env=_env(TA3N_BENCH_LAUNCH_TEST="1"), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert _json_lines(r.stdout)[0]["n_gpus"] == 1
+
+
+def test_steps_and_warmup_are_validated():
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, BENCH, *argv], cwd=ROOT, env=_env(TA3N_BENCH_LAUNCH_TEST="1"), capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode != 0 and "--steps must be >= 1" in r.stderr, argv
+        assert _json_lines(r.stdout) == []

@@ -1,4 +1,5 @@
 """Host-side boundary (no GPU): the module/flag surface the reference's scripts bind to."""
+import json
 import os
 import sys
 
@@ -85,20 +86,30 @@ def test_compat_import_names():
             sys.modules.pop(name, None)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout only exists in the build container")
-def test_flag_surface_identical_to_reference_parser():
-    import argparse
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("ref_opts", os.path.join(REF, "opts.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    from ta3n_amd import opts
+REF_OPTS = os.path.join(ROOT, "tests", "golden", "reference_opts_table.json")
 
-    def table(p):
-        return {a.dest: (tuple(sorted(a.option_strings)), a.default, tuple(a.choices) if a.choices else None, a.nargs,
-                         getattr(a, "type", None), type(a).__name__)
-                for a in p._actions if not isinstance(a, argparse._HelpAction)}
-    assert table(ref.parser) == table(opts.parser)
+
+def _flag_table(parser):
+    """dest -> [option strings, default, choices, nargs, type name, action class] of every argument but --help (JSON-able)."""
+    import argparse
+    return {a.dest: [sorted(a.option_strings), a.default, list(a.choices) if a.choices else None, a.nargs,
+                     getattr(getattr(a, "type", None), "__name__", None), type(a).__name__]
+            for a in parser._actions if not isinstance(a, argparse._HelpAction)}
+
+
+def test_flag_surface_identical_to_reference_parser():
+    """tests/golden/reference_opts_table.json is _flag_table of the reference's opts.parser, recorded from its opts.py; where that
+    checkout exists the recording is checked against it as well."""
+    from ta3n_amd import opts
+    with open(REF_OPTS) as f:
+        recorded = json.load(f)
+    assert json.loads(json.dumps(_flag_table(opts.parser))) == recorded
+    if os.path.exists(os.path.join(REF, "opts.py")):
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("ref_opts", os.path.join(REF, "opts.py"))
+        ref = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(ref)
+        assert json.loads(json.dumps(_flag_table(ref.parser))) == recorded
 
 
 def test_script_command_line_parses():

@@ -211,7 +211,8 @@ def test_own_main_fused_fast_path_logs_what_the_module_path_logs(tmp_path, bn): 
     outs, cks = [], []
     for fast in ("1", "0"):
         exp = str(tmp_path / f"exp{fast}")
-        cmd = [sys.executable, os.path.join(ROOT, "main.py"), data[0], "RGB", data[1], data[2], data[3], "--exp_path", exp + "/", *TA3N, *common]
+        cmd = [sys.executable, os.path.join(ROOT, "main.py"), data[0], "RGB", data[1], data[2], data[3], "--exp_path", exp + "/", *TA3N, *common,
+               "--save_best_log", str(tmp_path / f"best{fast}.log")]
         r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=dict(os.environ, TA3N_MAIN_FAST=fast))
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         outs.append([ln for ln in open(exp + "/RGB/train.log") if ln.startswith("Train:")])

@@ -13,10 +13,10 @@ python $R/tools/measure_traffic.py $O > $O/traffic_stdout.txt 2>&1
 cp $O/gemm_traffic.json $R/profiles/gemm_traffic.json      # so that the bench line below reports it as fresh
 # (also writes pmc_bf16.txt / pmc_f32.txt / pmc_f32x3.txt: per-dispatch counter tables of the last fused step per arithmetic)
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
-for c in 1 4 5; do python bench.py --config $c --steps 50 --warmup 10 > $O/bench_config$c.json 2>> $O/bench.err; done
+python bench.py --full > $O/bench.json 2> $O/bench.err
+for c in 1 4 5; do python bench.py --config $c --steps 50 --warmup 10 --full > $O/bench_config$c.json 2>> $O/bench.err; done
 TA3N_DDP_SELFTEST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 \
-  bench.py --gpus 1 --steps 200 --warmup 20 --skip-cpu-baseline --single-dtype > $O/ddp_selftest_1rank.json 2>> $O/bench.err
+  bench.py --gpus 1 --steps 200 --warmup 20 --full --skip-cpu-baseline --single-dtype > $O/ddp_selftest_1rank.json 2>> $O/bench.err
 python -m pytest tests/test_gpu_bf16.py -q -s -k "oracle" 2>&1 | grep -E "bf16 vs bf16-oracle|passed|failed" > $O/bf16_parity_gate.txt
 python tools/time_module_path.py > $O/module_path.txt 2>&1
 head -14 $O/bench_kernel_stats.csv | cut -c1-220

@@ -1,4 +1,4 @@
-"""Fill README.md's results table (the @NAME@ placeholders, or the previous numbers between the table markers) from committed bench lines:
+"""Fill README.md's results table (the @NAME@ placeholders, or the previous numbers between the table markers) from committed `bench.py --full` lines:
 usage: python tools/fill_readme.py profiles/r06_bench_driver_protocol.json [more lines of the same protocol ...]
 Every cell shows the range over the given lines."""
 import json
