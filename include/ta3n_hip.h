@@ -138,7 +138,13 @@ typedef struct {
                               * tile per compute unit), its single K segment halved (measured slower in both arithmetics,
                               * profiles/r06_split_k_shared_fc_ab.txt); 6 = both.
                               * 0: one workgroup per tile.  Experiments build only (measured 114.8 us against 113.6). */
-    int32_t reserved[1];
+    int32_t shared_fc_layers; /* --add_fc: Linear(F, F) -> ReLU -> dropout_i layers stacked on the shared frame FC, counting it
+                              * (models.py:145-153, 581-603: fc_feature_shared_2_source, fc_feature_shared_3_source).  0 and 1: the
+                              * single shared layer; 2 or 3: one or two more GEMM levels in the forward and the backward, their
+                              * parameters in the live prefix behind fc_feature_shared_source.  The frame discriminator, the
+                              * aggregation and everything behind them read the LAST layer's output (Geom o_F1 / o_gZ1); the
+                              * earlier layers' activations and gradients are the workspace regions "F_l<k>" / "gZ_l<k>".
+                              * Built for use_bn none without MCD and without chain / split_k / wgrads_late / phase_tiles. */
 } ta3n_config;
 
 /* Per-step scalars; lives in device memory inside ws (region "hyper").  The host

@@ -875,7 +875,8 @@ int ta3n_has_fused_update(const ta3n_plan *p) {
     // every live parameter's gradient is produced by a tile / column-sum task of the fused step (those carry the update)
     // (pair twins: the fused-update epilogue keeps no lo plane of the new parameters - the separate update does)
     // (experiments build only: measured time-neutral in round 3, profiles/r03_fused_update_ab.txt)
-    return TA3N_EXPERIMENTS && ta3n_has_fused_step(p) == 1 && p->cfg.aggregation == TA3N_AGG_TRN_M && p->geom.pair_delta == 0 ? 1 : 0;
+    return TA3N_EXPERIMENTS && ta3n_has_fused_step(p) == 1 && p->cfg.aggregation == TA3N_AGG_TRN_M && p->geom.pair_delta == 0 &&
+           p->cfg.shared_fc_layers <= 1 ? 1 : 0;      // (--add_fc > 1: not built)
 }
 
 int ta3n_train_steps_fused_update(ta3n_plan *p, const float *x, float *params, float *params_alt, float *grads, float *momentum, float *ws,

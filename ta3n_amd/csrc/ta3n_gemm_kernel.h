@@ -1188,6 +1188,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     const bool drop_on = (epi & (EPI_DROP_I | EPI_DROP_V)) && h_train != 0;
     const uint32_t dseed = (epi & EPI_DROP_I) ? hh.seed_i : hh.seed_v;
     const float dp = (epi & EPI_DROP_I) ? hh.p_drop_i : hh.p_drop_v;
+    const uint32_t doff = drop_on ? (uint32_t)t.pad2 : 0u;      // stream offset of a stacked shared layer (--add_fc; 0 otherwise)
     float *__restrict__ cbase = const_cast<float *>(base_ptr(ptrs, t.c_base)) + (size_t)t.c_off;
     const float *__restrict__ aux = (epi & EPI_MASK) ? base_ptr(ptrs, t.aux_base) + t.aux_off : nullptr;
     const float *__restrict__ add = (epi & EPI_ADD) ? base_ptr(ptrs, t.add_base) + t.add_off : nullptr;
@@ -1268,7 +1269,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             float x = (v[e] + ebias[e]) * alpha + av[e];
             if (epi & EPI_RELU) x = fmaxf(x, 0.f);
             x = mv[e] > 0.f ? x : 0.f;
-            if (drop_on) x *= keep_mask(dseed, (uint32_t)(m * t.drop_ld + n + e), dp);
+            if (drop_on) x *= keep_mask(dseed, (uint32_t)(m * t.drop_ld + n + e) + doff, dp);
             v[e] = x * gamma;
         }
         if (nrem <= 0) continue;

@@ -537,6 +537,93 @@ std::string Builder::end_chain() {
 
 typedef std::pair<int64_t, int64_t> Span;   // [first, last) in ws floats
 
+// ---------------------------------------------------------------------------------------------------------------------
+// --add_fc (ta3n_config.shared_fc_layers; models.py:145-153, 581-603): L - 1 more Linear(F, F) -> ReLU -> dropout_i layers on the
+// shared frame FC.  Layer k's output is F_k, the gradient at its pre-activation gZ_k; F_L / gZ_L are Geom's o_F1 / o_gZ1 (what the
+// heads, the pooling kernels and the frame discriminator read), the earlier ones the regions "F_l<k>" / "gZ_l<k>" that only GEMM
+// specs address.  Forward: one launch per layer, F_k = drop_i(relu(F_{k-1} W_k^T + b_k)).  Backward: one launch per layer,
+// gZ_{k-1} = (gZ_k W_k) * [F_{k-1} > 0] / keep_i beside dW_k = gZ_k^T F_{k-1}, db_k = column sums of gZ_k; dWsh = gZ_1^T X stays last.
+struct SharedStack {
+    int L = 1;
+    int64_t W[4] = {0, 0, 0, 0}, bias[4] = {0, 0, 0, 0};   // parameter offsets of layer k = 2 .. L
+    int64_t o_F[4] = {0, 0, 0, 0}, o_gZ[4] = {0, 0, 0, 0}; // ws offsets, k = 1 .. L
+};
+
+int shared_layers(const ta3n_config &c) { return c.shared_fc_layers <= 1 ? 1 : c.shared_fc_layers; }
+
+// "" when the configuration's shared_fc_layers is built, otherwise the refusal (naming the option)
+std::string shared_layers_refusal(const ta3n_config &c) {
+    if (c.shared_fc_layers < 0 || c.shared_fc_layers > 3)
+        return "shared_fc_layers (--add_fc) " + std::to_string(c.shared_fc_layers) + " is not built: 1, 2 or 3 (add_fc >= 4 shifts the "
+               "reference's place_dis slicing, main.py:368-378)";
+    if (c.shared_fc_layers <= 1) return "";
+    std::string what;
+    if (c.flags & TA3N_FLAG_BN_SHARED) what = "use_bn (TA3N_FLAG_BN_SHARED)";
+    else if (c.flags & TA3N_FLAG_MCD) what = "ens_DA MCD (TA3N_FLAG_MCD)";
+    else if (c.chain) what = "chain";
+    else if (c.split_k) what = "split_k";
+    else if (c.wgrads_late) what = "wgrads_late";
+    else
+        for (int i = 0; i < 16; ++i)
+            if (c.phase_tiles[i]) what = "phase_tiles (indexed by the single-layer launch order)";
+    return what.empty() ? "" : "shared_fc_layers (--add_fc) " + std::to_string(c.shared_fc_layers) + " with " + what + " is not built";
+}
+
+// parameters of layers 2 .. L: live, directly behind fc_feature_shared_source (first_floats: the update rides in the first launch)
+void add_stack_params(Builder &b, int L, int F) {
+    for (int k = 2; k <= L; ++k) b.add_linear("fc_feature_shared_" + std::to_string(k) + "_source", F, F, true);   // models.py:145-153
+}
+
+// parameter offsets and the earlier layers' regions; o_F1 / o_gZ1: Geom's (layer L)
+void lay_out_stack(ta3n_plan &p, Builder &b, SharedStack &st, int BT, int F, int64_t o_F1, int64_t o_gZ1) {
+    st.L = shared_layers(p.cfg);
+    for (int k = 2; k <= st.L; ++k) {
+        st.W[k] = p.poff("fc_feature_shared_" + std::to_string(k) + "_source.weight");
+        st.bias[k] = p.poff("fc_feature_shared_" + std::to_string(k) + "_source.bias");
+    }
+    for (int k = 1; k < st.L; ++k) st.o_F[k] = b.add_region("F_l" + std::to_string(k), (int64_t)BT * F);
+    for (int k = 1; k < st.L; ++k) st.o_gZ[k] = b.add_region("gZ_l" + std::to_string(k), (int64_t)BT * F);
+    st.o_F[st.L] = o_F1;
+    st.o_gZ[st.L] = o_gZ1;
+}
+
+GemmSpec spec_shared_layer(const SharedStack &st, int k, int BT, int F) {   // F_k = drop_i(relu(F_{k-1} W_k^T + b_k))  (models.py:581-603)
+    GemmSpec s;
+    s.M = BT; s.N = F;
+    s.segs.push_back(mkseg(KC(BASE_WS, st.o_F[k - 1], F), KC(BASE_P, st.W[k], F), F));
+    s.proto = proto(BASE_WS, st.o_F[k], F);
+    with_bias(s.proto, st.bias[k]);
+    s.proto.epi |= EPI_RELU | EPI_DROP_I;
+    s.proto.gamma_kind = SK_INV_KEEP_I;
+    s.proto.drop_ld = F;
+    s.proto.pad2 = (int32_t)(uint32_t)((uint64_t)(k - 1) * (uint64_t)BT * (uint64_t)F);   // a dropout stream of its own (ta3n_types.h)
+    return s;
+}
+
+void push_shared_layer_back(std::vector<GemmSpec> &s, const SharedStack &st, int k, int BT, int F) {
+    GemmSpec gz;                 // gZ_{k-1} = (gZ_k W_k) * [F_{k-1} > 0] / keep_i
+    gz.M = BT; gz.N = F;
+    gz.segs.push_back(mkseg(KC(BASE_WS, st.o_gZ[k], F), KM(BASE_P, st.W[k], F), F));
+    gz.proto = proto(BASE_WS, st.o_gZ[k - 1], F);
+    with_mask(gz.proto, st.o_F[k - 1], F);
+    gz.proto.gamma_kind = SK_INV_KEEP_I;
+    s.push_back(gz);
+    GemmSpec gw;                 // dW_k = gZ_k^T F_{k-1}, db_k = column sums of gZ_k
+    gw.M = F; gw.N = F;
+    gw.segs.push_back(mkseg(KM(BASE_WS, st.o_gZ[k], F), KM(BASE_WS, st.o_F[k - 1], F), BT));
+    gw.proto = proto(BASE_G, st.W[k], F);
+    gw.proto.epi |= EPI_ROWSUM_A; gw.proto.bias_base = BASE_G; gw.proto.bias_off = (int32_t)st.bias[k];
+    s.push_back(gw);
+}
+
+void add_stack_forward(Builder &b, const SharedStack &st, int group, int BT, int F) {
+    for (int k = 2; k <= st.L; ++k) { std::vector<GemmSpec> s{spec_shared_layer(st, k, BT, F)}; b.add_gemm_phase(group, s); }
+}
+
+void add_stack_backward(Builder &b, const SharedStack &st, int group, int BT, int F) {
+    for (int k = st.L; k >= 2; --k) { std::vector<GemmSpec> s; push_shared_layer_back(s, st, k, BT, F); b.add_gemm_phase(group, s); }
+}
+
 // bf16 twins (TA3N_FLAG_BF16_STORE).  extra_produced: ws spans whose twin a non-GEMM kernel of the fused step keeps current.
 void add_bf16_twins(ta3n_plan &p, Builder &b, Geom &g, int BT, int D, const std::vector<Span> &extra_produced,
                     const std::vector<Span> &gemm_only = {}) {
@@ -736,6 +823,7 @@ int build_plan_avgpool(ta3n_plan &p, std::string &err) {
     // live parameters first (the all-reduce / optimiser operand), then the rest of the reference's state_dict for this configuration
     b.add_linear("fc_feature_shared_source", F, D, true);              // models.py:141
     p.first_floats = p.param_floats;
+    add_stack_params(b, shared_layers(c), F);                          // --add_fc: :145-153
     b.add_linear("fc_classifier_video_source", C, F, true);            // :272 (feat_aggregated_dim = F, :246-247)
     p.live_floats = p.param_floats;
     b.add_linear("fc_feature_source", F, F, false);
@@ -760,6 +848,8 @@ int build_plan_avgpool(ta3n_plan &p, std::string &err) {
     g.o_Y = (int32_t)b.add_region("Y", (int64_t)B * C);
     g.o_gY = (int32_t)b.add_region("gY", (int64_t)B * C);
     g.o_gZ1 = (int32_t)b.add_region("gZ1", (int64_t)BT * F);
+    SharedStack st;
+    lay_out_stack(p, b, st, BT, F, g.o_F1, g.o_gZ1);
     g.o_zeros = (int32_t)b.add_region("zeros", 64);
     g.o_ones = (int32_t)b.add_region("ones", (int64_t)BT * 4);
     if (g.o_ones != g.o_zeros + 64) { err = "internal: ones must follow zeros"; return TA3N_ERR_INVALID; }
@@ -790,7 +880,7 @@ int build_plan_avgpool(ta3n_plan &p, std::string &err) {
             s.split = 2;
         } else
         s.segs.push_back(mkseg(KC(BASE_X, 0, D), KC(BASE_P, Wsh, D), D));
-        s.proto = proto(BASE_WS, g.o_F1, F);
+        s.proto = proto(BASE_WS, st.o_F[1], F);       // (--add_fc > 1: the first of the stacked layers' outputs)
         with_bias(s.proto, bsh);
         s.proto.epi |= EPI_RELU | EPI_DROP_I;
         s.proto.gamma_kind = SK_INV_KEEP_I;
@@ -799,9 +889,9 @@ int build_plan_avgpool(ta3n_plan &p, std::string &err) {
     };
     auto grads = [&]() {
         std::vector<GemmSpec> s;
-        GemmSpec gw;             // dWsh = gZ1^T X, dbsh = column sums of gZ1
+        GemmSpec gw;             // dWsh = gZ1^T X, dbsh = column sums of gZ1 (of the first layer's gradient with --add_fc > 1)
         gw.M = F; gw.N = D;
-        gw.segs.push_back(mkseg(KM(BASE_WS, g.o_gZ1, F), KM(BASE_X, 0, D), BT));
+        gw.segs.push_back(mkseg(KM(BASE_WS, st.o_gZ[1], F), KM(BASE_X, 0, D), BT));
         gw.proto = proto(BASE_G, Wsh, D);
         gw.proto.epi |= EPI_ROWSUM_A; gw.proto.bias_base = BASE_G; gw.proto.bias_off = (int32_t)bsh;
         s.push_back(gw);
@@ -816,11 +906,13 @@ int build_plan_avgpool(ta3n_plan &p, std::string &err) {
     for (int group : {0, 4}) {           // ta3n_forward / first part of ta3n_train_step
         std::vector<GemmSpec> s{spec_F1()};
         b.add_gemm_phase(group, s);
+        add_stack_forward(b, st, group, BT, F);
         b.add_simple_phase(PH_POOL_CLS, group);
         if (group == 4) b.sum8_pending(g.o_losses, g.o_loss_part, B);
-        if (group == 4) { auto q = grads(); b.add_gemm_phase(4, q); }
+        if (group == 4) { add_stack_backward(b, st, 4, BT, F); auto q = grads(); b.add_gemm_phase(4, q); }
     }
     b.sum8_pending(g.o_losses, g.o_loss_part, B);
+    add_stack_backward(b, st, 2, BT, F);
     { auto q = grads(); b.add_gemm_phase(2, q); }   // ta3n_backward (also adds up the loss partials for logging)
     b.add_simple_phase(PH_GRAD_NORM, 3);
     b.add_simple_phase(PH_SGD, 3);
@@ -878,6 +970,7 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     };
     b.add_linear("fc_feature_shared_source", F, D, true);              // models.py:141
     p.first_floats = p.param_floats;
+    add_stack_params(b, shared_layers(c), F);                          // --add_fc: :145-153
     lin("fc_feature_domain", F, F, live_frm);                          // :161
     lin("fc_classifier_domain", 2, F, live_frm);                       // :170
     lin("fc_feature_domain_video", F, F, live_vid);                    // :267 (feat_aggregated_dim = F)
@@ -930,6 +1023,8 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     g.o_gVt = (int32_t)b.add_region("gVt", (int64_t)B * F);
     g.o_gRa = (int32_t)b.add_region("gRa", live_frm ? (int64_t)BT * F : 4);   // gVt / T spread over the segments
     g.o_gZ1 = (int32_t)b.add_region("gZ1", (int64_t)BT * F);
+    SharedStack st;
+    lay_out_stack(p, b, st, BT, F, g.o_F1, g.o_gZ1);
     g.o_attn = (int32_t)b.add_region("attn", 4); g.o_gattn = (int32_t)b.add_region("g_attn", 4);
     const int64_t Wcv2 = mcd ? P("fc_classifier_video_source_2.weight") : 0, bcv2 = mcd ? P("fc_classifier_video_source_2.bias") : 0;
     if (feat_grads) g.o_gV_ext = (int32_t)b.add_region("gV_ext", (int64_t)B * F);
@@ -988,7 +1083,7 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
             with_bias(s.proto, bsh);
             return s;
         }
-        s.proto = proto(BASE_WS, g.o_F1, F);
+        s.proto = proto(BASE_WS, st.o_F[1], F);       // (--add_fc > 1: the first of the stacked layers' outputs)
         with_bias(s.proto, bsh);
         s.proto.epi |= EPI_RELU | EPI_DROP_I;
         s.proto.gamma_kind = SK_INV_KEEP_I;
@@ -1014,6 +1109,7 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     auto forward = [&](int group) {
         { std::vector<GemmSpec> s{spec_F1()}; b.add_gemm_phase(group, s); }
         if (bn_shared) b.add_simple_phase(PH_BN_FWD, group);
+        add_stack_forward(b, st, group, BT, F);
         if (live_frm) { std::vector<GemmSpec> s{fwd(BT, F, F, g.o_F1, Wfd, bfd, g.o_Hf, true)}; b.add_gemm_phase(group, s); }   // models.py:458-459
         b.add_simple_phase(PH_POOL_AVG_FWD, group);
         {
@@ -1071,8 +1167,9 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
             std::vector<GemmSpec> s{gz};
             b.add_gemm_phase(group, s);
         }
+        add_stack_backward(b, st, group, BT, F);
         if (bn_shared) b.add_simple_phase(PH_BN_BWD, group);
-        { std::vector<GemmSpec> s{wgrad(F, D, BT, bn_shared ? g.o_gZ0 : g.o_gZ1, F, BASE_X, 0, D, Wsh, bsh)}; b.add_gemm_phase(group, s); }
+        { std::vector<GemmSpec> s{wgrad(F, D, BT, bn_shared ? g.o_gZ0 : st.o_gZ[1], F, BASE_X, 0, D, Wsh, bsh)}; b.add_gemm_phase(group, s); }
     };
     forward(0);
     b.add_simple_phase(PH_LOSS, 1);
@@ -1135,6 +1232,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
     if (c.xcd_aware < 0 || c.xcd_aware > 3) { err = "xcd_aware must be 0, 1, 2 or 3"; return TA3N_ERR_INVALID; }
     const int B = Bs + Bt, BT = B * T, NR = T - 1;
     if ((int64_t)BT * D >= (1ll << 31) || (int64_t)BT * F >= (1ll << 31)) { err = "problem too large for 32-bit offsets"; return TA3N_ERR_INVALID; }
+    { const std::string e = shared_layers_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     if (c.aggregation == TA3N_AGG_AVGPOOL)      // source-only: the fused fast path (BASELINE configs[0]); with adversarial branches or a module-path option: the general one
         return (c.flags & (TA3N_FLAG_ADV_RELATION | TA3N_FLAG_ADV_VIDEO | TA3N_FLAG_ADV_FRAME | TA3N_FLAG_MCD | TA3N_FLAG_FEATURE_GRADS |
                            TA3N_FLAG_BN_SHARED)) ? build_plan_avgpool_general(p, err)
@@ -1169,6 +1267,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
     };
     b.add_linear("fc_feature_shared_source", F, D, true);              // models.py:141 (first: ta3n_train_step_after_update relies on it)
     p.first_floats = p.param_floats;
+    add_stack_params(b, shared_layers(c), F);                          // --add_fc: :145-153 (updated by the first launch's side workgroups)
     lin("fc_feature_domain", F, F, live_frm);                          // :161
     lin("fc_classifier_domain", 2, F, live_frm);                       // :170
     for (int j = 0; j < NR; ++j)                                       // TRNmodule.py:44-54
@@ -1247,6 +1346,8 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
     g.o_gR = (int32_t)b.add_region("gR", (int64_t)B * NR * NB);
     g.o_gZ = (int32_t)b.add_region("gZ", (int64_t)B * NT * NB);
     g.o_gZ1 = (int32_t)b.add_region("gZ1", (int64_t)BT * F);
+    SharedStack st;
+    lay_out_stack(p, b, st, BT, F, g.o_F1, g.o_gZ1);
     if (feat_grads) g.o_gV_ext = (int32_t)b.add_region("gV_ext", (int64_t)B * NB);
     if (bn_shared) {
         g.o_Z0 = (int32_t)b.add_region("Z0", (int64_t)BT * F);
@@ -1326,7 +1427,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
             with_bias(s.proto, bsh);
             return s;
         }
-        s.proto = proto(BASE_WS, g.o_F1, F);
+        s.proto = proto(BASE_WS, st.o_F[1], F);       // (--add_fc > 1: the first of the stacked layers' outputs)
         with_bias(s.proto, bsh);
         s.proto.epi |= EPI_RELU | EPI_DROP_I;
         s.proto.gamma_kind = SK_INV_KEEP_I;
@@ -1515,7 +1616,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
     auto push_shared_fc_wgrad = [&](std::vector<GemmSpec> &s) {   // shared frame FC weight grad (no input gradient: the features are data)
         GemmSpec gw;
         gw.M = F; gw.N = D;
-        gw.segs.push_back(mkseg(KM(BASE_WS, bn_shared ? g.o_gZ0 : g.o_gZ1, F), KM(BASE_X, 0, D), BT));   // (behind the BatchNorm with use_bn)
+        gw.segs.push_back(mkseg(KM(BASE_WS, bn_shared ? g.o_gZ0 : st.o_gZ[1], F), KM(BASE_X, 0, D), BT));   // (behind the BatchNorm with use_bn)
         gw.proto = proto(BASE_G, Wsh, D);
         gw.proto.epi |= EPI_ROWSUM_A; gw.proto.bias_base = BASE_G; gw.proto.bias_off = (int32_t)bsh;   // dbsh
         s.push_back(gw);
@@ -1524,6 +1625,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
     // ================= forward (group 0) =================
     { std::vector<GemmSpec> s{spec_F1()}; b.add_gemm_phase(0, s); }
     if (bn_shared) b.add_simple_phase(PH_BN_FWD, 0);
+    add_stack_forward(b, st, 0, BT, F);
     {   // F2
         std::vector<GemmSpec> s{spec_Hf()};
         for (int t = 0; t < NT; ++t) s.push_back(spec_Z(t));
@@ -1556,6 +1658,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
     b.add_simple_phase(PH_POOL_BWD, 2);   // gPrT (attention path), gRa = (1+w) gVt, gHr
     { std::vector<GemmSpec> s; push_relation_level(s); b.add_gemm_phase(2, s); }    // Q5
     { std::vector<GemmSpec> s; push_trn_level(s); b.add_gemm_phase(2, s); }         // Q6
+    add_stack_backward(b, st, 2, BT, F);
     if (bn_shared) b.add_simple_phase(PH_BN_BWD, 2);
     { std::vector<GemmSpec> s; push_shared_fc_wgrad(s); b.add_gemm_phase(2, s); }   // Q7
     // ================= optimiser (group 3) =================
@@ -1583,6 +1686,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
             }
             if (!chain && group == 5) return;      // unchained: the pipelined variant only mirrors the first launch
             if (bn_shared) b.add_simple_phase(PH_BN_FWD, group);      // F1 = dropout_i(relu(BatchNorm_domain(Z0))), batch statistics
+            add_stack_forward(b, st, group, BT, F);      // --add_fc: behind the first launch, whose side workgroups update W_2 / W_3
             {
                 std::vector<GemmSpec> s{spec_Hf()};
                 for (int t = 0; t < NT; ++t) s.push_back(spec_Z(t));
@@ -1637,6 +1741,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
             }
             b.add_gemm_phase(4, s);
         }
+        add_stack_backward(b, st, 4, BT, F);
         if (bn_shared) b.add_simple_phase(PH_BN_BWD, 4);      // gZ0 + the BatchNorm weight / bias gradients from gZ1
         {
             std::vector<GemmSpec> s;
@@ -1695,6 +1800,7 @@ static int build_plan_once(ta3n_plan &p, std::string &err) {
             kept.push_back(Span{g.o_gZ0, g.o_gZ0 + (int64_t)BT * F});
         } else {
             gemm_only.push_back(Span{g.o_gZ1, g.o_gZ1 + (int64_t)BT * F});
+            for (int k = 1; k < st.L; ++k) gemm_only.push_back(Span{st.o_gZ[k], st.o_gZ[k] + (int64_t)BT * F});   // (--add_fc)
         }
         add_bf16_twins(p, b, g, BT, D, kept, gemm_only);
         if (p.ws_floats >= (1ll << 31)) { err = "workspace too large for 32-bit offsets"; return TA3N_ERR_INVALID; }

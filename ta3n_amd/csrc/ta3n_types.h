@@ -27,7 +27,7 @@ enum EpiFlags : uint32_t {
     EPI_ADD = 1u << 1,      // v = alpha*v + add[m][n]
     EPI_RELU = 1u << 2,     // v = max(v, 0)
     EPI_MASK = 1u << 3,     // v *= (aux[m][n] > 0)
-    EPI_DROP_I = 1u << 4,   // v *= keep_i(m*drop_ld + n)   (dropout_i stream)
+    EPI_DROP_I = 1u << 4,   // v *= keep_i(m*drop_ld + n + pad2)   (dropout_i stream)
     EPI_DROP_V = 1u << 5,   // v *= keep_v(...)
     EPI_SUMROWS8 = 1u << 6, // workgroup side job: ws[pad[0] + c] = sum_r ws[pad[1] + 8 r + c], r < pad[2], c < 8 (loss scalars of the fused step)
     EPI_COLSUM = 1u << 12,  // not a tile: c[n] = sum_{r < pad[1]} ws[pad[0] + r * pad[2] + n] for n in [n0, n_valid), rows added in order by
@@ -67,7 +67,7 @@ struct Task {
     int32_t bias_base, bias_off;
     int32_t aux_base, aux_off, aux_ld;   // mask operand
     int32_t add_base, add_off, add_ld;   // additive operand
-    int32_t drop_ld;                     // element id for dropout = m*drop_ld + n
+    int32_t drop_ld;                     // element id for dropout = m*drop_ld + n + pad2
     int32_t fan_count;                   // extra masked outputs (all in BASE_WS, ld = fan_ld)
     int32_t fan_ld;
     int32_t fan_mask_off[3];
@@ -84,7 +84,9 @@ struct Task {
     // a lower index in the launch.
     int32_t sig;                         // -1: nobody in this launch reads what this task writes
     int32_t wait_begin, wait_count;
-    int32_t pad2;
+    int32_t pad2;                        // EPI_DROP_I / EPI_DROP_V: element-id offset of the dropout stream.  0 for the shared frame FC and
+                                         // every other task; (k - 1) * B*T*F for the k-th stacked shared layer (ta3n_config.shared_fc_layers),
+                                         // so each layer's dropout_i mask is a stream of its own instead of a repeat of layer 1's
 };
 struct Wait { int32_t counter, target; };
 

@@ -72,6 +72,24 @@ def _hyper_dtype():
     return np, _HYPER_DTYPE
 
 
+def add_fc_refusal(add_fc: int, use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", chain: bool = False, split_k: int = 0,
+                   wgrads_late: bool = False, phase_tiles: bool = False) -> str:
+    """'' when --add_fc `add_fc` is built together with the other options, otherwise the message that refuses it (naming the
+    combination).  add_fc 2 / 3: TA3N / trn-m and TemPooling with use_bn none, no dis_DA / ens_DA, the default launch shapes."""
+    if add_fc < 1:
+        return "add at least one fc layer (models.py:137-138)"
+    if add_fc > 3:
+        return (f"--add_fc {add_fc}: built for 1, 2 and 3 (the reference builds no fourth layer, models.py:145-153, but shifts the "
+                f"place_dis slicing with add_fc, main.py:368-378)")
+    if add_fc == 1:
+        return ""
+    other = [what for what, on in ((f"--use_bn {use_bn}", use_bn != "none"), (f"--dis_DA {dis_DA}", dis_DA != "none"),
+                                   (f"--ens_DA {ens_DA}", ens_DA != "none"), ("chained launches (chain)", chain),
+                                   ("split_k", bool(split_k)), ("wgrads_late", wgrads_late),
+                                   ("explicit phase_tiles / tuned tile lists", phase_tiles)) if on]
+    return f"--add_fc {add_fc} together with {', '.join(other)} is not built" if other else ""
+
+
 class TrainEngine:
     """Device-resident state of one rank: flat parameters / gradients / momentum,
     workspace, static input buffers.  Source rows come first in every batch
@@ -86,9 +104,20 @@ class TrainEngine:
                  f32_split: bool = False, chain: Optional[bool] = None, grad_transport: Optional[str] = None,
                  dis_DA: str = "none", place_dis: Sequence[str] = ("N", "Y", "N"), alpha: float = 0.0, use_bn: str = "none",
                  ens_DA: str = "none", mu: float = 0.0, split_k: Optional[int] = None, sharded_update: Optional[bool] = None,
-                 peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False):
+                 peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False,
+                 add_fc: int = 1):
         if not torch.cuda.is_available():
             raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
+        # --add_fc 2 / 3 (models.py:145-153, 581-603): one or two more Linear(F, F) -> ReLU -> dropout_i layers on the shared frame FC
+        # (ta3n_config.shared_fc_layers: one more GEMM launch per layer in the forward and in the backward).  Built for use_bn none without
+        # the discrepancy / MCD terms, on the measured default launch shapes (the tuned tile lists are indexed by the one-layer order).
+        add_fc_refused = add_fc_refusal(add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA, chain=bool(chain),
+                                        split_k=int(os.environ.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k),
+                                        wgrads_late=bool(wgrads_late), phase_tiles=bool(phase_tiles and any(phase_tiles)) or
+                                        bool(os.environ.get("TA3N_PHASE_TILES")))
+        if add_fc_refused:
+            raise NotImplementedError(add_fc_refused) if add_fc >= 1 else ValueError(add_fc_refused)
+        self.add_fc = int(add_fc)
         if flags is None:        # default: the full TA3N configuration for trn-m, the source-only one (BASELINE configs[0]) for avgpool
             flags = ALL_FLAGS if aggregation == "trn-m" else 0
         # dis_DA DAN / JAN (main.py:452-505, loss.py:46-120): a discrepancy loss on the class logits (feat[0]) and / or the pooled
@@ -156,7 +185,7 @@ class TrainEngine:
         if aggregation == "avgpool":     # TemPooling: no relation features, no attention (use_attn none in the reference's script); with
             # use_target none (BASELINE configs[0]) the caller passes no adversarial flag either (flags_from_options)
             flags &= ~(_lib.FLAG_ATTN_ENTROPY | _lib.FLAG_TRANS_ATTN)
-        if phase_tiles is None and tile_config == 0 and aggregation == "trn-m":      # measured choices for the benchmarked shapes
+        if phase_tiles is None and tile_config == 0 and aggregation == "trn-m" and add_fc == 1:      # measured choices for the benchmarked shapes
             from .tuning import tuned_phase_tiles
             phase_tiles = tuned_phase_tiles(batch_source + batch_target, num_segments, feature_dim, min(fc_dim, feature_dim),
                                             self.bf16, self.bf16_store, split=bool(flags & _lib.FLAG_F32_SPLIT))
@@ -166,14 +195,15 @@ class TrainEngine:
                 i, code = item.split(":")
                 phase_tiles[int(i)] = int(code)
         if chain is None:        # chained launches (ta3n_config.chain): the fused trn-m step in 5 launches instead of 8
-            chain = os.environ.get("TA3N_CHAIN", "0") == "1" and aggregation == "trn-m" and fused
+            chain = os.environ.get("TA3N_CHAIN", "0") == "1" and aggregation == "trn-m" and fused and add_fc == 1
         self._flags = int(flags)
         self.plan = _lib.Plan(batch_source, batch_target, num_segments, feature_dim, fc_dim, num_class, flags,
                               tile_config=tile_config, phase_tiles=list(phase_tiles or []), xcd_aware=xcd_aware,
                               aggregation=_lib.AGG_AVGPOOL if aggregation == "avgpool" else _lib.AGG_TRN_M,
                               wgrads_late=int(wgrads_late), chain=int(chain),
                               cost_model=int(os.environ.get("TA3N_COST_MODEL", "0")),
-                              split_k=int(os.environ.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k))
+                              split_k=int(os.environ.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k),
+                              shared_fc_layers=self.add_fc)
         self.chain = bool(chain)
         self.Bs, self.Bt, self.T, self.D, self.C = batch_source, batch_target, num_segments, feature_dim, num_class
         self.B = batch_source + batch_target

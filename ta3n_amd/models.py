@@ -10,7 +10,7 @@ HIP library or without a GPU raises).
 Supported configurations = the TA3N hot path and TemPooling:
 frame_aggregation='trn-m' (use_attn in {'TransAttn','none'}) or 'avgpool' (use_attn 'none': BASELINE configs[0] and the
 TemPooling + RevGrad rows), baseline_type='video', share_params='Y', use_bn='none', add_fc=1, ens_DA='none',
-use_attn_frame='none'.
+use_attn_frame='none'; add_fc 2 / 3 (models.py:145-153, 581-603) with use_bn 'none' and ens_DA 'none'.
 Anything else raises NotImplementedError at construction (several of those
 branches are broken in the reference itself).
 """
@@ -130,6 +130,12 @@ def _deliver_grads(model, plan, grads, fresh, unused, needs_grad) -> None:
         model._grad_live_elems_plan = plan
 
 
+def _lower_layers(model, reg, B, T) -> tuple:
+    """--add_fc > 1: the outputs of the shared layers below the last one, last first ([F_{k-1}, ..., F_1]: the order of the
+    reference's feature list, models.py:581-603); region "F1" holds the last layer's."""
+    return tuple(reg(f"F_l{k}", (B, T, -1)) for k in range(model.add_fc - 1, 0, -1))
+
+
 class _HipForward(torch.autograd.Function):
     """One autograd node for the whole forward; backward = ta3n_backward."""
 
@@ -168,18 +174,19 @@ class _HipForward(torch.autograd.Function):
         pr, pv, pf = reg("Pr", (B, NR, 2)), reg("Pv", (B, 2)), reg("Pf", (B, T, 2))
         v, f1 = reg("V", (B, -1)), reg("F1", (B, T, -1))
         y2 = reg("Y2", (B, Cn)) if model.ens_DA == 'MCD' else y.new_zeros(0)
+        lower = _lower_layers(model, reg, B, T)
         # the pooled video feature takes a gradient from the caller (dis_DA DAN / JAN on feat[1], main.py:452-505); the frame
         # features cannot be a loss operand in the reference either (loss.py:49 raises on 3-D features)
-        ctx.mark_non_differentiable(f1)
+        ctx.mark_non_differentiable(f1, *lower)
         if model.ens_DA != 'MCD':
             ctx.mark_non_differentiable(y2)
         if not model._attn_on:
             ctx.mark_non_differentiable(attn)
         ctx.set_materialize_grads(False)      # an output that feeds no loss arrives as None in backward (see there)
-        return attn, y, pr, pv, pf, v, f1, y2
+        return (attn, y, pr, pv, pf, v, f1, y2) + lower
 
     @staticmethod
-    def backward(ctx, g_attn, g_y, g_pr, g_pv, g_pf, g_v, g_f1, g_y2):
+    def backward(ctx, g_attn, g_y, g_pr, g_pv, g_pf, g_v, g_f1, g_y2, *g_lower):
         model, plan, ws = ctx.model, ctx.plan, ctx.ws
         dev = ws.device
 
@@ -251,14 +258,15 @@ class _HipForwardAvg(torch.autograd.Function):
         y, pv, pf = reg("Y", (B, Cn)), reg("Pv", (B, 2)), reg("Pf", (B, T, 2))
         v, f1 = reg("V", (B, -1)), reg("F1", (B, T, -1))
         y2 = reg("Y2", (B, Cn)) if model.ens_DA == 'MCD' else y.new_zeros(0)
-        ctx.mark_non_differentiable(f1)            # (V takes the caller's gradient: dis_DA on feat[1])
+        lower = _lower_layers(model, reg, B, T)
+        ctx.mark_non_differentiable(f1, *lower)    # (V takes the caller's gradient: dis_DA on feat[1])
         if model.ens_DA != 'MCD':
             ctx.mark_non_differentiable(y2)
         ctx.set_materialize_grads(False)
-        return y, pv, pf, v, f1, y2
+        return (y, pv, pf, v, f1, y2) + lower
 
     @staticmethod
-    def backward(ctx, g_y, g_pv, g_pf, g_v, g_f1, g_y2):
+    def backward(ctx, g_y, g_pv, g_pf, g_v, g_f1, g_y2, *g_lower):
         model, plan, ws = ctx.model, ctx.plan, ctx.ws
         dev = ws.device
         for name, g in (("gY", g_y), ("gPv", g_pv), ("gPf", g_pf), ("gV_ext", g_v)) + ((("gY2", g_y2),) if model.ens_DA == 'MCD' else ()):
@@ -307,7 +315,10 @@ class VideoModel(nn.Module):
         if not before_softmax: unsupported.append("before_softmax=False")
         if add_fc < 1:
             raise ValueError('add at least one fc layer')          # models.py:137-138
-        if add_fc != 1: unsupported.append(f"add_fc={add_fc}")
+        if add_fc > 3: unsupported.append(f"add_fc={add_fc} (built: 1, 2, 3)")
+        elif add_fc > 1:       # models.py:145-153, 581-603: built for the configurations without BatchNorm / MCD
+            if use_bn != 'none': unsupported.append(f"add_fc={add_fc} with use_bn={use_bn!r}")
+            if ens_DA != 'none': unsupported.append(f"add_fc={add_fc} with ens_DA={ens_DA!r}")
         if unsupported:
             raise NotImplementedError("ta3n_amd.VideoModel implements the TA3N hot path only; unsupported: " +
                                       ", ".join(unsupported))
@@ -343,6 +354,10 @@ class VideoModel(nn.Module):
             return m
 
         self.fc_feature_shared_source = lin(self.feature_dim, F_)        # :141
+        if add_fc > 1:
+            self.fc_feature_shared_2_source = lin(F_, F_)                # :145-148
+        if add_fc > 2:
+            self.fc_feature_shared_3_source = lin(F_, F_)                # :150-153
         self.fc_feature_source = lin(F_, F_)                             # :156 (unused in forward, kept for checkpoints)
         if use_bn != 'none':                                             # :194-198 AdaBN (ICLRW 2017): BN for source / target
             self.bn_shared_S = nn.BatchNorm1d(F_)                        # the two the trn-m forward uses (:515-516, 569-570)
@@ -426,7 +441,8 @@ class VideoModel(nn.Module):
         key = (Bs, Bt, T)
         if key not in self._plans:
             self._plans[key] = _lib.Plan(Bs, Bt, T, self.feature_dim, self._feat_dim_F, self.num_class,
-                                         self._flags(), aggregation=_lib.AGG_AVGPOOL if self._avg else _lib.AGG_TRN_M)
+                                         self._flags(), aggregation=_lib.AGG_AVGPOOL if self._avg else _lib.AGG_TRN_M,
+                                         shared_fc_layers=self.add_fc)
         return self._plans[key]
 
     def _ws_template(self, plan: _lib.Plan) -> torch.Tensor:
@@ -530,7 +546,8 @@ class VideoModel(nn.Module):
     def forward(self, input_source, input_target, beta, mu, is_train, reverse):
         """models.py:545-722.  Returns (attn_s, out_s, out_s2, pred_domain_s, feat_s, attn_t, out_t,
         out_t2, pred_domain_t, feat_t) with pred_domain = [relation [B,T-1,2], video [B,2],
-        frame [B,T,2]] and feat = [class logits, video feature V, frame features F1]."""
+        frame [B,T,2]] and feat = [class logits, video feature V, frame features F1] (add_fc > 1: [logits, V, F_k, ..., F_1], the
+        outputs of the stacked shared layers, last first)."""
         if not torch.cuda.is_available():
             raise _lib.Ta3nError("ta3n_amd.VideoModel.forward needs a HIP device; there is no CPU fallback")
         if self.use_bn != 'none' and float(self.alpha.detach()) != 1.0:
@@ -554,17 +571,17 @@ class VideoModel(nn.Module):
         s, t = slice(0, Bs), slice(Bs, Bs + Bt)
         if self._avg:
             with torch.cuda.device(device):
-                y, pv, pf, v, f1, y2 = _HipForwardAvg.apply(self, input_source, input_target, list(beta), self.training,
-                                                            float(mu) if reverse else None, *params)
+                y, pv, pf, v, f1, y2, *lower = _HipForwardAvg.apply(self, input_source, input_target, list(beta), self.training,
+                                                                    float(mu) if reverse else None, *params)
             if self.ens_DA != 'MCD':
                 y2 = y
             # models.py:627-628 (attn placeholder = first feature column), :697-708 (the relation slot repeats the video logits)
-            return (v[s][:, 0], y[s], y2[s], [pv[s], pv[s], pf[s]], [y[s], v[s], f1[s]],
-                    v[t][:, 0], y[t], y2[t], [pv[t], pv[t], pf[t]], [y[t], v[t], f1[t]])
+            return (v[s][:, 0], y[s], y2[s], [pv[s], pv[s], pf[s]], [y[s], v[s], f1[s]] + [f[s] for f in lower],
+                    v[t][:, 0], y[t], y2[t], [pv[t], pv[t], pf[t]], [y[t], v[t], f1[t]] + [f[t] for f in lower])
         with torch.cuda.device(device):
-            attn, y, pr, pv, pf, v, f1, y2 = _HipForward.apply(self, input_source, input_target, list(beta), self.training,
-                                                                float(mu) if reverse else None, *params)
+            attn, y, pr, pv, pf, v, f1, y2, *lower = _HipForward.apply(self, input_source, input_target, list(beta), self.training,
+                                                                        float(mu) if reverse else None, *params)
         out_s, out_t = y[s], y[t]
         out_s2, out_t2 = (y2[s], y2[t]) if self.ens_DA == 'MCD' else (out_s, out_t)      # models.py:713-720
-        return (attn[s], out_s, out_s2, [pr[s], pv[s], pf[s]], [y[s], v[s], f1[s]],
-                attn[t], out_t, out_t2, [pr[t], pv[t], pf[t]], [y[t], v[t], f1[t]])
+        return (attn[s], out_s, out_s2, [pr[s], pv[s], pf[s]], [y[s], v[s], f1[s]] + [f[s] for f in lower],
+                attn[t], out_t, out_t2, [pr[t], pv[t], pf[t]], [y[t], v[t], f1[t]] + [f[t] for f in lower])

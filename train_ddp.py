@@ -30,7 +30,7 @@ if ROOT not in sys.path:
 
 from ta3n_amd import checkpoint as ckpt  # noqa: E402
 from ta3n_amd import parallel  # noqa: E402
-from ta3n_amd.engine import TrainEngine, beta_dann, flags_from_options, lr_dann  # noqa: E402
+from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, lr_dann  # noqa: E402
 from ta3n_amd.models import ARCH_FEATURE_DIM  # noqa: E402
 from ta3n_amd.opts import parser  # noqa: E402
 
@@ -77,7 +77,9 @@ def validate_options(args, module_path: bool = False) -> None:
     need(args.use_attn in ("TransAttn", "none"), f"--use_attn {args.use_attn}")
     need(args.use_attn_frame == "none", f"--use_attn_frame {args.use_attn_frame}")
     need(args.share_params == "Y", "--share_params N")
-    need(args.add_fc == 1, f"--add_fc {args.add_fc}")
+    # --add_fc 2 / 3 (models.py:145-153, 581-603): TA3N / trn-m and TemPooling with use_bn none, without dis_DA / ens_DA
+    add_fc_msg = add_fc_refusal(args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA)
+    need(not add_fc_msg, add_fc_msg)
     need(args.modality == "RGB", f"modality {args.modality} (pre-extracted RGB features)")
     need(args.mu == 0 or args.ens_DA == "MCD", f"--mu {args.mu} (only used by --ens_DA MCD)")
     need(len(args.beta) == 3 and len(args.place_adv) == 3, "--beta and --place_adv take three values [relation, video, frame]")
@@ -149,7 +151,7 @@ def main():
                       clip=args.clip_gradient, device=dev, bf16=(args.arithmetic == "bf16"), bf16_store=(args.arithmetic == "bf16"),
                       f32_split=(args.arithmetic == "f32x3"), aggregation=args.frame_aggregation,
                       dis_DA=args.dis_DA, place_dis=args.place_dis, alpha=max(args.alpha, 0.0), use_bn=args.use_bn,
-                      ens_DA=args.ens_DA, mu=args.mu)
+                      ens_DA=args.ens_DA, mu=args.mu, add_fc=args.add_fc)
     from ta3n_amd.models import VideoModel
     torch.manual_seed(1)
     model = VideoModel(num_class, args.baseline_type, args.frame_aggregation, args.modality, train_segments=T,
