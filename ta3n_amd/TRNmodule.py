@@ -3,7 +3,7 @@
 
 Inside `VideoModel` the multi-scale relation network runs as one grouped GEMM
 launch of libta3n_hip.so (the per-tuple gather+concat of TRNmodule.py:60-63,
-75-77 is folded into the A-operand addressing; see csrc/ta3n_plan.cpp phase F2),
+75-77 is folded into the A-operand addressing; see csrc/ta3n_plan.cpp, TrnModel::spec_Z / phase F2 of add_unfused_lists),
 so this module's own `forward` is never called on main.py's path.
 """
 from __future__ import annotations
@@ -56,7 +56,7 @@ class RelationModuleMultiScale(nn.Module):
     def forward(self, input):
         """TRNmodule.py:58-82 on its own: input [B, T, D] -> [B, T-1, bottleneck].  Runs the SAME grouped tile-list launches the
         train step uses: forward = the tuple GEMMs (gather + concat folded into the operand addressing, bias + ReLU in the
-        epilogue; csrc/ta3n_plan.cpp: spec_Z), backward = the launch of the TRN weight gradients and the scatter-free input
+        epilogue; csrc/ta3n_plan.cpp: TrnModel::spec_Z), backward = the launch of the TRN weight gradients and the scatter-free input
         gradient (push_trn_wgrads / push_f1_grad) - on a plan of B source videos; the per-scale sum of the (at most 3) tuple
         activations and its fan-out back through their ReLU masks are the only things done here."""
         if not torch.cuda.is_available():

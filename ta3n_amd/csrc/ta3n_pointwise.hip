@@ -760,7 +760,7 @@ __device__ __forceinline__ BnRow bn_load(const float *__restrict__ row, int c0) 
 }
 __device__ __forceinline__ void bn_store(float *__restrict__ row, unsigned short *__restrict__ tw, int pair_delta, int c0, const BnRow &y) {
     *reinterpret_cast<float4 *>(row + c0) = make_float4(y.v[0], y.v[1], y.v[2], y.v[3]);
-    if (tw) {      // bf16 twin (TA3N_FLAG_BF16_STORE): the next GEMM launch reads it as an operand (ta3n_plan.cpp: add_bf16_twins)
+    if (tw) {      // bf16 twin (TA3N_FLAG_BF16_STORE): the next GEMM launch reads it as an operand (ta3n_plan_twins.cpp: add_bf16_twins)
         const unsigned h0 = pack_bf16(y.v[0], y.v[1]), h1 = pack_bf16(y.v[2], y.v[3]);
         *reinterpret_cast<uint2 *>(tw + c0) = make_uint2(h0, h1);
         if (pair_delta) *reinterpret_cast<uint2 *>(tw + c0 + 2 * (size_t)pair_delta) = make_uint2(pack_bf16_lo(y.v[0], y.v[1], h0), pack_bf16_lo(y.v[2], y.v[3], h1));
@@ -918,7 +918,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_shared_bwd_kernel(Geom g, Ptrs 
     const int dom = blockIdx.y, tid = threadIdx.x, cg = bn_column_group((int)blockIdx.x, (int)gridDim.x), c0 = cg * BN_COLS;
     const int row0 = dom == 0 ? 0 : g.Bs * g.T, n = dom == 0 ? g.Bs * g.T : g.Bt * g.T, F = g.F;
     // fused step: this workgroup's share of the gradient norm (sum of squares of the 2 x BN_COLS BatchNorm gradients it writes) goes to ITS
-    // slot at the end of ws["sumsq"] (ta3n_plan.cpp: the last 2 * gridDim.x slots) - the fused optimiser adds the slots in a fixed order
+    // slot at the end of ws["sumsq"] (ta3n_plan.cpp, bn_sumsq_slots: the last 2 * gridDim.x slots) - the fused optimiser adds the slots in a fixed order
     float *slot = g.n_sumsq > 0 ? ws + g.o_sumsq + g.n_sumsq - 2 * (int)gridDim.x + dom * (int)gridDim.x + cg : nullptr;
     if (n == 0) {
         if (slot && tid == 0) *slot = 0.f;

@@ -80,7 +80,7 @@ struct Task {
     // Chained launch (Phase.chain_off >= 0): several dependency levels in ONE launch.  A task whose output a later task of the
     // same launch reads increments counter `sig` once its stores are visible at agent scope; a task that reads such output first
     // waits until every (counter, target) pair of its wait list waits[wait_begin .. wait_begin + wait_count) is reached.  The plan
-    // builder derives both from the tasks' read / write spans (ta3n_plan.cpp: derive_chain); tasks only ever wait on tasks with
+    // builder derives both from the tasks' read / write spans (ta3n_plan_tiles.cpp: Builder::end_chain); tasks only ever wait on tasks with
     // a lower index in the launch.
     int32_t sig;                         // -1: nobody in this launch reads what this task writes
     int32_t wait_begin, wait_count;

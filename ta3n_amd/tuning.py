@@ -4,7 +4,7 @@ engine.autotune_phase_tiles does the measurement: every candidate tile for every
 A tile code is WM*100 + WN*10 + WK (waves of the workgroup in M, N and the in-workgroup K split), + 1000 * LDS stages for the
 bf16 kernels (5000 / 6000 / 7000: two / three / four HALF stages of 64 k, bf16-twin kernel), + 10000 / 20000 / 30000 for 2 row / 2 column / 2 x 2
 32x32 blocks per wave (bf16-twin kernel: 128x64, 64x128, 128x128 tiles; 46221 / 56221: 192x128 / 256x128, four waves, half stages).  Entries 0-9 are the forward / loss / backward launches of the unfused sequence, 10-15 the six GEMM launches of
-the fused step (ta3n_train_step); 0 = the plan builder's own choice (ta3n_plan.cpp: add_gemm_phase).
+the fused step (ta3n_train_step); 0 = the plan builder's own choice (ta3n_plan_tiles.cpp: Builder::choose_tiles).
 
 What decides a launch ("tile choice"): a CU fills its LDS at ~41 B/clk whatever the tile, so a launch wants (a) at
 least one workgroup per CU and (b) beyond that the largest tile, which brings the fewest operand bytes per flop; launches with
