@@ -170,7 +170,11 @@ typedef struct {
     int32_t train;           /* nn.Module.training: dropout active */
     int32_t reverse;         /* VideoModel.forward(..., reverse=True) (models.py:682-684): GradReverse(mu) on the video feature */
     float mu;                /* ... its weight (the MCD step's second forward, main.py:550) */
-    int32_t reserved[2];
+    int32_t bn_eval_target;  /* use_bn, train == 0 only: non-zero = EVERY row goes through the target domain's BatchNorm (bn_shared_T:
+                              * its affine pair and its running statistics).  main.validate's call, main.py:707: model(val_data,
+                              * val_data) scored on the target branch - the videos sit in the source rows here, so that is what
+                              * TrainEngine.evaluate_batch sets.  0: each half through its own BatchNorm.  Ignored in train mode. */
+    int32_t reserved[1];
 } ta3n_hyper;
 
 typedef struct ta3n_plan ta3n_plan;

@@ -63,7 +63,7 @@ class Hyper(C.Structure):
                 ("seed_i", C.c_uint32), ("seed_v", C.c_uint32), ("inv_n_cls", C.c_float), ("inv_n_rel", C.c_float),
                 ("inv_n_vid", C.c_float), ("inv_n_frm", C.c_float), ("inv_n_ent", C.c_float),
                 ("valid_source", C.c_int32), ("valid_target", C.c_int32), ("train", C.c_int32),
-                ("reverse", C.c_int32), ("mu", C.c_float), ("reserved", C.c_int32 * 2)]
+                ("reverse", C.c_int32), ("mu", C.c_float), ("bn_eval_target", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 class Feed(C.Structure):

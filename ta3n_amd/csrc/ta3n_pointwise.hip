@@ -811,6 +811,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_shared_fwd_kernel(Geom g, Ptrs 
     const int train = hy->train;
     const float p_drop = hy->p_drop_i;
     const uint32_t seed = hy->seed_i;
+    const int eval_target = hy->bn_eval_target;
     float w[BN_COLS], b[BN_COLS], run_m[BN_COLS], run_v[BN_COLS];
     {
         const float *run = ws + g.o_bn_run + (size_t)dom * 2 * F;
@@ -884,6 +885,19 @@ __global__ __launch_bounds__(BN_THREADS) void bn_shared_fwd_kernel(Geom g, Ptrs 
             }
         }
     } else {
+        // main.validate (main.py:707) scores the target branch of model(val_data, val_data): with Hyper::bn_eval_target set the source rows
+        // - where the validation videos sit - go through the TARGET domain's affine pair and running statistics too.  Read here, in the
+        // eval branch only: making the loads above wait for the step's scalars would put a round trip in front of every train-mode launch.
+        if (eval_target && dom == 0) {
+            const float *run = ws + g.o_bn_run + (size_t)2 * F;
+#pragma unroll
+            for (int e = 0; e < BN_COLS; ++e) {
+                w[e] = ptrs.p[g.p_bn_w[1] + c0 + e];
+                b[e] = ptrs.p[g.p_bn_b[1] + c0 + e];
+                run_m[e] = run[c0 + e];
+                run_v[e] = run[F + c0 + e];
+            }
+        }
 #pragma unroll
         for (int e = 0; e < BN_COLS; ++e) { mean[e] = run_m[e]; invstd[e] = 1.f / sqrtf(run_v[e] + BN_EPS); }
     }

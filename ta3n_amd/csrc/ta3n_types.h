@@ -134,7 +134,8 @@ struct Hyper {
     int32_t valid_source, valid_target, train;
     int32_t reverse;             // forward(..., reverse=True): GradReverse(mu) between dropout_v and the video heads (models.py:682-684)
     float mu;
-    int32_t reserved[2];
+    int32_t bn_eval_target;      // eval mode (train == 0): every row through the target domain's BatchNorm (main.validate, main.py:707)
+    int32_t reserved[1];
 };
 
 // Columns per workgroup of the two BatchNorm launches (TA3N_FLAG_BN_SHARED): a thread moves the BN_COLS columns of one row as one 16-byte

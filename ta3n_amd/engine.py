@@ -405,10 +405,12 @@ class TrainEngine:
     def set_hyper(self, beta: Sequence[float], gamma: float, lr: float, train: bool = True,
                   valid_source: Optional[int] = None, valid_target: Optional[int] = None,
                   global_source: Optional[int] = None, global_target: Optional[int] = None,
-                  seed: Optional[int] = None, upload: bool = True, raw_seeds: Optional[Sequence[int]] = None) -> None:
+                  seed: Optional[int] = None, upload: bool = True, raw_seeds: Optional[Sequence[int]] = None,
+                  bn_eval_target: int = 0) -> None:
         """Per-step scalars.  global_* are the job-wide valid video counts (all ranks):
         losses are means over the GLOBAL batch like the reference's DataParallel gather
-        (main.py:446, 533; loss.py:24), so ranks divide by global counts and gradients are SUMMED."""
+        (main.py:446, 533; loss.py:24), so ranks divide by global counts and gradients are SUMMED.
+        bn_eval_target (use_bn, train=False only): every row through the target domain's BatchNorm (ta3n_hyper.bn_eval_target)."""
         h = self._hyper
         ns = self.Bs if valid_source is None else valid_source
         nt = self.Bt if valid_target is None else valid_target
@@ -425,6 +427,7 @@ class TrainEngine:
         for k, v in parallel.loss_normalisers(gs, gt, self.T).items():
             setattr(h, k, v)
         h.valid_source, h.valid_target, h.train = int(ns), int(nt), int(bool(train))
+        h.bn_eval_target = int(bn_eval_target)
         self._global_source, self._global_target = int(gs), int(gt)
         if not upload:      # the caller delivers self._hyper another way (ta3n_sgd_step_next)
             return
@@ -1072,14 +1075,18 @@ class TrainEngine:
     # ---- validation (main.validate, main.py:669-761) ----
     def evaluate_batch(self, val_data: torch.Tensor, val_label: torch.Tensor, reset: bool = False) -> None:
         """Forward in eval mode (no dropout, beta = 0: main.py:707) on up to batch_source videos and accumulate
-        loss / top-1 / top-5 / confusion matrix on the device; read them with eval_results()."""
+        loss / top-1 / top-5 / confusion matrix on the device; read them with eval_results().
+        The reference scores the TARGET branch of model(val_data, val_data) (main.py:707-712): with use_bn the videos - which sit in the
+        source rows here - go through bn_shared_T, its affine pair and its running statistics (ta3n_hyper.bn_eval_target).
+        An update that train_step_pipelined / train_steps left pending is applied first: the parameters scored are current."""
         n = val_data.shape[0]
         if n > self.Bs:
             raise ValueError(f"at most batch_source = {self.Bs} validation videos per call")
+        self.flush()
         self.X[: n * self.T].copy_(val_data.reshape(-1, self.D), non_blocking=True)
         self.refresh_bf16(x=True)      # (the forward launches of a twin plan read the input's bf16 twin - since round 6 the unfused lists do too)
         self._labels[:n].copy_(val_label.to(torch.int32), non_blocking=True)
-        self.set_hyper([0.0, 0.0, 0.0], 0.0, 0.0, train=False, valid_source=n, valid_target=0)
+        self.set_hyper([0.0, 0.0, 0.0], 0.0, 0.0, train=False, valid_source=n, valid_target=0, bn_eval_target=1)
         self.forward()
         _lib.check(self._L.ta3n_eval_metrics(self.plan.handle, self.ws.data_ptr(), n, int(reset), self._stream()), "ta3n_eval_metrics")
 

@@ -446,6 +446,8 @@ class Interp:
                 run = self.r(g.o_bn_run + dom * 2 * F, (2, F))      # nn.BatchNorm1d's buffer update on the device (momentum 0.1, unbiased variance)
                 run[0] = 0.9 * run[0] + 0.1 * mean; run[1] = 0.9 * run[1] + 0.1 * var * (n / max(n - 1, 1))
             else:
+                if h.get("bn_eval_target", 0):      # main.validate (main.py:707): every row through the target domain's BatchNorm
+                    dom, pw, pb = 1, g.p_bn_w1, g.p_bn_b1
                 run = self.r(g.o_bn_run + dom * 2 * F, (2, F)); mean = run[0]; inv = 1.0 / np.sqrt(run[1] + 1e-5)
             y = np.maximum((z - mean) * inv * self.P[pw:pw + F] + self.P[pb:pb + F], 0)
             if h["train"] and h["p_drop_i"] > 0:
