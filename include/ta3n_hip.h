@@ -84,6 +84,17 @@ typedef enum {
  * without converting anything in the K loop; the others keep splitting fp32 operands in registers.  Same products, other
  * summation order inside the MFMAs.  ta3n_train_steps_fused_update is not built for it (ta3n_has_fused_update returns 0). */
 #define TA3N_FLAG_F32_SPLIT      (1u << 10)
+/* use_attn_frame=='TransAttn' together with use_attn=='TransAttn' on trn-m (models.py:368-377, 612-614): every frame feature is scaled
+ * by 1 + w, w = 1 - H(softmax(frame-discriminator logits)), before it enters the TRN; the weights are not detached, so the frame
+ * discriminator receives a gradient through them whatever place_adv says (its two layers are live parameters of the plan).  Regions:
+ * "F1a" [B*T][F] the attended features (what the TRN tuple products and weight gradients read; "F1" stays feat[2], un-attended),
+ * "attn_frame" [B*T] the weights, "gF1a" the TRN input gradient, "gPfT" the frame logit gradient including the attention term.
+ * Unfused entry points only (ta3n_has_fused_step returns 0): forward F1 | Hf | Pf | frame attention | tuples | ...; backward ... | TRN
+ * weight and input gradients | frame attention | {gHf, dWcd} | {dWfd, gradient at F1} | shared-FC weight gradient.  fp32 and
+ * TA3N_FLAG_BF16_MFMA (with or without TA3N_FLAG_BF16_STORE); TA3N_FLAG_FEATURE_GRADS may be set.  ta3n_plan_create refuses it by name
+ * without TA3N_FLAG_TRANS_ATTN (the reference fails there), on TA3N_AGG_AVGPOOL, and with TA3N_FLAG_F32_SPLIT, _MCD, _BN_SHARED,
+ * shared_fc_layers > 1, chain, split_k or wgrads_late. */
+#define TA3N_FLAG_FRAME_ATTN     (1u << 11)
 
 /* ta3n_config.aggregation */
 #define TA3N_AGG_TRN_M    0   /* 'trn-m': multi-scale TRN - the TA3N path (TRNmodule.py:27-86) */

@@ -191,21 +191,25 @@ def _fast_engine(model, optimizer, num_class):
     add_fc = int(getattr(args, "add_fc", 1))      # --add_fc 2 / 3: the stacked shared layers are part of the engine's step (use_bn none, no dis_DA / MCD)
     if add_fc != 1 and (dis or mcd or args.use_bn != "none" or add_fc not in (2, 3)):
         return None
+    # --use_attn_frame TransAttn: the engine's unfused launch lists with the two frame-attention launches (with --use_attn TransAttn, alone)
+    attn_frame = getattr(args, "use_attn_frame", "none")
+    if attn_frame != "none" and (attn_frame != "TransAttn" or args.use_attn != "TransAttn" or dis or mcd or args.use_bn != "none" or add_fc != 1):
+        return None
     g = optimizer.param_groups[0]
     # everything the engine is BUILT from: a later train() call with other options must not find an engine made for these
     key = (args.batch_size[0], args.batch_size[1], args.num_segments, args.fc_dim, num_class, tuple(args.place_adv), args.add_loss_DA,
            args.use_attn, args.adv_DA, args.use_target, float(args.dropout_i), float(args.dropout_v), float(g["momentum"]),
            float(g["weight_decay"]), None if args.clip_gradient is None else float(args.clip_gradient), args.use_bn,
-           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc)
+           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame)
     eng = m.__dict__.get("_main_fast_engine", {}).get(key)
     if eng is None:
         eng = TrainEngine(args.batch_size[0], args.batch_size[1], args.num_segments, m.feature_dim, args.fc_dim, num_class,
-                          flags=flags_from_options(args.place_adv, args.add_loss_DA, args.use_attn, args.adv_DA, args.use_target),
+                          flags=flags_from_options(args.place_adv, args.add_loss_DA, args.use_attn, args.adv_DA, args.use_target, use_attn_frame=attn_frame),
                           dropout_i=args.dropout_i, dropout_v=args.dropout_v, momentum=g["momentum"], weight_decay=g["weight_decay"],
                           clip=args.clip_gradient if args.clip_gradient is not None else 0.0, device=next(m.parameters()).device,
                           use_bn=args.use_bn, **(dict(dis_DA=args.dis_DA, place_dis=tuple(args.place_dis)) if dis else {}),
                           **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc)
-        if not eng.fused and not (dis or mcd):
+        if not eng.fused and not (dis or mcd or attn_frame != "none"):
             return None
         m.__dict__.setdefault("_main_fast_engine", {})[key] = eng
     return eng

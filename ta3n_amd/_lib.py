@@ -28,6 +28,7 @@ FLAG_BN_SHARED = 1 << 7        # use_bn AdaBN / AutoDIAL: BatchNorm1d per domain
 FLAG_BF16_MFMA = 1 << 8
 FLAG_BF16_STORE = 1 << 9
 FLAG_F32_SPLIT = 1 << 10       # fp32-grade contractions as three bf16 MFMAs on operands split hi + lo in registers ("bf16x3")
+FLAG_FRAME_ATTN = 1 << 11      # use_attn_frame TransAttn: frame features scaled by 1 + (1 - H(frame-discriminator softmax)) in front of the TRN (regions F1a, attn_frame); unfused entry points
 AGG_TRN_M, AGG_AVGPOOL = 0, 1
 
 # every symbol include/ta3n_hip.h declares (tests check the export list)

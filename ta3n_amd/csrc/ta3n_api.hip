@@ -71,6 +71,14 @@ Ptrs make_ptrs(const ta3n_plan *p, const float *x, const float *params, float *g
     return Ptrs{x, params, grads, ws, (ws && o >= 0) ? ws + o : nullptr};
 }
 
+// the two frame-attention launches (TA3N_FLAG_FRAME_ATTN): their regions have no Geom field, the builder left the offsets in the plan
+int launch_frame_attn(const ta3n_plan *p, int kind, const Ptrs &ptrs, hipStream_t stream) {
+    const ta3n_plan::FrameAttn &o = p->frame_attn;
+    if (o.F1a < 0 || o.attn < 0 || o.gF1a < 0 || o.gFs < 0 || o.gPfT < 0) return -1;
+    return kind == PH_FRAME_ATTN_FWD ? launch_frame_attn_fwd(p->geom, ptrs, o.F1a, o.attn, stream)
+                                     : launch_frame_attn_bwd(p->geom, ptrs, o.gF1a, o.gFs, o.gPfT, stream);
+}
+
 int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float *momentum, hipStream_t stream,
               hipEvent_t join_after_first = nullptr, int first_launch = 0, int n_launches = 1 << 30,
               const SgdSide *side = nullptr) {
@@ -102,6 +110,7 @@ int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float
             case PH_POOL_AVG_BWD: rc = launch_pool_avg_bwd(p->geom, ptrs, stream); break;
             case PH_BN_FWD: rc = launch_bn_shared_fwd(p->geom, ptrs, stream); break;
             case PH_BN_BWD: rc = launch_bn_shared_bwd(p->geom, ptrs, stream); break;
+            case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: rc = launch_frame_attn(p, ph.kind, ptrs, stream); break;
             case PH_GRAD_NORM: rc = launch_grad_norm(p->geom, ptrs.g, ptrs.ws, stream); break;
             case PH_SGD: rc = launch_sgd(p->geom, params_rw, ptrs.g, momentum, ptrs.ws, stream); break;
             default: rc = -1;
@@ -399,6 +408,7 @@ int ta3n_time_phases(ta3n_plan *p, const float *x, float *params, float *grads, 
                 case PH_POOL_AVG_BWD: lrc = launch_pool_avg_bwd(p->geom, ptrs, s); break;
                 case PH_BN_FWD: lrc = launch_bn_shared_fwd(p->geom, ptrs, s); break;
                 case PH_BN_BWD: lrc = launch_bn_shared_bwd(p->geom, ptrs, s); break;
+                case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: lrc = launch_frame_attn(p, ph.kind, ptrs, s); break;
                 case PH_GRAD_NORM: lrc = launch_grad_norm(p->geom, grads, ws, s); break;
                 case PH_SGD: lrc = launch_sgd(p->geom, params, grads, momentum, ws, s); break;
                 default: lrc = -1;

@@ -12,6 +12,7 @@
 //   Pr_j = W2_j relu(W1_j GRL(R_j) + b1_j) + b2_j              models.py:472-488
 //   w = 1 - H(softmax Pr);  V = sum_j (1+w_j) R_j;  Vd = drop_v(V)   models.py:351-357, 379-388, 651, 679
 //   Y = Wcv Vd + bcv;  Pv = Wcdv relu(Wdv GRL(Vd) + bdv) + bcdv      models.py:686, 464-470
+//   TA3N_FLAG_FRAME_ATTN: wf = 1 - H(softmax Pf);  F1a = (1 + wf) F1 replaces F1 in Z_t             models.py:368-377, 612-614
 #include "ta3n_plan_builder.h"
 
 #include <cstdlib>
@@ -556,8 +557,13 @@ struct TrnModel {
     // keeps grad None and is skipped by SGD (no weight decay either): the frame discriminator is live only with its adversarial loss
     // (place_adv[2], main.py:508-538), the video discriminator with its loss (attentive entropy needs it too, and the plan requires ADV_VIDEO
     // for it), the relation discriminators with their loss OR the transferable attention, whose weights are not detached (models.py:351-357, 379-388).
+    // TA3N_FLAG_FRAME_ATTN (models.py:368-377, 612-614): the TRN reads F1a = (1 + wf) F1, wf from the frame discriminator's logits and not
+    // detached - so that discriminator is live whatever place_adv[2] says, its logits come BEFORE the tuple products and its backward
+    // AFTER the TRN input gradient (add_unfused_lists)
+    const bool frame_attn;
     const bool live_frm, live_vid, live_rel, mcd, feat_grads, bn_shared;
     const int ldZ, ldR, ldF;
+    int64_t o_F1a = -1, o_gF1a = -1, o_gFs = -1, o_gPfT = -1;   // frame attention: attended features, TRN input gradient, (1 + wf) gF1a, gPf + attention term
     HeadParams w;
     std::vector<int64_t> trnW, trnB, W1, B1, W2, B2;   // per scale j
     SharedStack st;
@@ -565,7 +571,8 @@ struct TrnModel {
     int split_f1_grad = 0;      // (set for the fused step's launches: ta3n_config.split_k)
 
     TrnModel(ta3n_plan &pl, const Dims &dm)
-        : p(pl), b(pl), g(pl.geom), c(pl.cfg), d(dm), NR(dm.T - 1), NT(pl.n_tuples), live_frm(c.flags & TA3N_FLAG_ADV_FRAME),
+        : p(pl), b(pl), g(pl.geom), c(pl.cfg), d(dm), NR(dm.T - 1), NT(pl.n_tuples), frame_attn(c.flags & TA3N_FLAG_FRAME_ATTN),
+          live_frm(c.flags & (TA3N_FLAG_ADV_FRAME | TA3N_FLAG_FRAME_ATTN)),
           live_vid(c.flags & TA3N_FLAG_ADV_VIDEO), live_rel(c.flags & (TA3N_FLAG_ADV_RELATION | TA3N_FLAG_TRANS_ATTN)), mcd(c.flags & TA3N_FLAG_MCD),
           feat_grads(c.flags & TA3N_FLAG_FEATURE_GRADS), bn_shared(c.flags & TA3N_FLAG_BN_SHARED), ldZ(NT * dm.NB), ldR(NR * dm.NB), ldF(dm.T * dm.F) {}
 
@@ -574,6 +581,8 @@ struct TrnModel {
     void add_params();
     bool lay_out_workspace(std::string &err);
     void add_unfused_lists();
+    void add_frame_attn_lists();
+    int64_t trn_input() const { return frame_attn ? o_F1a : g.o_F1; }   // what the tuple products and the TRN weight gradients read
     bool add_fused_step(std::string &err);
     void forward_levels(int group, const std::vector<Task> *side, std::string &cerr);
     std::vector<Task> update_side_tasks() const;
@@ -587,7 +596,8 @@ struct TrnModel {
     GemmSpec spec_Hv() const { return spec_linear(d.B, d.NB, d.NB, BASE_WS, g.o_Vd, d.NB, w.Wdv, w.bdv, g.o_Hv, d.NB, true); }    // video-discriminator hidden layer (:466-467)
     GemmSpec spec_Pv() const { return spec_linear(d.B, 2, d.NB, BASE_WS, g.o_Hv, d.NB, w.Wcdv, w.bcdv, g.o_Pv, 2, false); }   // video domain logits (:468)
     GemmSpec spec_gHv() const { return spec_masked_back(d.B, d.NB, g.o_gPv, w.Wcdv, g.o_Hv, g.o_gHv); }   // gHv = (gPv Wcdv) * [Hv>0]
-    GemmSpec spec_gHf() const { return spec_masked_back(d.BT, d.F, g.o_gPf, w.Wcd, g.o_Hf, g.o_gHf); }     // gHf = (gPf Wcd) * [Hf>0]
+    GemmSpec spec_gHf() const { return spec_masked_back(d.BT, d.F, frame_attn ? o_gPfT : g.o_gPf, w.Wcd, g.o_Hf, g.o_gHf); }     // gHf = (gPf Wcd) * [Hf>0]
+    GemmSpec spec_dWcd() const { return wgrad(2, d.F, d.BT, frame_attn ? o_gPfT : g.o_gPf, 2, g.o_Hf, d.F, w.Wcd, w.bcd); }              // dWcd = gPf^T Hf, dbcd
     GemmSpec wgrad(int M, int N, int K, int64_t g_off, int g_ld, int64_t x_off, int x_ld, int64_t dst, int64_t bias_dst) const {
         return spec_wgrad(M, N, K, g_off, g_ld, BASE_WS, x_off, x_ld, dst, bias_dst);
     }
@@ -611,6 +621,7 @@ struct TrnModel {
     }
     void push_trn_wgrads(std::vector<GemmSpec> &s, unsigned scale_mask = ~0u) const;
     void push_f1_grad(std::vector<GemmSpec> &s) const;
+    GemmSpec spec_gZ1_behind_frame_attn() const;
     void push_shared_fc_wgrad(std::vector<GemmSpec> &s) const {   // shared frame FC weight grad (no input gradient: the features are data); behind the BatchNorm with use_bn
         s.push_back(spec_wgrad(d.F, d.D, d.BT, bn_shared ? g.o_gZ0 : st.o_gZ[1], d.F, BASE_X, 0, d.D, w.Wsh, w.bsh));   // + dbsh
     }
@@ -622,7 +633,7 @@ GemmSpec TrnModel::spec_Z(int t) const {   // TRN tuple GEMM (TRNmodule.py:60-79
     z.M = d.B; z.N = NB;
     z.affinity = 300 + j;               // the tuples of scale j read the same W_j
     for (int pos = 0; pos < sl; ++pos)
-        z.segs.push_back(mkseg(KC(BASE_WS, g.o_F1 + (int64_t)tau(t, pos) * F, ldF),
+        z.segs.push_back(mkseg(KC(BASE_WS, trn_input() + (int64_t)tau(t, pos) * F, ldF),
                                KC(BASE_P, trnW[j] + (int64_t)pos * F, sl * F), F));
     z.proto = proto(BASE_WS, g.o_Zr + (int64_t)t * NB, ldZ);
     with_bias(z.proto, trnB[j]); z.proto.epi |= EPI_RELU;
@@ -669,7 +680,7 @@ void TrnModel::push_trn_wgrads(std::vector<GemmSpec> &s, unsigned scale_mask) co
             gw.affinity = 100 + j;      // every position of scale j reads the same gZ_t
             for (int t = p.tuple_first[j]; t < p.tuple_first[j + 1]; ++t)
                 gw.segs.push_back(mkseg(KM(BASE_WS, g.o_gZ + (int64_t)t * NB, ldZ),
-                                        KM(BASE_WS, g.o_F1 + (int64_t)tau(t, pos) * F, ldF), d.B));
+                                        KM(BASE_WS, trn_input() + (int64_t)tau(t, pos) * F, ldF), d.B));
             gw.proto = proto(BASE_G, trnW[j] + (int64_t)pos * F, sl * F);
             if (pos == 0) with_bias_grad(gw.proto, trnB[j]);   // db_j = sum_t column sums of gZ_t
             s.push_back(gw);
@@ -683,7 +694,9 @@ void TrnModel::push_f1_grad(std::vector<GemmSpec> &s) const {   // gradient at t
         GemmSpec gz;
         gz.M = d.B; gz.N = F;
         gz.affinity = 200 + f;          // the row panels of frame f read the same weight slabs (Wfd, W_j[:, pos] of every tuple that holds f)
-        gz.segs.push_back(mkseg(KC(BASE_WS, g.o_gHf + (int64_t)f * F, ldF), KM(BASE_P, w.Wfd, F), F, SK_NEG_BETA_FRM));
+        // (frame attention: the TRN input gradient alone, gF1a[:, f] = sum gZ_t W_j[:, pos] - the frame discriminator's share, the
+        // ReLU / dropout mask and the attention scale follow behind PH_FRAME_ATTN_BWD: spec_gZ1_behind_frame_attn)
+        if (!frame_attn) gz.segs.push_back(mkseg(KC(BASE_WS, g.o_gHf + (int64_t)f * F, ldF), KM(BASE_P, w.Wfd, F), F, SK_NEG_BETA_FRM));
         for (int t = 0; t < NT; ++t) {
             const int j = p.scale_id[t], sl = p.scale_len[t];
             for (int pos = 0; pos < sl; ++pos)
@@ -691,12 +704,30 @@ void TrnModel::push_f1_grad(std::vector<GemmSpec> &s) const {   // gradient at t
                     gz.segs.push_back(mkseg(KC(BASE_WS, g.o_gZ + (int64_t)t * NB, ldZ),
                                             KM(BASE_P, trnW[j] + (int64_t)pos * F, sl * F), NB));
         }
+        if (frame_attn) {
+            gz.proto = proto(BASE_WS, o_gF1a + (int64_t)f * F, ldF);
+            s.push_back(gz);
+            continue;
+        }
         gz.proto = proto(BASE_WS, g.o_gZ1 + (int64_t)f * F, ldF);
         with_mask(gz.proto, g.o_F1 + (int64_t)f * F, ldF);
         gz.proto.gamma_kind = SK_INV_KEEP_I;
         gz.split = split_f1_grad;
         s.push_back(gz);
     }
+}
+
+// frame attention: gZ1 = ( -beta2 gHf Wfd + (1 + wf) gF1a ) * [F1 > 0] / keep_i - the spec the avgpool model uses behind its pooling
+GemmSpec TrnModel::spec_gZ1_behind_frame_attn() const {
+    const int F = d.F;
+    GemmSpec gz;
+    gz.M = d.BT; gz.N = F;
+    gz.segs.push_back(mkseg(KC(BASE_WS, g.o_gHf, F), KM(BASE_P, w.Wfd, F), F, SK_NEG_BETA_FRM));
+    gz.proto = proto(BASE_WS, g.o_gZ1, F);
+    with_add(gz.proto, o_gFs, F);
+    with_mask(gz.proto, g.o_F1, F);
+    gz.proto.gamma_kind = SK_INV_KEEP_I;
+    return gz;
 }
 
 // ---- parameters: live first (they form the all-reduce / optimiser operand) ----
@@ -771,6 +802,15 @@ bool TrnModel::lay_out_workspace(std::string &err) {
     if (feat_grads) g.o_gV_ext = (int32_t)b.add_region("gV_ext", (int64_t)B * NB);
     if (bn_shared) add_bn_regions(p, b, g, d);
     if (mcd) add_mcd_regions(b, g, d);
+    if (frame_attn) {
+        o_F1a = b.add_region("F1a", (int64_t)BT * F);
+        const int64_t o_attn = b.add_region("attn_frame", BT);
+        o_gF1a = b.add_region("gF1a", (int64_t)BT * F);
+        o_gPfT = b.add_region("gPfT", (int64_t)BT * 2);
+        // (1 + wf) gF1a, the additive base of the gradient at F1: in gRa - free once the relation level has read it - when it fits
+        o_gFs = (int64_t)B * NR * NB >= (int64_t)BT * F ? (int64_t)g.o_gRa : b.add_region("gF1s", (int64_t)BT * F);
+        p.frame_attn = {(int32_t)o_F1a, (int32_t)o_attn, (int32_t)o_gF1a, (int32_t)o_gFs, (int32_t)o_gPfT};
+    }
 #ifdef TA3N_GEMM_STAMPS
     b.add_region("stamps", 8192 * 16 * 2);            // (debug build: per-workgroup cycle stamps of the GEMM launches, directly in front of "zeros")
 #endif
@@ -807,6 +847,7 @@ bool TrnModel::lay_out_workspace(std::string &err) {
 // ---- the unfused lists: forward (group 0), loss (1), backward (2), optimiser (3) ----
 void TrnModel::add_unfused_lists() {
     const int BT = d.BT, F = d.F;
+    if (frame_attn) { add_frame_attn_lists(); return; }
     b.add_gemm_phase(0, spec_F1());
     if (bn_shared) b.add_simple_phase(PH_BN_FWD, 0);
     add_stack_forward(b, st, 0, BT, F);
@@ -828,7 +869,7 @@ void TrnModel::add_unfused_lists() {
     {   // Q1: heads that depend only on the logit gradients
         std::vector<GemmSpec> s{spec_gHv(), spec_gHf()};
         push_video_head_wgrads(s);
-        s.push_back(wgrad(2, F, BT, g.o_gPf, 2, g.o_Hf, F, w.Wcd, w.bcd));   // dWcd = gPf^T Hf, dbcd
+        s.push_back(spec_dWcd());
         b.add_gemm_phase(2, s);
     }
     {   // Q2: gradient at the pooled video feature + first-layer weight grads of the video/frame discriminators
@@ -843,6 +884,34 @@ void TrnModel::add_unfused_lists() {
     add_stack_backward(b, st, 2, BT, F);
     if (bn_shared) b.add_simple_phase(PH_BN_BWD, 2);
     { std::vector<GemmSpec> s; push_shared_fc_wgrad(s); b.add_gemm_phase(2, s); }                      // Q7
+    b.add_simple_phase(PH_GRAD_NORM, 3);
+    b.add_simple_phase(PH_SGD, 3);
+}
+
+// TA3N_FLAG_FRAME_ATTN: the same lists re-ordered around the two frame-attention launches.  Forward: the frame discriminator runs to
+// its logits before the tuple products (which read F1a); backward: its two layers follow the TRN input gradient, whose inner product
+// with F1 is the gradient at the attention weight.  Two more GEMM launches in the forward (Hf and Pf no longer share a launch with
+// the tuples / Hr), two more in the backward, and the two pointwise launches.
+void TrnModel::add_frame_attn_lists() {
+    b.add_gemm_phase(0, spec_F1());
+    b.add_gemm_phase(0, spec_Hf());
+    b.add_gemm_phase(0, spec_Pf());
+    b.add_simple_phase(PH_FRAME_ATTN_FWD, 0);   // attn_frame, F1a (+ its twin)
+    { std::vector<GemmSpec> s; for (int t = 0; t < NT; ++t) s.push_back(spec_Z(t)); b.add_gemm_phase(0, s); }
+    { std::vector<GemmSpec> s; for (int j = 0; j < NR; ++j) s.push_back(spec_Hr(j)); b.add_gemm_phase(0, s); }
+    b.add_simple_phase(PH_POOL_FWD, 0);
+    { std::vector<GemmSpec> s{spec_Y(), spec_Hv()}; b.add_gemm_phase(0, s); }
+    b.add_gemm_phase(0, spec_Pv());
+    b.add_simple_phase(PH_LOSS, 1);
+    { std::vector<GemmSpec> s{spec_gHv()}; push_video_head_wgrads(s); b.add_gemm_phase(2, s); }
+    { std::vector<GemmSpec> s{spec_gVt(g, d.NB, w, true, false)}; push_video_disc_wgrads(s); b.add_gemm_phase(2, s); }
+    b.add_simple_phase(PH_POOL_BWD, 2);
+    { std::vector<GemmSpec> s; push_relation_level(s); b.add_gemm_phase(2, s); }
+    { std::vector<GemmSpec> s; push_trn_wgrads(s); push_f1_grad(s); b.add_gemm_phase(2, s); }          // TRN weight gradients (on F1a), gF1a
+    b.add_simple_phase(PH_FRAME_ATTN_BWD, 2);   // gPfT, (1 + wf) gF1a
+    { std::vector<GemmSpec> s{spec_gHf(), spec_dWcd()}; b.add_gemm_phase(2, s); }
+    { std::vector<GemmSpec> s; push_frame_disc_wgrads(s); s.push_back(spec_gZ1_behind_frame_attn()); b.add_gemm_phase(2, s); }
+    { std::vector<GemmSpec> s; push_shared_fc_wgrad(s); b.add_gemm_phase(2, s); }
     b.add_simple_phase(PH_GRAD_NORM, 3);
     b.add_simple_phase(PH_SGD, 3);
 }
@@ -978,6 +1047,25 @@ bool TrnModel::add_fused_step(std::string &err) {
     return true;
 }
 
+// "" when the configuration's frame attention is built, otherwise the refusal (naming the combination)
+std::string frame_attn_refusal(const ta3n_config &c) {
+    if (!(c.flags & TA3N_FLAG_FRAME_ATTN)) return "";
+    const std::string what = "use_attn_frame TransAttn (TA3N_FLAG_FRAME_ATTN)";
+    if (c.aggregation != TA3N_AGG_TRN_M) return what + " on avgpool is not built: frame attention feeds the TRN of trn-m";
+    if (!(c.flags & TA3N_FLAG_TRANS_ATTN))
+        return what + " needs use_attn TransAttn (TA3N_FLAG_TRANS_ATTN): the reference takes the kind of frame attention from use_attn "
+               "(models.py:369-372) and fails with use_attn none";
+    const char *with = nullptr;
+    if (c.flags & TA3N_FLAG_F32_SPLIT) with = "TA3N_FLAG_F32_SPLIT";
+    else if (c.flags & TA3N_FLAG_MCD) with = "ens_DA MCD (TA3N_FLAG_MCD)";
+    else if (c.flags & TA3N_FLAG_BN_SHARED) with = "use_bn (TA3N_FLAG_BN_SHARED)";
+    else if (c.shared_fc_layers > 1) with = "shared_fc_layers (--add_fc) > 1";
+    else if (c.chain) with = "chain";
+    else if (c.split_k) with = "split_k";
+    else if (c.wgrads_late) with = "wgrads_late";
+    return with ? what + " with " + with + " is not built" : "";
+}
+
 int build_plan_trn(ta3n_plan &p, std::string &err) {
     const Dims d = dims_of(p.cfg);
     if (const char *e = bn_shared_refusal(p.cfg, d)) { err = e; return TA3N_ERR_INVALID; }
@@ -999,7 +1087,11 @@ int build_plan_trn(ta3n_plan &p, std::string &err) {
     // (The fused heads kernel knows neither the second classifier nor an outside gradient.  use_bn - round 6 - IS part of the fused
     // step: the two BatchNorm launches sit where the unfused lists have them, behind the shared-FC product and in front of its weight
     // gradient: 10 launches instead of 17, models.py:490-543, 569-570; chained launches stay without it.)
-    if (heads_supported(d.NB, d.C, d.F) && !m.mcd && !m.feat_grads && !(m.bn_shared && p.cfg.chain != 0)) {
+    if (m.frame_attn) {
+        // frame attention: the unfused lists only (the fused heads kernel computes Pf behind the tuple products); the frame-attention
+        // launch keeps the twin of F1a, which the tuple products and the TRN weight gradients read
+        add_bf16_twins(p, m.b, m.g, d.BT, d.D, {}, {}, {Span{m.o_F1a, m.o_F1a + (int64_t)d.BT * d.F}});
+    } else if (heads_supported(d.NB, d.C, d.F) && !m.mcd && !m.feat_grads && !(m.bn_shared && p.cfg.chain != 0)) {
         if (!m.add_fused_step(err)) return TA3N_ERR_INVALID;
     } else {
         // no fused step (TA3N_FLAG_FEATURE_GRADS: dis_DA DAN / JAN put a gradient between forward and backward; TA3N_FLAG_MCD; a shape the heads
@@ -1040,6 +1132,7 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     if (c.xcd_aware < 0 || c.xcd_aware > 3) { err = "xcd_aware must be 0, 1, 2 or 3"; return TA3N_ERR_INVALID; }
     if ((int64_t)d.BT * d.D >= (1ll << 31) || (int64_t)d.BT * d.F >= (1ll << 31)) { err = "problem too large for 32-bit offsets"; return TA3N_ERR_INVALID; }
     { const std::string e = shared_layers_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
+    { const std::string e = frame_attn_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     if (c.aggregation == TA3N_AGG_TRN_M) return build_plan_trn(p, err);
     p.n_tuples = 0;      // (no relation tuples)
     p.tuple_first.assign(1, 0);

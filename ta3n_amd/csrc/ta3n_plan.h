@@ -35,6 +35,9 @@ struct ta3n_plan {
     std::vector<int32_t> tuples, scale_len, scale_id, tuple_first;  // tuple_first[j..j+1) = tuples of scale j
     int n_tuples = 0;
     std::vector<int32_t> phase_kinds;   // per phase: which operand-kind combinations its GEMM tasks use (gemm_tiles' KV bits; filled at upload)
+    // workspace offsets of the two frame-attention launches (TA3N_FLAG_FRAME_ATTN; -1 without it).  Kept here and not in Geom, whose
+    // layout is fixed; resolved once by the builder and passed to the kernels as launch arguments.
+    struct FrameAttn { int32_t F1a = -1, attn = -1, gF1a = -1, gFs = -1, gPfT = -1; } frame_attn;
     uint64_t deny_blocking = 0;   // bit i: phase i must not use register-blocked tiles (it does not read bf16 twins; build_plan's retry)
     // device copies (created lazily by the launcher)
     void *d_segs = nullptr;

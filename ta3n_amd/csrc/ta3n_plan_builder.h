@@ -162,8 +162,8 @@ private:
 };
 
 // bf16 twins (TA3N_FLAG_BF16_STORE; ta3n_plan_twins.cpp).  extra_produced: ws spans whose twin a non-GEMM kernel of the fused step
-// keeps current; gemm_only: ws regions that only GEMM launches read.
+// keeps current (unfused_produced: the same for the unfused lists); gemm_only: ws regions that only GEMM launches read.
 void add_bf16_twins(ta3n_plan &p, Builder &b, Geom &g, int BT, int D, const std::vector<Span> &extra_produced,
-                    const std::vector<Span> &gemm_only = {});
+                    const std::vector<Span> &gemm_only = {}, const std::vector<Span> &unfused_produced = {});
 
 }  // namespace ta3n

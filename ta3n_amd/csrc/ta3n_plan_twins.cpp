@@ -141,7 +141,7 @@ bool has_fp32_reader(const ta3n_plan &p, const Span &reg) {
 }  // namespace
 
 void add_bf16_twins(ta3n_plan &p, Builder &b, Geom &g, int BT, int D, const std::vector<Span> &extra_produced,
-                    const std::vector<Span> &gemm_only) {
+                    const std::vector<Span> &gemm_only, const std::vector<Span> &unfused_produced) {
     const ta3n_config &c = p.cfg;
     if (!stored_twins(c)) return;
     // bf16 twins.  A launch of the fused step reads twins when every one of its operands can be moved 16 bytes (8
@@ -166,7 +166,7 @@ void add_bf16_twins(ta3n_plan &p, Builder &b, Geom &g, int BT, int D, const std:
     }
     analyse(p, g, fused_family, extra_produced);
     const char *ue = std::getenv("TA3N_UNFUSED_TWINS");      // (=0: the unfused lists on fp32 stages rounded in registers, as before round 6 - A/B aid)
-    if (!(ue && std::atoi(ue) == 0)) analyse(p, g, unfused_family, {});
+    if (!(ue && std::atoi(ue) == 0)) analyse(p, g, unfused_family, unfused_produced);
     // gemm_only: workspace regions that only GEMM launches read (no pointwise kernel, no API output).  If every launch
     // that reads such a region reads its twin, the producers skip the fp32 store (EPI_TWIN_ONLY): the fp32 region then
     // holds nothing meaningful in this configuration.

@@ -8,6 +8,9 @@
 //  loss       CE + 3 adversarial CE + attentive entropy and all logit gradients
 //             (main.py:439-451, 508-538, 559-562; loss.py:15-25).
 //  pool_bwd   backward of pool_fwd including the un-detached attention path.
+//  frame_attn_fwd / _bwd   TA3N_FLAG_FRAME_ATTN: one wavefront per frame row, F1a = (1 + w) F1 with
+//             w = 1 - H(softmax(frame-discriminator logits)) in front of the TRN (models.py:368-377,
+//             612-614) and the way back, the weights not detached.
 //  grad_norm / sgd   clip_grad_norm_ + Nesterov SGD with weight decay over the
 //             flat live-parameter prefix (main.py:578-583).
 #include <hip/hip_runtime.h>
@@ -126,6 +129,79 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(Geom g, Ptrs ptrs) {
             const float gh = g0 * W2[c] + g1 * W2[NB + c];
             ws[g.o_gHr + bj * NB + c] = ws[g.o_Hr + bj * NB + c] > 0.f ? gh : 0.f;
         }
+    }
+}
+
+// ---- TA3N_FLAG_FRAME_ATTN (use_attn_frame TransAttn, models.py:368-377, 612-614) ----
+// One wavefront per frame row r < B T, four rows per workgroup.  Rows of F floats start 16-byte aligned when F % 4 == 0 (regions start
+// 256-byte aligned): a lane then moves four columns per access, otherwise one.  The region offsets the Geom has no field for arrive as
+// kernel arguments (resolved by the plan builder, ta3n_plan::frame_attn).
+__global__ __launch_bounds__(256) void frame_attn_fwd_kernel(Geom g, Ptrs ptrs, int o_F1a, int o_attn_frame) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= g.B * g.T) return;
+    float *__restrict__ ws = ptrs.ws;
+    const int F = g.F;
+    const float w = 1.f - soft2(ws[g.o_Pf + (size_t)r * 2], ws[g.o_Pf + (size_t)r * 2 + 1]).H;   // get_trans_attn on the row's own logits
+    const float w1 = w + 1.f;
+    if (lane == 0) ws[o_attn_frame + r] = w;
+    const float *__restrict__ src = ws + g.o_F1 + (size_t)r * F;
+    float *__restrict__ dst = ws + o_F1a + (size_t)r * F;
+    // bf16 twin (TA3N_FLAG_BF16_STORE): the tuple launch and the TRN weight gradients read it as an operand (build_plan_trn)
+    unsigned short *__restrict__ tw = g.o_ws16 >= 0 ? reinterpret_cast<unsigned short *>(ws + g.o_ws16) + o_F1a + (size_t)r * F : nullptr;
+    if ((F & 3) == 0) {
+        for (int c = lane * 4; c < F; c += 256) {
+            const float4 v = *reinterpret_cast<const float4 *>(src + c);
+            const float4 y = make_float4(w1 * v.x, w1 * v.y, w1 * v.z, w1 * v.w);
+            *reinterpret_cast<float4 *>(dst + c) = y;
+            if (tw) *reinterpret_cast<uint2 *>(tw + c) = make_uint2(pack_bf16(y.x, y.y), pack_bf16(y.z, y.w));
+        }
+    } else {
+        for (int c = lane; c < F; c += 64) {
+            const float y = w1 * src[c];
+            dst[c] = y;
+            if (tw) tw[c] = (unsigned short)(pack_bf16(y, 0.f) & 0xFFFFu);
+        }
+    }
+}
+
+// gF1a: the TRN input gradient (gradient at F1a).  d = <gF1a[r], F1[r]> is the gradient at the row's weight, dw/dz_i = p_i (log p_i + H)
+// as in pool_bwd_kernel; the gradient that goes on to F1 is (1 + w) gF1a, the additive base of the launch that closes the frame level.
+// The lanes' partial products are added by the DPP butterfly: a fixed order, no atomics.  Rows of padded videos carry no guard here:
+// the kernel is linear in gF1a, so such a row adds nothing exactly when its rows of gF1a are zero.  On the engine path loss_kernel
+// guarantees that (every logit gradient of a padded video is zero, hence everything behind it).  On the module path
+// (ta3n_backward on gradients the caller supplies, ta3n_amd/models.py) the guarantee is the caller's: autograd hands in zero gradients
+// for outputs that its loss does not read, as the reference's removeDummy leaves them.
+__global__ __launch_bounds__(256) void frame_attn_bwd_kernel(Geom g, Ptrs ptrs, int o_gF1a, int o_gFs, int o_gPfT) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= g.B * g.T) return;
+    float *__restrict__ ws = ptrs.ws;
+    const int F = g.F;
+    const Soft2 s = soft2(ws[g.o_Pf + (size_t)r * 2], ws[g.o_Pf + (size_t)r * 2 + 1]);
+    const float w1 = 1.f + (1.f - s.H);
+    const float *__restrict__ f1 = ws + g.o_F1 + (size_t)r * F;
+    const float *__restrict__ gin = ws + o_gF1a + (size_t)r * F;
+    float *__restrict__ gout = ws + o_gFs + (size_t)r * F;
+    float dot = 0.f;
+    if ((F & 3) == 0) {
+        for (int c = lane * 4; c < F; c += 256) {
+            const float4 a = *reinterpret_cast<const float4 *>(gin + c);
+            const float4 b = *reinterpret_cast<const float4 *>(f1 + c);
+            dot = fmaf(a.x, b.x, dot); dot = fmaf(a.y, b.y, dot); dot = fmaf(a.z, b.z, dot); dot = fmaf(a.w, b.w, dot);
+            *reinterpret_cast<float4 *>(gout + c) = make_float4(w1 * a.x, w1 * a.y, w1 * a.z, w1 * a.w);
+        }
+    } else {
+        for (int c = lane; c < F; c += 64) {
+            const float a = gin[c];
+            dot = fmaf(a, f1[c], dot);
+            gout[c] = w1 * a;
+        }
+    }
+    dot = wave_allreduce_sum(dot);
+    if (lane == 0) {
+        ws[o_gPfT + (size_t)r * 2 + 0] = ws[g.o_gPf + (size_t)r * 2 + 0] + dot * s.p0 * (s.lp0 + s.H);
+        ws[o_gPfT + (size_t)r * 2 + 1] = ws[g.o_gPf + (size_t)r * 2 + 1] + dot * s.p1 * (s.lp1 + s.H);
     }
 }
 
@@ -722,6 +798,16 @@ int launch_pool_fwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
 int launch_pool_bwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
     const dim3 grid((g.B + 3) / 4);
     TA3N_DISPATCH_Q(pool_bwd_kernel, grid, stream, g, ptrs)
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_frame_attn_fwd(const Geom &g, const Ptrs &ptrs, int o_F1a, int o_attn_frame, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_attn_fwd_kernel, dim3((g.B * g.T + 3) / 4), dim3(256), 0, stream, g, ptrs, o_F1a, o_attn_frame);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_frame_attn_bwd(const Geom &g, const Ptrs &ptrs, int o_gF1a, int o_gFs, int o_gPfT, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_attn_bwd_kernel, dim3((g.B * g.T + 3) / 4), dim3(256), 0, stream, g, ptrs, o_gF1a, o_gFs, o_gPfT);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

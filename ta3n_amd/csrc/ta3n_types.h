@@ -103,6 +103,8 @@ enum PhaseKind : int32_t {
     PH_POOL_AVG_BWD = 9,     // TA3N_AGG_AVGPOOL, general: gradient at V spread back over the segments (-> gZ1 or its additive base)
     PH_BN_FWD = 10,          // TA3N_FLAG_BN_SHARED: F1 = dropout_i(relu(BatchNorm_domain(Z0)))
     PH_BN_BWD = 11,          // ... and back: gZ0, d(bn weight), d(bn bias) from gZ1
+    PH_FRAME_ATTN_FWD = 12,  // TA3N_FLAG_FRAME_ATTN: attn_frame = 1 - H(softmax(Pf)), F1a = (1 + attn_frame) F1
+    PH_FRAME_ATTN_BWD = 13,  // ... and back: gPfT = gPf + <gF1a, F1> dw/dPf, additive base of the gradient at F1 = (1 + attn_frame) gF1a
 };
 
 // work split of the fused heads kernel (ta3n_heads.hip); the plan builder sizes its partial-sum regions from these

@@ -23,8 +23,9 @@ ALL_FLAGS = (_lib.FLAG_ADV_RELATION | _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME 
 
 
 def flags_from_options(place_adv: Sequence[str] = ("Y", "Y", "Y"), add_loss_DA: str = "attentive_entropy",
-                       use_attn: str = "TransAttn", adv_DA: str = "RevGrad", use_target: str = "uSv") -> int:
-    """opts.py flags -> TA3N_FLAG_* (main.py:508-562 conditions)."""
+                       use_attn: str = "TransAttn", adv_DA: str = "RevGrad", use_target: str = "uSv",
+                       use_attn_frame: str = "none") -> int:
+    """opts.py flags -> TA3N_FLAG_* (main.py:508-562 conditions; use_attn_frame: models.py:612-614)."""
     f = 0
     adv_on = adv_DA != "none" and use_target != "none"
     if adv_on and place_adv[0] == "Y":
@@ -37,6 +38,10 @@ def flags_from_options(place_adv: Sequence[str] = ("Y", "Y", "Y"), add_loss_DA: 
         f |= _lib.FLAG_ATTN_ENTROPY
     if use_attn == "TransAttn":
         f |= _lib.FLAG_TRANS_ATTN
+    if use_attn_frame not in ("none", "TransAttn"):      # the bit means TransAttn; no other kind may turn into it silently
+        raise ValueError(frame_attn_refusal(use_attn_frame))
+    if use_attn_frame == "TransAttn":      # (with which other options it is built: frame_attn_refusal)
+        f |= _lib.FLAG_FRAME_ATTN
     return f
 
 
@@ -90,6 +95,27 @@ def add_fc_refusal(add_fc: int, use_bn: str = "none", dis_DA: str = "none", ens_
     return f"--add_fc {add_fc} together with {', '.join(other)} is not built" if other else ""
 
 
+def frame_attn_refusal(use_attn_frame: str, use_attn: str = "TransAttn", frame_aggregation: str = "trn-m", add_fc: int = 1,
+                       use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", f32_split: bool = False, chain: bool = False,
+                       split_k: int = 0, wgrads_late: bool = False) -> str:
+    """'' when --use_attn_frame `use_attn_frame` is built together with the other options, otherwise the message that refuses it
+    (naming the combination).  Built: TransAttn together with --use_attn TransAttn on trn-m (models.py:368-377, 612-614), fp32 and bf16."""
+    if use_attn_frame == "none":
+        return ""
+    if use_attn_frame != "TransAttn":
+        return f"--use_attn_frame {use_attn_frame}: built for TransAttn (the reference's 'general' frame attention needs an attn_layer its model never creates for frames)"
+    if frame_aggregation != "trn-m":
+        return f"--use_attn_frame TransAttn on --frame_aggregation {frame_aggregation}: built for trn-m (frame attention in front of the TRN)"
+    if use_attn != "TransAttn":
+        return (f"--use_attn_frame TransAttn with --use_attn {use_attn}: the reference takes the kind of frame attention from --use_attn "
+                f"(models.py:369-372; with use_attn none it raises UnboundLocalError) - built with --use_attn TransAttn")
+    other = [what for what, on in ((f"--add_fc {add_fc}", add_fc != 1), (f"--use_bn {use_bn}", use_bn != "none"),
+                                   (f"--dis_DA {dis_DA}", dis_DA != "none"), (f"--ens_DA {ens_DA}", ens_DA != "none"),
+                                   ("f32_split", f32_split), ("chained launches (chain)", chain), ("split_k", bool(split_k)),
+                                   ("wgrads_late", wgrads_late)) if on]
+    return f"--use_attn_frame TransAttn together with {', '.join(other)} is not built" if other else ""
+
+
 class TrainEngine:
     """Device-resident state of one rank: flat parameters / gradients / momentum,
     workspace, static input buffers.  Source rows come first in every batch
@@ -120,6 +146,19 @@ class TrainEngine:
         self.add_fc = int(add_fc)
         if flags is None:        # default: the full TA3N configuration for trn-m, the source-only one (BASELINE configs[0]) for avgpool
             flags = ALL_FLAGS if aggregation == "trn-m" else 0
+        # use_attn_frame TransAttn (TA3N_FLAG_FRAME_ATTN in `flags`, flags_from_options(use_attn_frame=...); models.py:368-377, 612-614): the
+        # frame features enter the TRN scaled by 1 + (1 - H(frame-discriminator softmax)).  The frame discriminator's logits come before the
+        # tuple products and its backward behind the TRN input gradient: the unfused launch lists with two more pointwise launches.
+        self.frame_attn = bool(flags & _lib.FLAG_FRAME_ATTN)
+        if self.frame_attn:
+            refused = frame_attn_refusal("TransAttn", use_attn="TransAttn" if flags & _lib.FLAG_TRANS_ATTN else "none",
+                                         frame_aggregation=aggregation, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA,
+                                         f32_split=bool(f32_split), chain=bool(chain),
+                                         split_k=int(os.environ.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k),
+                                         wgrads_late=bool(wgrads_late))
+            if refused:
+                raise NotImplementedError(refused)
+            fused = False
         # dis_DA DAN / JAN (main.py:452-505, loss.py:46-120): a discrepancy loss on the class logits (feat[0]) and / or the pooled
         # video feature (feat[1]), weighted by alpha.  It enters the step as one more gradient at those two tensors: the unfused
         # launch lists (ta3n_forward / ta3n_loss / ta3n_backward) with the gradient entry at the video feature
@@ -185,7 +224,7 @@ class TrainEngine:
         if aggregation == "avgpool":     # TemPooling: no relation features, no attention (use_attn none in the reference's script); with
             # use_target none (BASELINE configs[0]) the caller passes no adversarial flag either (flags_from_options)
             flags &= ~(_lib.FLAG_ATTN_ENTROPY | _lib.FLAG_TRANS_ATTN)
-        if phase_tiles is None and tile_config == 0 and aggregation == "trn-m" and add_fc == 1:      # measured choices for the benchmarked shapes
+        if phase_tiles is None and tile_config == 0 and aggregation == "trn-m" and add_fc == 1 and not self.frame_attn:      # measured choices for the benchmarked shapes (indexed by the plain launch order)
             from .tuning import tuned_phase_tiles
             phase_tiles = tuned_phase_tiles(batch_source + batch_target, num_segments, feature_dim, min(fc_dim, feature_dim),
                                             self.bf16, self.bf16_store, split=bool(flags & _lib.FLAG_F32_SPLIT))
@@ -195,7 +234,7 @@ class TrainEngine:
                 i, code = item.split(":")
                 phase_tiles[int(i)] = int(code)
         if chain is None:        # chained launches (ta3n_config.chain): the fused trn-m step in 5 launches instead of 8
-            chain = os.environ.get("TA3N_CHAIN", "0") == "1" and aggregation == "trn-m" and fused and add_fc == 1
+            chain = os.environ.get("TA3N_CHAIN", "0") == "1" and aggregation == "trn-m" and fused and add_fc == 1 and not self.frame_attn
         self._flags = int(flags)
         self.plan = _lib.Plan(batch_source, batch_target, num_segments, feature_dim, fc_dim, num_class, flags,
                               tile_config=tile_config, phase_tiles=list(phase_tiles or []), xcd_aware=xcd_aware,
@@ -1106,10 +1145,13 @@ class TrainEngine:
             if "Pv" in self.plan.regions:      # general variant: video- / frame-level domain logits (the relation slot repeats the video's)
                 out.update(pred_vid=self.region("Pv", (B, 2)), pred_frm=self.region("Pf", (B, T, 2)))
             return out
-        return dict(out=self.region("Y", (B, self.C)), attn=self.region("attn", (B, NR)),
-                    pred_rel=self.region("Pr", (B, NR, 2)), pred_vid=self.region("Pv", (B, 2)),
-                    pred_frm=self.region("Pf", (B, T, 2)), feat_v=self.region("V", (B, -1)),
-                    feat_f1=self.region("F1", (B, T, self.F)))
+        out = dict(out=self.region("Y", (B, self.C)), attn=self.region("attn", (B, NR)),
+                   pred_rel=self.region("Pr", (B, NR, 2)), pred_vid=self.region("Pv", (B, 2)),
+                   pred_frm=self.region("Pf", (B, T, 2)), feat_v=self.region("V", (B, -1)),
+                   feat_f1=self.region("F1", (B, T, self.F)))
+        if self.frame_attn:      # use_attn_frame: the frame-level weights (feat_f1 stays the un-attended feat[2], models.py:600-603)
+            out["attn_frame"] = self.region("attn_frame", (B, T))
+        return out
 
     def losses(self) -> Dict[str, float]:
         v = self.region("losses")[:6].tolist()

@@ -10,7 +10,8 @@ HIP library or without a GPU raises).
 Supported configurations = the TA3N hot path and TemPooling:
 frame_aggregation='trn-m' (use_attn in {'TransAttn','none'}) or 'avgpool' (use_attn 'none': BASELINE configs[0] and the
 TemPooling + RevGrad rows), baseline_type='video', share_params='Y', use_bn='none', add_fc=1, ens_DA='none',
-use_attn_frame='none'; add_fc 2 / 3 (models.py:145-153, 581-603) with use_bn 'none' and ens_DA 'none'.
+use_attn_frame='none'; add_fc 2 / 3 (models.py:145-153, 581-603) with use_bn 'none' and ens_DA 'none';
+use_attn_frame='TransAttn' (models.py:368-377, 612-614) with use_attn='TransAttn' on 'trn-m', use_bn 'none', ens_DA 'none', add_fc 1.
 Anything else raises NotImplementedError at construction (several of those
 branches are broken in the reference itself).
 """
@@ -211,7 +212,7 @@ class _HipForward(torch.autograd.Function):
         # A discriminator whose logits feed no loss (place_adv 'N', use_target none, ...) keeps grad None in the reference,
         # so torch.optim.SGD skips it - no weight decay either (main.py:508-538).  Same here: None, not zeros.
         unused = []
-        if g_pf is None:
+        if g_pf is None and not model._attn_frame_on:      # (frame attention: the weights come from these logits and are not detached either)
             unused += ["fc_feature_domain.", "fc_classifier_domain."]
         if g_pv is None:
             unused += ["fc_feature_domain_video.", "fc_classifier_domain_video."]
@@ -311,7 +312,11 @@ class VideoModel(nn.Module):
         if ens_DA not in ('none', 'MCD'): unsupported.append(f"ens_DA={ens_DA!r}")
         if ens_DA == 'MCD' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("ens_DA='MCD' with this frame_aggregation")
         if use_attn not in ('TransAttn', 'none'): unsupported.append(f"use_attn={use_attn!r}")
-        if use_attn_frame != 'none': unsupported.append(f"use_attn_frame={use_attn_frame!r}")
+        if use_attn_frame != 'none':      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
+            from .engine import frame_attn_refusal
+            refused = frame_attn_refusal(use_attn_frame, use_attn=use_attn, frame_aggregation=frame_aggregation, add_fc=add_fc, use_bn=use_bn,
+                                         ens_DA=ens_DA)
+            if refused: unsupported.append(f"use_attn_frame={use_attn_frame!r} ({refused})")
         if not before_softmax: unsupported.append("before_softmax=False")
         if add_fc < 1:
             raise ValueError('add at least one fc layer')          # models.py:137-138
@@ -336,6 +341,7 @@ class VideoModel(nn.Module):
         self.new_length = (1 if modality == "RGB" else 5) if new_length is None else new_length
         self.num_class = num_class
         self._attn_on = use_attn == 'TransAttn'
+        self._attn_frame_on = use_attn_frame == 'TransAttn'
         self._avg = frame_aggregation == 'avgpool'
         if verbose:
             print(f"Initializing TSN with base model: {base_model}. input_modality: {modality}, "
@@ -432,6 +438,7 @@ class VideoModel(nn.Module):
                     (_lib.FLAG_BN_SHARED if self.use_bn != 'none' else 0) | (_lib.FLAG_MCD if self.ens_DA == 'MCD' else 0))
         return (_lib.FLAG_ADV_RELATION | _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME |
                 (_lib.FLAG_TRANS_ATTN if self._attn_on else 0) |
+                (_lib.FLAG_FRAME_ATTN if self._attn_frame_on else 0) |      # use_attn_frame: F1a = (1 + w_frame) F1 into the TRN
                 _lib.FLAG_FEATURE_GRADS |                                   # feat[1] may carry a discrepancy loss (dis_DA)
                 (_lib.FLAG_BN_SHARED if self.use_bn != 'none' else 0) |
                 (_lib.FLAG_MCD if self.ens_DA == 'MCD' else 0))

@@ -30,7 +30,7 @@ if ROOT not in sys.path:
 
 from ta3n_amd import checkpoint as ckpt  # noqa: E402
 from ta3n_amd import parallel  # noqa: E402
-from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, lr_dann  # noqa: E402
+from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, frame_attn_refusal, lr_dann  # noqa: E402
 from ta3n_amd.models import ARCH_FEATURE_DIM  # noqa: E402
 from ta3n_amd.opts import parser  # noqa: E402
 
@@ -75,7 +75,11 @@ def validate_options(args, module_path: bool = False) -> None:
     need(not args.pretrain_source, "--pretrain_source")
     need(args.lr_adaptive in ("dann", "none"), f"--lr_adaptive {args.lr_adaptive} (built: dann, none with --lr_steps/--lr_decay)")
     need(args.use_attn in ("TransAttn", "none"), f"--use_attn {args.use_attn}")
-    need(args.use_attn_frame == "none", f"--use_attn_frame {args.use_attn_frame}")
+    # --use_attn_frame TransAttn (models.py:368-377, 612-614): with --use_attn TransAttn on trn-m, without the options listed there
+    frame_attn_msg = frame_attn_refusal(args.use_attn_frame, use_attn=args.use_attn, frame_aggregation=args.frame_aggregation, add_fc=args.add_fc,
+                                        use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA,
+                                        f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
+    need(not frame_attn_msg, frame_attn_msg)
     need(args.share_params == "Y", "--share_params N")
     # --add_fc 2 / 3 (models.py:145-153, 581-603): TA3N / trn-m and TemPooling with use_bn none, without dis_DA / ens_DA
     add_fc_msg = add_fc_refusal(args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA)
@@ -145,7 +149,7 @@ def main():
     T, D = args.num_segments, ARCH_FEATURE_DIM[args.arch]
     Bs_g, Bt_g = args.batch_size[0], args.batch_size[1]
     Bs, Bt = parallel.padded_shard_size(Bs_g, world), parallel.padded_shard_size(Bt_g, world)
-    flags = flags_from_options(args.place_adv, args.add_loss_DA, args.use_attn, args.adv_DA, args.use_target)
+    flags = flags_from_options(args.place_adv, args.add_loss_DA, args.use_attn, args.adv_DA, args.use_target, use_attn_frame=args.use_attn_frame)
     eng = TrainEngine(Bs, Bt, T, D, args.fc_dim, num_class, flags=flags, dropout_i=args.dropout_i,
                       dropout_v=args.dropout_v, momentum=args.momentum, weight_decay=args.weight_decay,
                       clip=args.clip_gradient, device=dev, bf16=(args.arithmetic == "bf16"), bf16_store=(args.arithmetic == "bf16"),
@@ -157,7 +161,7 @@ def main():
     model = VideoModel(num_class, args.baseline_type, args.frame_aggregation, args.modality, train_segments=T,
                        val_segments=T, base_model=args.arch, add_fc=args.add_fc, fc_dim=args.fc_dim,
                        dropout_i=args.dropout_i, dropout_v=args.dropout_v, partial_bn=not args.no_partialbn,
-                       use_bn=args.use_bn, ens_DA=args.ens_DA, use_attn=args.use_attn, verbose=False)
+                       use_bn=args.use_bn, ens_DA=args.ens_DA, use_attn=args.use_attn, use_attn_frame=args.use_attn_frame, verbose=False)
     eng.load_state(model.state_dict())                  # reference initialisation under torch.manual_seed(1)
     start_epoch, best_prec1, lr_resumed = 1, 0.0, None
     if args.resume:                                      # main.py:94-106
