@@ -387,7 +387,7 @@ def forward_domain(p, x, beta, cfg: Config, drop_i=None, drop_v=None, reverse_mu
     optional multiplicative dropout masks already scaled by 1/(1-p)
     ([B*T,F] and [B,256]); None means dropout off (eval or p=0).
     masks: optional dict of on/off patterns {"F1" [B*T,F], "Hf" [B*T,F], "Z" [B,n_tuples,256], "Hr" [B,T-1,256], "Hv" [B,256]} imposed
-    on the ReLUs (trn-m path; _relu_m).
+    on the ReLUs (_relu_m; avgpool has "F1", "Hf", "Hv" only).
     Returns dict with the reference's per-domain outputs."""
     B, T = x.size(0), cfg.num_segments
     mk = (lambda k: None) if masks is None else (lambda k: masks.get(k))
@@ -419,12 +419,13 @@ def forward_domain(p, x, beta, cfg: Config, drop_i=None, drop_v=None, reverse_mu
         if reverse_mu is not None:                                                   # :682-684
             vd = _GradReverse.apply(vd, reverse_mu)
         y = _linear(p, "fc_classifier_video_source", vd, cfg)                        # :686
-        hv = F.relu(_linear(p, "fc_feature_domain_video", _GradReverse.apply(vd, beta[1]), cfg))
+        hv = _relu_m(_linear(p, "fc_feature_domain_video", _GradReverse.apply(vd, beta[1]), cfg), mk("Hv"))
         pred_video = _linear(p, "fc_classifier_domain_video", hv, cfg)
         y2 = y
         if cfg.ens_DA == "MCD":                                                      # :716-720
             y2 = F.linear(vd, p["fc_classifier_video_source_2.weight"], p["fc_classifier_video_source_2.bias"])
-        return dict(attn=v[:, 0], out=y, out2=y2, pred_domain=[pred_video, pred_video, pred_frame], feat=[y, v, feat_frame])
+        return dict(attn=v[:, 0], out=y, out2=y2, pred_domain=[pred_video, pred_video, pred_frame], feat=[y, v, feat_frame],
+                    hidden=dict(F1=f, Hf=h, Hv=hv), pre_f1=z0, vd=vd)
     # TRN (:632-636)
     rel, rel_parts = trn_multiscale(p, feat_frame, cfg, with_tuples=True, masks=mk("Z"))
     # relation discriminators (:472-488)
@@ -461,7 +462,10 @@ def forward_domain(p, x, beta, cfg: Config, drop_i=None, drop_v=None, reverse_mu
                 pred_domain=[pred_rel.view(B, T - 1, 2), pred_video, pred_frame],   # :697-707, :722 reversed
                 feat=[y, v, feat_frame],                                             # :578, :675, :690, :722
                 # the post-ReLU hidden activations (test infrastructure: mask-synchronised comparisons read their on/off patterns)
-                hidden=dict(F1=f, Hf=h, Z=torch.stack([z for zs in rel_parts for z in zs], 1), Hr=torch.stack(hrs, 1), Hv=hv))
+                hidden=dict(F1=f, Hf=h, Z=torch.stack([z for zs in rel_parts for z in zs], 1), Hr=torch.stack(hrs, 1), Hv=hv),
+                # ... and what the dropout pattern checks read (tests/test_gpu_dropout_parity.py): the pre-activation of the shared frame
+                # layer (post-BatchNorm with use_bn) and the video feature behind dropout_v
+                pre_f1=z0, vd=vd)
 
 
 # ----------------------------------------------------------------------------
@@ -599,12 +603,15 @@ class TrainState:
 
 def train_step(state: TrainState, xs, xt, label_source, beta, gamma, cfg: Config,
                momentum=0.9, weight_decay=1e-4, clip=20.0, drop_i=None, drop_v=None,
-               n_src=None, n_tgt=None, grad_hook=None, alpha=0.0, mu=0.0, masks=None):
+               n_src=None, n_tgt=None, grad_hook=None, alpha=0.0, mu=0.0, masks=None, drop_rev=None, masks_rev=None):
     """One optimisation step: forward both domains, total loss, backward,
     clip_grad_norm_ (main.py:578-581), Nesterov SGD with weight decay
     (main.py:83, 583; torch.optim.SGD semantics: g += wd*p; buf = mu*buf + g
     (buf = g on first use); g = g + mu*buf; p -= lr*g).  Parameters without a
-    gradient are skipped (they are not in any BASELINE config's graph)."""
+    gradient are skipped (they are not in any BASELINE config's graph).
+    drop_rev: optional (drop_i_t, drop_v_t) of the MCD step's second, reversed forward of the target batch (the reference's nn.Dropout
+    draws fresh masks there); None: that pass reuses the first pass's target masks.  masks_rev: optional ReLU on/off patterns imposed on
+    that pass (as masks[1] on the first; _relu_m)."""
     p = {k: v.detach().clone().requires_grad_(True) for k, v in state.params.items()}
     di_s = di_t = dv_s = dv_t = None
     if drop_i is not None:
@@ -615,7 +622,8 @@ def train_step(state: TrainState, xs, xt, label_source, beta, gamma, cfg: Config
     tgt = forward_domain(p, xt, beta, cfg, di_t, dv_t, domain="T", masks=None if masks is None else masks[1])
     tgt_rev = None
     if cfg.ens_DA == "MCD":      # main.py:550: the whole model once more with reverse=True; only the target outputs are used
-        tgt_rev = forward_domain(p, xt, beta, cfg, di_t, dv_t, reverse_mu=mu, domain="T")
+        di_r, dv_r = (di_t, dv_t) if drop_rev is None else drop_rev
+        tgt_rev = forward_domain(p, xt, beta, cfg, di_r, dv_r, reverse_mu=mu, domain="T", masks=masks_rev)
     loss, parts = total_loss(src, tgt, label_source, gamma, cfg, n_src, n_tgt, alpha=alpha, tgt_rev=tgt_rev)
     names = [k for k in p if is_live(k)]
     grads = torch.autograd.grad(loss, [p[k] for k in names], allow_unused=True)
@@ -638,4 +646,4 @@ def train_step(state: TrainState, xs, xt, label_source, beta, gamma, cfg: Config
         new_params[k] = new_params[k] - state.lr * d
     state.params = new_params
     return dict(loss=loss.detach(), parts={k: v.detach() for k, v in parts.items()},
-                src=src, tgt=tgt, grads=raw, clipped=g, total_norm=total_norm)
+                src=src, tgt=tgt, tgt_rev=tgt_rev, grads=raw, clipped=g, total_norm=total_norm)

@@ -151,8 +151,9 @@ class Interp:
         if kind == 1: return -h["beta"][0]
         if kind == 2: return -h["beta"][1]
         if kind == 3: return -h["beta"][2]
-        if kind == 4: return 1.0 / (1.0 - h["p_drop_i"]) if (h["train"] and h["p_drop_i"] > 0) else 1.0
-        if kind == 5: return 1.0 / (1.0 - h["p_drop_v"]) if (h["train"] and h["p_drop_v"] > 0) else 1.0
+        inv_keep = lambda p: (1.0 / (1.0 - p) if p < 1 else 0.0) if (h["train"] and p > 0) else 1.0      # (ta3n_kernels.h: hyper_scale; p = 1 drops everything)
+        if kind == 4: return inv_keep(h["p_drop_i"])
+        if kind == 5: return inv_keep(h["p_drop_v"])
         if kind == 6: return -h["mu"] if h.get("reverse", 0) else 1.0
         return 1.0
 
@@ -284,7 +285,8 @@ class Interp:
             if (t.epi & (EPI_DROP_I | EPI_DROP_V)) and self.hy["train"]:
                 seed = self.hy["seed_i"] if t.epi & EPI_DROP_I else self.hy["seed_v"]
                 p = self.hy["p_drop_i"] if t.epi & EPI_DROP_I else self.hy["p_drop_v"]
-                v = v * keep_mask(seed, m * t.drop_ld + n, p)
+                # element id m * drop_ld + n + pad2 in uint32 (ta3n_types.h; pad2: the stream offset of a stacked shared layer, --add_fc)
+                v = v * keep_mask(seed, (m * t.drop_ld + n + (int(t.pad2) & 0xFFFFFFFF)) & 0xFFFFFFFF, p)
             v = v * self.scale(t.gamma_kind)
             self.buf(t.c_base)[t.c_off + m * t.c_ld + n] = v
             if t.epi & EPI_ROWSUM_A:

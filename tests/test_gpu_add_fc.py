@@ -208,6 +208,13 @@ def test_each_layer_draws_its_own_dropout_mask(fused):
     both = act1 & act2
     agree = (keep1[both] == keep2[both]).double().mean().item()
     assert both.sum().item() > 10000 and abs(agree - 0.5) < 0.02, agree      # a repeated mask would agree everywhere
+    # ... and exactly: each layer's pattern is the host's restatement of the stream at that layer's id offset (tests/dropout_masks.py;
+    # the seeds of step 0, which set_hyper took) - zero where it drops, nonzero where it keeps an active unit
+    from dropout_masks import check_frame_pattern, dropout_masks
+    from ta3n_amd.engine import dropout_seeds
+    for k, (Fk, Zk) in enumerate(((F1, Z1), (F2, Z2)), 1):
+        keep = torch.cat(dropout_masks(*dropout_seeds(0, 0), 0.5, 0.5, c["Bs"], c["Bt"], T, eng.F, 256, layer=k)["keep_i"])
+        check_frame_pattern(Fk.cpu(), Zk.cpu(), keep, f"layer {k}")
     # kept units carry the 1 / (1 - p) scale
     assert torch.allclose(F1[act1 & keep1], 2 * Z1[act1 & keep1], rtol=1e-3, atol=1e-5)
     gZ1, gZ2 = eng.region("gZ_l1", (B * T, -1)), eng.region("gZ1", (B * T, -1))

@@ -1,6 +1,7 @@
 """Host-side schedules of the PRODUCT (ta3n_amd/engine.py) against values the reference itself produced, and the
-statistical quality of the stateless dropout stream (ta3n_kernels.h: keep_mask, restated in tests/plan_interp.py; the GPU
-tests check that the kernels use exactly that stream)."""
+statistical quality of the stateless dropout stream (ta3n_kernels.h: keep_mask, restated in tests/plan_interp.py;
+tests/test_gpu_dropout_parity.py checks that the kernels use exactly that stream, element id by element id, and
+tests/test_dropout_cpu.py that the launch plans do)."""
 import numpy as np
 import pytest
 
