@@ -429,6 +429,47 @@ int ta3n_train_step_join(ta3n_plan *plan, const float *x, const float *params, f
 int ta3n_sgd_step_fused(ta3n_plan *plan, float *params, float *grads, float *momentum, float *ws,
                         void *stream);
 
+/* ---- --optimizer Adam (reference opts.py:21, main.py:84-86: torch.optim.Adam(model.parameters(), args.lr, weight_decay=...)
+ * behind the clip_grad_norm_ of main.py:578-581) --------------------------------------------------------------------------------
+ * torch.optim.Adam with amsgrad False, maximize False and L2 weight decay that is NOT decoupled, as one pass over the flat live
+ * prefix after the gradients are final:
+ *     coef = min(clip / (norm + 1e-6), 1) if clip > 0 else 1          d = g * coef + weight_decay * p
+ *     exp_avg = beta1 * exp_avg + (1 - beta1) * d                     exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * d * d
+ *     p -= step_size * exp_avg / (sqrt(exp_avg_sq) / bc2_sqrt + eps)
+ * 4 arrays read and 3 written per parameter (+ the bf16 twins of TA3N_FLAG_BF16_STORE / _F32_SPLIT in the same pass); exact
+ * square root and divide.  Independent of the model variant: every plan has it.  exp_avg / exp_avg_sq: live_param_floats floats
+ * each, zero before the first update.  `step` is the 1-based number of the update being applied (the `step` entry of
+ * torch.optim.Adam's state after it).  The betas are doubles: torch hands its kernels the fp32 rounding of the DOUBLE 1 - beta
+ * (for beta2 = 0.999 the complement of the fp32 beta is off by 1.3e-5 relative).  ta3n_hyper.momentum is unused under Adam.
+ *
+ * ta3n_adam_scalars: the two bias corrections as torch forms them (torch/optim/adam.py: Python floats, i.e. double):
+ * step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step), rounded to fp32.  Host only - no device is touched. */
+int ta3n_adam_scalars(int64_t step, float lr, double beta1, double beta2, float *step_size, float *bc2_sqrt);
+
+/* The update over floats [begin, end) of the live prefix with the scalars passed by value: the semantics of ta3n_sgd_range
+ * (fused_norm as in ta3n_sgd_step_fused, otherwise the range that starts at 0 first runs the gradient-norm pass;
+ * ws["grad_norm"], ws["grad_norm" + 1] are written by the range that starts at 0).  Ranges of one update compose bit-exactly. */
+int ta3n_adam_range(ta3n_plan *plan, float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int64_t begin,
+                    int64_t end, int fused_norm, float lr, double beta1, double beta2, float eps, float weight_decay, float clip,
+                    int64_t step, void *stream);
+
+/* The whole-prefix update that also leaves `next` - the per-step scalars of the following step - in the workspace
+ * (as ta3n_sgd_step_next: a loop that postpones each update to the start of the next step needs no ta3n_set_hyper copy). */
+int ta3n_adam_step_next(ta3n_plan *plan, float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *ws,
+                        int fused_norm, float lr, double beta1, double beta2, float eps, float weight_decay, float clip,
+                        int64_t step, const ta3n_hyper *next, void *stream);
+
+/* Several steps from ONE call on the pending-update contract of ta3n_train_steps (main.train's loop, main.py:348-621, under
+ * --optimizer Adam): for k in [0, n_steps): { optional batch assembly (ta3n_gather_segments[_bf16]_into of step k's ids);
+ * ta3n_adam_step_next as update number step_pending + k with the learning rate of the step before (lr_pending for k = 0,
+ * hypers[k-1].lr afterwards) and next = hypers[k]; the launches of ta3n_train_step }.  The update of step n_steps - 1 stays
+ * pending (update number step_pending + n_steps).  Requires ta3n_has_fused_step.  Single rank.  Bit-identical to the same
+ * calls issued one at a time. */
+int ta3n_train_steps_adam(ta3n_plan *plan, const float *x, float *params, float *grads, float *exp_avg, float *exp_avg_sq,
+                          float *ws, int fused_norm, float lr_pending, double beta1, double beta2, float eps, float weight_decay,
+                          float clip, int64_t step_pending, const ta3n_hyper *hypers, int n_steps, const ta3n_feed *source,
+                          const ta3n_feed *target, void *stream);
+
 /* ---- discrepancy losses (dis_DA DAN / JAN): loss.py:46-120, called from main.py:452-505 ----------------------------------------
  * ta3n_gaussian_kernel = loss.py:46-59 `guassian_kernel` on the stacked rows total = [source; target] ([n, d] fp32 device
  * memory): k_out [n, n] = sum_i exp(-||t_p - t_q||^2 / bw_i) with the reference's data-dependent bandwidth (fix_sigma <= 0) or the

@@ -60,8 +60,13 @@ def main():
                        n_directions=args.n_directions, n_ts=args.n_ts, use_attn=args.use_attn, n_attn=args.n_attn,
                        use_attn_frame=args.use_attn_frame, verbose=args.verbose, share_params=args.share_params)
     model = torch.nn.DataParallel(model, [0]).cuda()                                    # :79 (one device: a pass-through wrapper)
-    optimizer = torch.optim.SGD(model.parameters(), args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
-                                nesterov=True)                                          # :83
+    if args.optimizer == "SGD":                                                         # :81-89
+        print("using SGD")
+        optimizer = torch.optim.SGD(model.parameters(), args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                                    nesterov=True)
+    else:                                                                               # (validate_options: Adam)
+        print("using Adam")
+        optimizer = torch.optim.Adam(model.parameters(), args.lr, weight_decay=args.weight_decay)
 
     start_epoch = 1
     if args.resume:                                                                     # :94-106
@@ -161,7 +166,8 @@ def _fast_engine(model, optimizer, num_class):
     with a discrepancy / MCD term; use_bn AdaBN / AutoDIAL alone, dis_DA DAN / JAN and ens_DA MCD ARE covered since round 6 - the last three on the
     engine's unfused launch lists) or TA3N_MAIN_FAST=0.  The engine works on its own flat buffers: train() copies the model's parameters and the
     optimiser's momentum in at the start of an epoch and back at its end, so validate(), checkpoints and --resume see nn.Parameters and
-    torch.optim state as before."""
+    torch.optim state as before.  --optimizer Adam (a plain torch.optim.Adam: one group, amsgrad / maximize / decoupled weight decay /
+    capturable off) takes the same path with the engine's Adam update; exp_avg / exp_avg_sq / step travel like the momentum buffers."""
     from ta3n_amd.engine import TrainEngine, flags_from_options
     m = model.module
     needed = ("frame_aggregation", "dis_DA", "ens_DA", "use_bn", "save_attention", "add_loss_DA", "use_attn", "use_target", "place_adv", "adv_DA",
@@ -171,8 +177,14 @@ def _fast_engine(model, optimizer, num_class):
     # (round 6: use_bn AdaBN / AutoDIAL is part of the fused step - two BatchNorm launches inside ta3n_train_step - so those rows of the
     # paper's tables train at the fused speed too; the running statistics travel with the parameters below)
     if (os.environ.get("TA3N_MAIN_FAST", "1") == "0" or args.frame_aggregation != "trn-m" or args.dis_DA not in ("none", "DAN", "JAN") or args.ens_DA not in ("none", "MCD") or
-            args.use_bn not in ("none", "AdaBN", "AutoDIAL") or args.save_attention >= 0 or type(optimizer) is not torch.optim.SGD or
+            args.use_bn not in ("none", "AdaBN", "AutoDIAL") or args.save_attention >= 0 or type(optimizer) not in (torch.optim.SGD, torch.optim.Adam) or
             len(optimizer.param_groups) != 1):
+        return None
+    adam = type(optimizer) is torch.optim.Adam
+    g0 = optimizer.param_groups[0]
+    # torch.optim.Adam as the engine builds it (ta3n_adam_range): plain Adam with L2 weight decay; anything else keeps torch's own step
+    if adam and (g0.get("amsgrad") or g0.get("maximize") or g0.get("decoupled_weight_decay") or g0.get("capturable") or
+                 g0.get("differentiable") or torch.is_tensor(g0["lr"])):
         return None
     # (round 6: dis_DA DAN / JAN take the ENGINE too - unfused launch lists with the discrepancy term from the library, ta3n_discrepancy: 0.26 ms
     # per step at the headline shape against 1.25 ms on the module path.  Not with use_bn, not on the frame-level features (place_dis[2]), and
@@ -198,14 +210,16 @@ def _fast_engine(model, optimizer, num_class):
     g = optimizer.param_groups[0]
     # everything the engine is BUILT from: a later train() call with other options must not find an engine made for these
     key = (args.batch_size[0], args.batch_size[1], args.num_segments, args.fc_dim, num_class, tuple(args.place_adv), args.add_loss_DA,
-           args.use_attn, args.adv_DA, args.use_target, float(args.dropout_i), float(args.dropout_v), float(g["momentum"]),
+           args.use_attn, args.adv_DA, args.use_target, float(args.dropout_i), float(args.dropout_v),
+           ("Adam", float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) if adam else ("SGD", float(g["momentum"])),
            float(g["weight_decay"]), None if args.clip_gradient is None else float(args.clip_gradient), args.use_bn,
            args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame)
     eng = m.__dict__.get("_main_fast_engine", {}).get(key)
     if eng is None:
         eng = TrainEngine(args.batch_size[0], args.batch_size[1], args.num_segments, m.feature_dim, args.fc_dim, num_class,
                           flags=flags_from_options(args.place_adv, args.add_loss_DA, args.use_attn, args.adv_DA, args.use_target, use_attn_frame=attn_frame),
-                          dropout_i=args.dropout_i, dropout_v=args.dropout_v, momentum=g["momentum"], weight_decay=g["weight_decay"],
+                          dropout_i=args.dropout_i, dropout_v=args.dropout_v, weight_decay=g["weight_decay"],
+                          **(dict(optimizer="Adam", betas=tuple(g["betas"]), eps=g["eps"]) if adam else dict(momentum=g["momentum"])),
                           clip=args.clip_gradient if args.clip_gradient is not None else 0.0, device=next(m.parameters()).device,
                           use_bn=args.use_bn, **(dict(dis_DA=args.dis_DA, place_dis=tuple(args.place_dis)) if dis else {}),
                           **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc)
@@ -229,8 +243,19 @@ def _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, 
     model.train()
     named = dict(m.named_parameters())
     eng.load_state({k: v.detach() for k, v in m.state_dict().items()})
+    adam = eng.optimizer == "Adam"
     mom = eng.momentum_views()
-    for name, view in mom.items():                                      # torch.optim.SGD's momentum buffers -> the engine's flat buffer
+    if adam:                                                            # torch.optim.Adam's exp_avg / exp_avg_sq / step -> the engine's
+        moments = eng.adam_views()
+        steps = {int(optimizer.state[named[name]]["step"]) if "step" in optimizer.state.get(named[name], {}) else 0 for name in moments}
+        if len(steps) > 1:      # the engine keeps ONE step count (every live parameter is updated at every step): torch's own step otherwise
+            return None
+        for name, (m_view, v_view) in moments.items():
+            st = optimizer.state.get(named[name], {})
+            m_view.zero_() if "exp_avg" not in st else m_view.copy_(st["exp_avg"])
+            v_view.zero_() if "exp_avg_sq" not in st else v_view.copy_(st["exp_avg_sq"])
+        eng.adam_step_count = steps.pop() if steps else 0
+    for name, view in ({} if adam else mom).items():                    # torch.optim.SGD's momentum buffers -> the engine's flat buffer
         buf = optimizer.state.get(named[name], {}).get("momentum_buffer")
         view.zero_() if buf is None else view.copy_(buf)
     dev = eng.device
@@ -310,7 +335,16 @@ def _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, 
             for name, prm in named.items():
                 if name in views:
                     prm.copy_(views[name])
-            for name, view in mom.items():
+            if adam and eng.adam_step_count > 0:
+                for name, (m_view, v_view) in moments.items():
+                    st = optimizer.state[named[name]]
+                    st["step"] = torch.tensor(float(eng.adam_step_count), dtype=torch.float32)
+                    for key, view in (("exp_avg", m_view), ("exp_avg_sq", v_view)):
+                        if key in st:
+                            st[key].copy_(view)
+                        else:
+                            st[key] = view.clone()
+            for name, view in ({} if adam else mom).items():
                 st = optimizer.state[named[name]]
                 buf = st.get("momentum_buffer")
                 if buf is None:
@@ -332,7 +366,9 @@ def train(num_class, source_loader, target_loader, model, criterion, criterion_d
     """:309-667 for the supported options: RevGrad adversarial losses on the enabled levels and attentive entropy."""
     eng = _fast_engine(model, optimizer, num_class)
     if eng is not None:
-        return _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, epoch, log, log_short, beta, gamma, alpha, mu)
+        done = _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, epoch, log, log_short, beta, gamma, alpha, mu)
+        if done is not None:      # (None: optimiser state the engine cannot hold - Adam step counts that differ - found before anything ran)
+            return done
     batch_time, data_time = AverageMeter(), AverageMeter()
     losses_a, losses_e, losses_c, losses = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
     losses_d, losses_s = AverageMeter(), AverageMeter()                                 # discrepancy loss / ensemble loss (:313-315)

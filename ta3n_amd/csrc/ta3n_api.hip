@@ -5,6 +5,7 @@
 // own pad-to-batch-size rule, main.py:359-364).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -1019,6 +1020,101 @@ int ta3n_sgd_step(ta3n_plan *p, float *params, float *grads, float *momentum, fl
     if (rc != TA3N_OK) return rc;
     Ptrs ptrs = make_ptrs(p, nullptr, params, grads, ws);
     return run_group(p, 3, ptrs, params, momentum, static_cast<hipStream_t>(stream));
+}
+
+// ---- clip + Adam (reference main.py:84-86: torch.optim.Adam(model.parameters(), lr, weight_decay=...); clip_grad_norm_ of :578-581) ----
+int ta3n_adam_scalars(int64_t step, float lr, double beta1, double beta2, float *step_size, float *bc2_sqrt) {
+    if (!step_size || !bc2_sqrt) return fail(TA3N_ERR_INVALID, "null argument");
+    if (step < 1) return fail(TA3N_ERR_INVALID, "Adam: step counts from 1 (the number of the update being applied)");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(TA3N_ERR_INVALID, "Adam: betas must be in [0, 1)");
+    // torch/optim/adam.py (_single_tensor_adam): bias_correction = 1 - beta ** step in Python floats (double)
+    *step_size = (float)((double)lr / (1.0 - std::pow(beta1, (double)step)));
+    *bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
+    return TA3N_OK;
+}
+
+namespace {
+int check_adam(const ta3n_plan *p, const float *params, const float *grads, const float *exp_avg, const float *exp_avg_sq, const float *ws,
+               int64_t step, float eps, int fused_norm) {
+    if (!p || !params || !grads || !exp_avg || !exp_avg_sq || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    if (!aligned16(params) || !aligned16(grads) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) || !aligned16(ws))
+        return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    if (step < 1) return fail(TA3N_ERR_INVALID, "Adam: step counts from 1 (the number of the update being applied)");
+    if (!(eps >= 0.f)) return fail(TA3N_ERR_INVALID, "Adam: eps must be >= 0");
+    if (fused_norm && ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
+    return TA3N_OK;
+}
+// grad-norm pass (unless the fused step left the partials) + one Adam launch over [begin, end) as update number `step`
+int enqueue_adam(ta3n_plan *p, float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int64_t begin, int64_t end,
+                 int fused_norm, float lr, double beta1, double beta2, float eps, float weight_decay, float clip, int64_t step,
+                 const ta3n_hyper *next, hipStream_t s) {
+    float step_size, bc2_sqrt;
+    int rc = ta3n_adam_scalars(step, lr, beta1, beta2, &step_size, &bc2_sqrt);
+    if (rc != TA3N_OK) return rc;
+    if (!fused_norm && begin == 0 && launch_grad_norm(p->geom, grads, ws, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
+    if (launch_adam_range(p->geom, params, grads, exp_avg, exp_avg_sq, ws, begin, end, fused_norm != 0, step_size, bc2_sqrt, beta1, beta2, eps,
+                          weight_decay, clip, reinterpret_cast<const Hyper *>(next), s) != 0)
+        return fail(TA3N_ERR_HIP, std::string("adam launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return TA3N_OK;
+}
+}  // namespace
+
+int ta3n_adam_range(ta3n_plan *p, float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int64_t begin, int64_t end,
+                    int fused_norm, float lr, double beta1, double beta2, float eps, float weight_decay, float clip, int64_t step,
+                    void *stream) {
+    int rc = check_adam(p, params, grads, exp_avg, exp_avg_sq, ws, step, eps, fused_norm);
+    if (rc != TA3N_OK) return rc;
+    if (begin < 0 || end > p->live_floats || begin > end || (begin & 3) || (end & 3))
+        return fail(TA3N_ERR_INVALID, "range must be 4-float aligned and inside the live parameter prefix");
+    float ss, bc;
+    if ((rc = ta3n_adam_scalars(step, lr, beta1, beta2, &ss, &bc)) != TA3N_OK) return rc;      // (the betas, before anything touches a device)
+    if ((rc = ensure_uploaded(p)) != TA3N_OK) return rc;
+    return enqueue_adam(p, params, grads, exp_avg, exp_avg_sq, ws, begin, end, fused_norm, lr, beta1, beta2, eps, weight_decay, clip, step,
+                        nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ta3n_adam_step_next(ta3n_plan *p, float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int fused_norm, float lr,
+                        double beta1, double beta2, float eps, float weight_decay, float clip, int64_t step, const ta3n_hyper *next,
+                        void *stream) {
+    int rc = check_adam(p, params, grads, exp_avg, exp_avg_sq, ws, step, eps, fused_norm);
+    if (rc != TA3N_OK) return rc;
+    if (!next) return fail(TA3N_ERR_INVALID, "null argument");
+    float ss, bc;
+    if ((rc = ta3n_adam_scalars(step, lr, beta1, beta2, &ss, &bc)) != TA3N_OK) return rc;
+    if ((rc = ensure_uploaded(p)) != TA3N_OK) return rc;
+    return enqueue_adam(p, params, grads, exp_avg, exp_avg_sq, ws, 0, p->live_floats, fused_norm, lr, beta1, beta2, eps, weight_decay, clip,
+                        step, next, static_cast<hipStream_t>(stream));
+}
+
+int ta3n_train_steps_adam(ta3n_plan *p, const float *x, float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *ws,
+                          int fused_norm, float lr_pending, double beta1, double beta2, float eps, float weight_decay, float clip,
+                          int64_t step_pending, const ta3n_hyper *hypers, int n_steps, const ta3n_feed *source, const ta3n_feed *target,
+                          void *stream) {
+    if (n_steps < 0) return fail(TA3N_ERR_INVALID, "n_steps must be >= 0");
+    int rc = check_adam(p, params, grads, exp_avg, exp_avg_sq, ws, step_pending, eps, fused_norm);
+    if (rc != TA3N_OK) return rc;
+    if (!x || !hypers) return fail(TA3N_ERR_INVALID, "null argument");
+    if (!aligned16(x)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    if (ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
+    if ((source || target) && (p->geom.D & 7) != 0) return fail(TA3N_ERR_INVALID, "ta3n_feed: feature_dim % 8 required");
+    float ss, bc;
+    if ((rc = ta3n_adam_scalars(step_pending, lr_pending, beta1, beta2, &ss, &bc)) != TA3N_OK) return rc;
+    if ((rc = ensure_uploaded(p)) != TA3N_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Geom &g = p->geom;
+    Ptrs ptrs = make_ptrs(p, x, params, grads, ws);
+    float lr = lr_pending;
+    for (int k = 0; k < n_steps; ++k) {
+        // the batch of step k (its input rows were last read by the final launch of step k - 1, already enqueued)
+        if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
+        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, nullptr, s)) != TA3N_OK) return rc;
+        // the update of the step before as update number step_pending + k, carrying this step's scalars; then the step's own launches
+        if ((rc = enqueue_adam(p, params, grads, exp_avg, exp_avg_sq, ws, 0, p->live_floats, fused_norm, lr, beta1, beta2, eps, weight_decay,
+                               clip, step_pending + k, &hypers[k], s)) != TA3N_OK) return rc;
+        if ((rc = run_group(p, 4, ptrs, nullptr, nullptr, s)) != TA3N_OK) return rc;
+        lr = hypers[k].lr;
+    }
+    return TA3N_OK;
 }
 
 }  // extern "C"

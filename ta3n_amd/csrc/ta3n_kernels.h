@@ -178,6 +178,11 @@ int launch_sgd_fixup(const Geom &g, float *params, const float *grads, float *mo
                      float clip, const Hyper *next, hipStream_t stream);
 int launch_sgd_range(const Geom &g, float *params, const float *grads, float *momentum, float *ws, int64_t begin, int64_t end,
                      bool fused_norm, float lr, float mu, float wd, float clip, const Hyper *next, hipStream_t stream, bool write_norm = false);
+// clip + Adam over floats [begin, end) of the live prefix (adam_range_kernel): step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t)
+// already formed by the host (ta3n_adam_scalars); the betas in double so that 1 - beta reaches the kernel as torch's fp32 value of it
+int launch_adam_range(const Geom &g, float *params, const float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int64_t begin,
+                      int64_t end, bool fused_norm, float step_size, float bc2_sqrt, double beta1, double beta2, float eps, float wd,
+                      float clip, const Hyper *next, hipStream_t stream);
 // One batch half of the launch that opens a pipelined step together with its batch assembly (sgd_open_feed_kernel): device pointers of a packed
 // feature store, this step's video ids, where the rows go (fp32 rows / bf16 twin rows; either may be null) - n_videos = 0: nothing to assemble
 struct FeedJob {

@@ -674,6 +674,72 @@ __global__ __launch_bounds__(256) void sgd_range_kernel(Geom g, float *__restric
     sgd_range_body(g, params, grads, mom, ws, i0, i1, norm_off, norm_n, lr, mu, wd, clip, next, has_next, (int)gridDim.x, red);
 }
 
+// clip_grad_norm_ + torch.optim.Adam (amsgrad False, maximize False, L2 weight decay added to the gradient: reference main.py:84-86, 578-583)
+// over floats [4 i0, 4 i1) of the flat prefix, on the contract of sgd_range_body: scalars by value, the norm partials added up by every
+// workgroup in the fixed order of strided_partial_sum, the next element's loads in flight while the current one is updated, the range that
+// starts at 0 records norm and coefficient, the next step's scalars ride along (bit 0 of has_next), bf16 twins written in the same pass.
+//     d = g coef + wd p;  m = b1 m + (1 - b1) d;  v = b2 v + (1 - b2) d d;  p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+// step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t) and the two complements 1 - b1, 1 - b2 come from the host, formed in double the way
+// torch forms them (a complement taken from the fp32 beta would be off by 1e-5 relative for b2 = 0.999).  Exact sqrtf and divide.
+struct AdamScalars {
+    float b1, omb1, b2, omb2, step_size, bc2_sqrt, eps, wd, clip;
+};
+__device__ __forceinline__ void adam_range_body(const Geom &g, float *__restrict__ params, const float *__restrict__ grads,
+                                                float *__restrict__ exp_avg, float *__restrict__ exp_avg_sq, float *__restrict__ ws,
+                                                int i0, int i1, int norm_off, int norm_n, const AdamScalars &a, const Hyper &next,
+                                                int has_next, int n_blocks, float *red) {
+    float4 *__restrict__ p4 = reinterpret_cast<float4 *>(params);
+    float4 *__restrict__ m4 = reinterpret_cast<float4 *>(exp_avg);
+    float4 *__restrict__ v4 = reinterpret_cast<float4 *>(exp_avg_sq);
+    const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
+    const int stride = n_blocks * blockDim.x;
+    int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, v = p, gr = p;
+    if (i < i1) { p = p4[i]; m = m4[i]; v = v4[i]; gr = g4[i]; }      // in flight while the norm partials are added up
+    const float acc = strided_partial_sum(ws + norm_off, norm_n, (int)threadIdx.x, (int)blockDim.x);
+    const float total = sqrtf(block_sum(acc, red));
+    float coef = 1.f;
+    if (a.clip > 0.f) coef = fminf(a.clip / (total + 1e-6f), 1.f);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && i0 == 0) {
+        ws[g.o_grad_norm] = total;
+        ws[g.o_grad_norm + 1] = coef;
+    }
+    if ((has_next & 1) && blockIdx.x == 0 && threadIdx.x < (int)(sizeof(Hyper) / 4))
+        reinterpret_cast<uint32_t *>(ws + g.o_hyper)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&next)[threadIdx.x];
+    while (i < i1) {
+        const int nxt = i + stride;
+        float4 pn = p, mn = m, vn = v, gn = gr;
+        if (nxt < i1) { pn = p4[nxt]; mn = m4[nxt]; vn = v4[nxt]; gn = g4[nxt]; }
+        float gg[4] = {gr.x, gr.y, gr.z, gr.w};
+        float pp[4] = {p.x, p.y, p.z, p.w};
+        float mm[4] = {m.x, m.y, m.z, m.w};
+        float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float d = fmaf(a.wd, pp[e], gg[e] * coef);
+            mm[e] = fmaf(a.b1, mm[e], a.omb1 * d);
+            vv[e] = fmaf(a.b2, vv[e], (a.omb2 * d) * d);
+            const float denom = sqrtf(vv[e]) / a.bc2_sqrt + a.eps;
+            pp[e] = fmaf(-a.step_size, mm[e] / denom, pp[e]);
+        }
+        p4[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
+        m4[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        v4[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+        if (g.o_p16 >= 0) {
+            const unsigned h0 = pack_bf16(pp[0], pp[1]), h1 = pack_bf16(pp[2], pp[3]);
+            reinterpret_cast<uint2 *>(ws + g.o_p16)[i] = make_uint2(h0, h1);
+            if (g.pair_delta) reinterpret_cast<uint2 *>(ws + g.o_p16 + g.pair_delta)[i] = make_uint2(pack_bf16_lo(pp[0], pp[1], h0), pack_bf16_lo(pp[2], pp[3], h1));
+        }
+        i = nxt; p = pn; m = mn; v = vn; gr = gn;
+    }
+}
+__global__ __launch_bounds__(256) void adam_range_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
+                                                         float *__restrict__ exp_avg, float *__restrict__ exp_avg_sq, float *__restrict__ ws,
+                                                         int i0, int i1, int norm_off, int norm_n, AdamScalars a, Hyper next, int has_next) {
+    __shared__ float red[8];
+    adam_range_body(g, params, grads, exp_avg, exp_avg_sq, ws, i0, i1, norm_off, norm_n, a, next, has_next, (int)gridDim.x, red);
+}
+
 // The launch that opens a pipelined step WITH its batch assembly (ta3n_train_steps with feeds): workgroups [0, sgd_blocks) are
 // sgd_range_kernel's - the previous step's update of the shared frame FC, this step's scalars - and the rest assemble the step's batch, one
 // input row each (gather_row_*: the source half's rows, then the target half's).  The two jobs touch disjoint memory (parameters / momentum /
@@ -1322,6 +1388,23 @@ int launch_sgd_range(const Geom &g, float *params, const float *grads, float *mo
     hipLaunchKernelGGL(sgd_range_kernel, dim3(blocks), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1,
                        fused_norm ? g.o_sumsq : g.o_norm_part, fused_norm ? g.n_sumsq : g.n_norm_blocks, lr, mu, wd, clip, nh,
                        (next ? 1 : 0) | (write_norm ? 2 : 0));
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_adam_range(const Geom &g, float *params, const float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int64_t begin,
+                      int64_t end, bool fused_norm, float step_size, float bc2_sqrt, double beta1, double beta2, float eps, float wd,
+                      float clip, const Hyper *next, hipStream_t stream) {
+    const int i0 = (int)(begin / 4), i1 = (int)(end / 4);
+    if (i1 <= i0) return 0;
+    int blocks = (i1 - i0 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    Hyper nh;
+    std::memset(&nh, 0, sizeof(nh));
+    if (next) nh = *next;
+    // torch hands the kernels beta and 1 - beta as fp32 roundings of the double values (lerp_ weight, mul_ / addcmul_ value)
+    const AdamScalars a{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), step_size, bc2_sqrt, eps, wd, clip};
+    hipLaunchKernelGGL(adam_range_kernel, dim3(blocks), dim3(256), 0, stream, g, params, grads, exp_avg, exp_avg_sq, ws, i0, i1,
+                       fused_norm ? g.o_sumsq : g.o_norm_part, fused_norm ? g.n_sumsq : g.n_norm_blocks, a, nh, next ? 1 : 0);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -1,5 +1,6 @@
 """Fused TA3N train step on one MI355X: forward, loss assembly, backward, gradient
-all-reduce (RCCL, only when world_size > 1), clip + Nesterov SGD - every
+all-reduce (RCCL, only when world_size > 1), clip + Nesterov SGD (or, on one
+rank, clip + Adam: optimizer="Adam") - every
 arithmetic op is a HIP kernel of libta3n_hip.so; this module only owns device
 buffers (torch tensors), the stream and the optional hipGraph capture.
 
@@ -116,6 +117,22 @@ def frame_attn_refusal(use_attn_frame: str, use_attn: str = "TransAttn", frame_a
     return f"--use_attn_frame TransAttn together with {', '.join(other)} is not built" if other else ""
 
 
+def adam_refusal(world: int = 1, sharded_update: bool = False, process_group: bool = False, ddp_selftest: bool = False,
+                 peer_exchange: bool = False, fused_update: bool = False, side_update: bool = False, capture: bool = False,
+                 two_stream: bool = False) -> str:
+    """'' when optimizer="Adam" is built together with the named schedule, otherwise the message that refuses it.  Adam is one launch over
+    the flat prefix behind the step's gradients on one rank; every schedule below is a way of splitting or moving the SGD update."""
+    what = [w for w, on in ((f"world size {world} (a process group)", world > 1 or process_group),
+                            ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest),
+                            ("the sharded update (sharded_update / TA3N_DDP_SHARDED)", sharded_update),
+                            ("the peer gradient exchange (peer_exchange / TA3N_DDP_PEER)", peer_exchange),
+                            ("fused_update=True (the Nesterov update inside the gradient tiles, TA3N_FUSED_UPDATE)", fused_update),
+                            ("the side-stream / side-workgroup update (TA3N_SIDE_UPDATE)", side_update),
+                            ("capture() (a hipGraph would freeze the step count of the bias corrections)", capture),
+                            ("the two-stream multi-job call (ta3n_train_steps_multi)", two_stream)) if on]
+    return f"optimizer Adam together with {', '.join(what)} is not built (Adam: single rank, the update as one launch behind the step)" if what else ""
+
+
 class TrainEngine:
     """Device-resident state of one rank: flat parameters / gradients / momentum,
     workspace, static input buffers.  Source rows come first in every batch
@@ -131,7 +148,22 @@ class TrainEngine:
                  dis_DA: str = "none", place_dis: Sequence[str] = ("N", "Y", "N"), alpha: float = 0.0, use_bn: str = "none",
                  ens_DA: str = "none", mu: float = 0.0, split_k: Optional[int] = None, sharded_update: Optional[bool] = None,
                  peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False,
-                 add_fc: int = 1):
+                 add_fc: int = 1, optimizer: str = "SGD", betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8):
+        # --optimizer Adam (reference main.py:84-86): clip + torch.optim.Adam as ONE launch over the flat live prefix behind the step's
+        # gradients (include/ta3n_hip.h: ta3n_adam_range) - the same for every model variant.  self.M is exp_avg, self.V exp_avg_sq,
+        # self.adam_step_count the number of updates applied.  The schedules that overlap or shard the SGD update are not built for it.
+        if optimizer not in ("SGD", "Adam"):
+            raise NotImplementedError(f"optimizer {optimizer!r} (built: SGD with Nesterov momentum, Adam)")
+        self.optimizer = optimizer
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        if optimizer == "Adam":
+            refused = adam_refusal(sharded_update=bool(sharded_update) or (sharded_update is None and os.environ.get("TA3N_DDP_SHARDED", "0") == "1"),
+                                   process_group=process_group is not None, ddp_selftest=os.environ.get("TA3N_DDP_SELFTEST") == "1",
+                                   peer_exchange=bool(peer_exchange))
+            if refused:
+                raise NotImplementedError(refused)
+            if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0) or self.eps < 0.0:
+                raise ValueError(f"Adam: betas {self.betas} must be in [0, 1) and eps {self.eps} >= 0 (torch.optim.Adam's own checks)")
         if not torch.cuda.is_available():
             raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
         # --add_fc 2 / 3 (models.py:145-153, 581-603): one or two more Linear(F, F) -> ReLU -> dropout_i layers on the shared frame FC
@@ -254,6 +286,8 @@ class TrainEngine:
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(process_group)
             self.rank = torch.distributed.get_rank(process_group)
+        if self.optimizer == "Adam" and self.world > 1:
+            raise NotImplementedError(adam_refusal(world=self.world))
         # The DA options under more than one rank follow what the reference's nn.DataParallel does with them (main.py:79): the discrepancy
         # loss is taken on the gathered global batch (discrepancy()); MCD's discrepancy is a mean over the global target batch
         # (mcd_second_forward()); BatchNorm statistics are PER REPLICA - each replica normalises its own slice of the batch with its own
@@ -264,6 +298,8 @@ class TrainEngine:
             self.P = torch.zeros(p.param_floats, dtype=torch.float32, device=self.device)
             self.G = torch.zeros(p.param_floats, dtype=torch.float32, device=self.device)
             self.M = torch.zeros(p.live_floats, dtype=torch.float32, device=self.device)
+            # Adam: self.M is exp_avg and self.V exp_avg_sq (zero = torch.optim.Adam's lazily created state)
+            self.V = torch.zeros(p.live_floats, dtype=torch.float32, device=self.device) if self.optimizer == "Adam" else None
             self.ws = torch.zeros(p.ws_floats, dtype=torch.float32, device=self.device)
             self.X = torch.zeros(self.B * self.T, self.D, dtype=torch.float32, device=self.device)
             self._L = _lib.lib()
@@ -294,6 +330,10 @@ class TrainEngine:
         # TA3N_SIDE_UPDATE=0: keep the pipelined update a launch of its own (ta3n_sgd_step_next)
         self._side_update = (os.environ.get("TA3N_SIDE_UPDATE", "1") == "1" and
                              self._L.ta3n_has_pipelined_step(self.plan.handle) == 1)
+        if self.optimizer == "Adam":      # the side workgroups of the step's first launch (EPI_SGD tasks) apply Nesterov SGD: not taken under Adam
+            self._side_update = False
+        self.adam_step_count = 0          # Adam: updates applied so far (the `step` of torch.optim.Adam's state)
+        self.force_unfused_norm = False   # Adam: take the clip norm from the gradient-norm pass even where the fused step left its partials
         # 1 (default): one all-reduce after the last launch; 2: everything but the shared frame FC's gradient is reduced while
         # the last launch runs (worth it only when that launch is longer than an extra collective's fixed cost)
         self._ddp_buckets = int(os.environ.get("TA3N_DDP_BUCKETS", "1")) if ddp_buckets is None else int(ddp_buckets)
@@ -433,6 +473,40 @@ class TrainEngine:
                     n *= s
                 out[name] = self.M[off:off + n].view(shape)
         return out
+
+    def adam_views(self) -> Dict[str, tuple]:
+        """optimizer="Adam": {name: (exp_avg view, exp_avg_sq view)} over the live parameters (zero = no update yet; the step count,
+        one for all of them, is self.adam_step_count)."""
+        if self.optimizer != "Adam":
+            raise _lib.Ta3nError("adam_views: this engine was built with optimizer='SGD' (momentum_views)")
+        m = self.momentum_views()
+        out = {}
+        for name, off, shape, live in self.plan.params:
+            if live:
+                out[name] = (m[name], self.V[off:off + m[name].numel()].view(shape))
+        return out
+
+    def _adam_fused_norm(self) -> int:
+        """1 where the SGD path takes ta3n_sgd_step_fused: the fused step's per-tile partials are the norm of the final gradients."""
+        return int(self.fused and self.world == 1 and not self._ddp_selftest and not self.force_unfused_norm)
+
+    def _adam_args(self, lr: float, wd: float, clip: float):
+        return (float(lr), self.betas[0], self.betas[1], self.eps, float(wd), float(clip), self.adam_step_count + 1)
+
+    def adam_range(self, lo: int, hi: int, lr: float, fused_norm: Optional[int] = None, step: Optional[int] = None) -> None:
+        """ta3n_adam_range over floats [lo, hi) of the live prefix as update number `step` (default: the next one).  Does not count the
+        update: the caller that has covered the whole prefix adds 1 to self.adam_step_count."""
+        args = list(self._adam_args(lr, self.weight_decay, float(self.clip) if self.clip is not None else 0.0))
+        if step is not None:
+            args[-1] = int(step)
+        _lib.check(self._L.ta3n_adam_range(self.plan.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
+                                           self.ws.data_ptr(), int(lo), int(hi), self._adam_fused_norm() if fused_norm is None else int(fused_norm),
+                                           *args, self._stream()), "ta3n_adam_range")
+
+    def adam_step(self, lr: Optional[float] = None, fused_norm: Optional[int] = None) -> None:
+        """clip + Adam over the whole live prefix on the gradients in self.G (lr: default the current step's), counted."""
+        self.adam_range(0, self.plan.live_floats, float(self._hyper.lr) if lr is None else lr, fused_norm=fused_norm)
+        self.adam_step_count += 1
 
     def set_batch(self, source: torch.Tensor, target: torch.Tensor, source_label: torch.Tensor) -> None:
         """[Bs,T,D], [Bt,T,D] float features and int labels into the static device buffers."""
@@ -720,7 +794,14 @@ class TrainEngine:
             if self.ens_DA == "MCD":
                 self.mcd_second_backward()
         self.all_reduce_grads()
-        if self.fused and self.world == 1 and not self._ddp_selftest:
+        if self.optimizer == "Adam":
+            # the norm partials of the fused step only where sgd_step_fused is taken below; by value: lr, weight decay and clip of set_hyper
+            h = self._hyper
+            _lib.check(self._L.ta3n_adam_range(self.plan.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
+                                               self.ws.data_ptr(), 0, self.plan.live_floats, self._adam_fused_norm(),
+                                               *self._adam_args(h.lr, h.weight_decay, h.clip), self._stream()), "ta3n_adam_range")
+            self.adam_step_count += 1
+        elif self.fused and self.world == 1 and not self._ddp_selftest:
             self.sgd_step_fused()       # local gradients are final: their norm partials are already in ws
         else:
             self.sgd_step()
@@ -732,9 +813,15 @@ class TrainEngine:
             return None
         lr, mu, wd, clip = self._pending
         self._pending = None
+        L, h = self._L, self.plan.handle
+        if self.optimizer == "Adam":      # one launch on the step's stream (the side-stream split is an SGD schedule): nothing to join
+            _lib.check(L.ta3n_adam_range(h, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), self.ws.data_ptr(),
+                                         0, self.plan.live_floats, self._adam_fused_norm(), *self._adam_args(lr, wd, clip), self._stream()),
+                       "ta3n_adam_range")
+            self.adam_step_count += 1
+            return None
         fused_norm = int(self.fused and self.world == 1)
         main = torch.cuda.current_stream(self.device)
-        L, h = self._L, self.plan.handle
 
         def rng(lo, hi, stream):
             _lib.check(L.ta3n_sgd_range(h, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.ws.data_ptr(), lo, hi,
@@ -835,7 +922,13 @@ class TrainEngine:
             lr_p, mu, wd, clip = self._pending
             self._pending = None
             fused_norm = int(self.world == 1 and not self._ddp_selftest)
-            if self._side_update and not two_buckets:
+            if self.optimizer == "Adam":      # one launch: the update of the step before + this step's scalars (ta3n_adam_step_next)
+                _lib.check(self._L.ta3n_adam_step_next(self.plan.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(),
+                                                       self.V.data_ptr(), self.ws.data_ptr(), self._adam_fused_norm(),
+                                                       *self._adam_args(lr_p, wd, clip), C.byref(self._hyper), self._stream()),
+                           "ta3n_adam_step_next")
+                self.adam_step_count += 1
+            elif self._side_update and not two_buckets:
                 # the update of everything but the shared frame FC rides in the new step's first launch
                 _lib.check(self._L.ta3n_train_step_after_update(self.plan.handle, self.X.data_ptr(), self.P.data_ptr(),
                                                                 self.G.data_ptr(), self.M.data_ptr(), self.ws.data_ptr(), fused_norm,
@@ -937,6 +1030,8 @@ class TrainEngine:
         ddp = self.world > 1 or self._ddp_selftest
         if fused_update is None:
             fused_update = os.environ.get("TA3N_FUSED_UPDATE", "0") == "1"
+        if fused_update and self.optimizer == "Adam":
+            raise NotImplementedError(adam_refusal(fused_update=True))
         if fused_update and not ddp and self.fused and self.bn_running is None and self._L.ta3n_has_fused_update(self.plan.handle) == 1:
             # the optimiser inside the gradient launches (ta3n_train_steps_fused_update): no separate update launches at all
             self.flush()
@@ -979,6 +1074,13 @@ class TrainEngine:
         job, keep, n_run = self._steps_job(schedule, feeds)
         if job is None:
             return
+        if self.optimizer == "Adam":      # the same pending-update contract: update number adam_step_count + 1 + k opens step k
+            _lib.check(self._L.ta3n_train_steps_adam(job.plan, job.x, job.params, job.grads, job.momentum, self.V.data_ptr(), job.ws,
+                                                     self._adam_fused_norm(), *self._adam_args(job.lr_pending, job.weight_decay, job.clip),
+                                                     job.hypers, n_run, job.source, job.target, job.stream), "ta3n_train_steps_adam")
+            self.adam_step_count += n_run
+            self._steps_done(schedule, keep, n_run)
+            return
         if self._sharded:      # the same steps with the sharded update; region B's collectives on a second stream
             if self._comm_stream is None:
                 self._comm_stream = torch.cuda.Stream(self.device)
@@ -1000,6 +1102,8 @@ class TrainEngine:
         ddp = self.world > 1 or self._ddp_selftest
         if self._sharded:
             return bool(self.comm is not None and not self.skip_collective)
+        if self.optimizer == "Adam":      # ta3n_train_steps_adam: the fused step, single rank (no side-workgroup update to ask for)
+            return bool(self.fused)
         return bool(self.fused and self._side_update and
                     not (ddp and (self.comm is None or self._ddp_buckets == 2 or self.skip_collective)))
 
@@ -1054,6 +1158,8 @@ class TrainEngine:
     def capture(self) -> None:
         """Capture forward+loss+backward(+all-reduce)+update into one hipGraph (shapes
         are static).  set_hyper / set_batch stay outside: they only write device buffers."""
+        if self.optimizer == "Adam":
+            raise NotImplementedError(adam_refusal(capture=True))
         torch.cuda.synchronize(self.device)
         keep_p, keep_m = self.P.clone(), self.M.clone()
         side = torch.cuda.Stream(self.device)
@@ -1099,6 +1205,8 @@ class TrainEngine:
         """(ms of the optimiser launch that opens a pipelined step, ms of the step's first GEMM launch carrying the rest of the
         update as side workgroups) - what train_step_pipelined runs instead of the plain first launch time_phases reports.
         Applies the update `reps` times: a measurement aid for the END of a benchmark run."""
+        if self.optimizer == "Adam":
+            raise NotImplementedError(adam_refusal(side_update=True))
         out = (C.c_float * 2)()
         fused_norm = int(self.world == 1 and not self._ddp_selftest)
         _lib.check(self._L.ta3n_time_update_launches(self.plan.handle, self.X.data_ptr(), self.P.data_ptr(), self.G.data_ptr(),

@@ -54,6 +54,9 @@ class TwoStreamEngine:
         stream against 0.5 ms of GPU work).  Bit-identical to train_step called once per entry."""
         if not schedule:
             return
+        if any(getattr(e, "optimizer", "SGD") == "Adam" for e in self.streams):
+            from .engine import adam_refusal
+            raise NotImplementedError(adam_refusal(two_stream=True))
         if not all(e.can_batch_steps() for e in self.streams):
             for beta, gamma, lr in schedule:
                 self.train_step(beta, gamma, lr)

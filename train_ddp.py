@@ -50,7 +50,11 @@ def validate_options(args, module_path: bool = False) -> None:
     if args.frame_aggregation == "avgpool":      # TemPooling: source-only (BASELINE configs[0]) or with the RevGrad branches; no attention
         need(args.use_attn == "none" and (args.add_loss_DA == "none" or args.use_target == "none"),
              "avgpool is built without attention / attentive entropy (--use_attn none --add_loss_DA none, as the reference's script runs it)")
-    need(args.optimizer == "SGD", f"--optimizer {args.optimizer} (built: SGD with Nesterov momentum, main.py:83)")
+    if module_path:      # main.py builds torch.optim.Adam (main.py:84-86) and trains it on the engine's Adam update (ta3n_adam_range)
+        need(args.optimizer in ("SGD", "Adam"), f"--optimizer {args.optimizer} (built: SGD with Nesterov momentum, Adam; main.py:81-89)")
+    else:
+        need(args.optimizer == "SGD", f"--optimizer {args.optimizer} (built: SGD with Nesterov momentum, main.py:83)" +
+             (" (built on main.py; train_ddp.py trains with SGD)" if args.optimizer == "Adam" else ""))
     if module_path:
         need(args.dis_DA in ("none", "DAN", "JAN"), f"--dis_DA {args.dis_DA} (built: DAN, JAN)")
         need(args.ens_DA in ("none", "MCD"), f"--ens_DA {args.ens_DA}")
