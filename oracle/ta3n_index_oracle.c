@@ -29,6 +29,27 @@ static int next_comb(int *c, int n, int k) {
     return 1;
 }
 
+/* ceil(num / den) as CPython evaluates int(math.ceil(num / den)) on integers: the double nearest to the exact
+ * quotient (one rounding, ties to even), then ceil.  (double)num / (double)den rounds twice above 2^53; the
+ * enumeration below never gets that far, but the index is formed the documented way all the same.  den is 1..3. */
+static uint64_t ceil_of_rounded_quotient(unsigned __int128 num, unsigned den) {
+    unsigned __int128 q = num / den, m;
+    unsigned r = (unsigned)(num % den);
+    int bits = 0, shift, up;
+    if (q < ((unsigned __int128)1 << 52)) return (uint64_t)q + (r != 0);
+    for (m = q; m; m >>= 1) ++bits;
+    shift = bits - 53;
+    m = q >> shift;
+    if (shift == 0) {
+        up = 2 * r > den || (2 * r == den && (m & 1));
+    } else {
+        unsigned __int128 low = q & (((unsigned __int128)1 << shift) - 1), half = (unsigned __int128)1 << (shift - 1);
+        up = low > half || (low == half && (r != 0 || (m & 1)));
+    }
+    if (up) ++m;
+    return (uint64_t)(m << shift);
+}
+
 /* Writes the selected tuples scale by scale (scale T first).  tuples is a
  * [n_out][T] row-major array padded with -1; scale_len[r] is the tuple size of
  * row r; scale_id[r] the scale index (0 = T-frame scale).  Returns n_out. */
@@ -42,7 +63,7 @@ int ta3n_oracle_relation_table(int T, int32_t *tuples, int32_t *scale_len, int32
         do { ++n_total; } while (next_comb(c, T, s));
         int n_sel = (sid == 0) ? 1 : (int)(n_total < SUBSAMPLE_NUM ? n_total : SUBSAMPLE_NUM);
         for (int i = 0; i < n_sel; ++i) {
-            long idx = (sid == 0) ? 0 : (long)ceil((double)(i * n_total) / (double)n_sel);
+            long idx = (sid == 0) ? 0 : (long)ceil_of_rounded_quotient((unsigned __int128)i * (unsigned __int128)n_total, (unsigned)n_sel);
             for (int j = 0; j < s; ++j) c[j] = j;
             for (long r = 0; r < idx; ++r) next_comb(c, T, s);
             for (int j = 0; j < T; ++j) tuples[(size_t)n_out * T + j] = (j < s) ? c[j] : -1;

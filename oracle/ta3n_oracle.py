@@ -58,6 +58,25 @@ def relation_scales(num_frames: int) -> List[int]:
     return [i for i in range(num_frames, 1, -1)]
 
 
+def _nth_combination(n: int, k: int, index: int) -> Tuple[int, ...]:
+    """The index-th (0-based) element of itertools.combinations(range(n), k) without enumerating: the combinations that
+    start with x number C(n - x - 1, k - 1), so the first element is found by walking x upwards and subtracting those
+    counts from the index; the remaining k - 1 elements follow the same way among the values above x.  Python integers."""
+    if not 0 <= index < math.comb(n, k):
+        raise IndexError(f"combination {index} of C({n},{k})")
+    out, x = [], 0
+    for left in range(k, 0, -1):
+        while True:
+            starting_here = math.comb(n - x - 1, left - 1)
+            if index < starting_here:
+                break
+            index -= starting_here
+            x += 1
+        out.append(x)
+        x += 1
+    return tuple(out)
+
+
 def selected_relations(num_frames: int) -> List[List[Tuple[int, ...]]]:
     """Frame tuples actually used by RelationModuleMultiScale.forward.
 
@@ -65,7 +84,27 @@ def selected_relations(num_frames: int) -> List[List[Tuple[int, ...]]]:
     itertools.combinations, TRNmodule.py:84-86), :60 (scale 0 uses tuple 0),
     :68-71 (later scales use idx = int(ceil(i * n_total / n_select)) for
     i < min(3, n_total)).
+
+    The reference builds every list and indexes it; here the list's length is math.comb and its idx-th element comes
+    from _nth_combination, so 64 segments (C(64,32) ~ 1.8e18 tuples in the middle scale) cost what 5 do.  The index is
+    the reference's own expression evaluated by CPython: int / int is the correctly rounded double of the exact
+    quotient.  selected_relations_enumerated is the literal restatement, for cross-checks at small T.
     """
+    out = []
+    for sid, scale in enumerate(relation_scales(num_frames)):
+        if sid == 0:
+            out.append([_nth_combination(num_frames, scale, 0)])
+            continue
+        n_total = math.comb(num_frames, scale)
+        n_sel = min(SUBSAMPLE_NUM, n_total)
+        idx = [int(math.ceil(i * n_total / n_sel)) for i in range(n_sel)]
+        out.append([_nth_combination(num_frames, scale, i) for i in idx])
+    return out
+
+
+def selected_relations_enumerated(num_frames: int) -> List[List[Tuple[int, ...]]]:
+    """selected_relations the way the reference does it: every C(T,s) tuple listed with itertools.combinations, then
+    indexed.  Memory grows like C(T, T/2): usable up to about 20 segments."""
     out = []
     for sid, scale in enumerate(relation_scales(num_frames)):
         rel = list(itertools.combinations(range(num_frames), scale))

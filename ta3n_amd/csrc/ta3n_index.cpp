@@ -45,6 +45,28 @@ void unrank(int n, int k, uint64_t idx, int32_t *out) {
     }
 }
 
+// ceil(num / den) the way CPython evaluates int(math.ceil(num / den)) on integers: `/` gives the double nearest to the EXACT quotient
+// (one rounding, ties to even), ceil acts on that double.  (double)num / (double)den rounds twice once num passes 2^53 - at 57 or more
+// segments - and then lands on another tuple than the reference's expression.  den is 1..3 here.
+uint64_t ceil_of_rounded_quotient(unsigned __int128 num, unsigned den) {
+    const unsigned __int128 q = num / den;
+    const unsigned r = (unsigned)(num % den);
+    if (q < ((unsigned __int128)1 << 52)) return (uint64_t)q + (r != 0);      // doubles are at most 0.5 apart: a fraction of 1/3 .. 2/3 stays inside (q, q + 1)
+    int bits = 0;
+    for (unsigned __int128 t = q; t; t >>= 1) ++bits;
+    const int shift = bits - 53;                                             // the double keeps the top 53 bits of q
+    unsigned __int128 m = q >> shift;
+    bool up;
+    if (shift == 0) {
+        up = 2 * r > den || (2 * r == den && (m & 1));
+    } else {
+        const unsigned __int128 low = q & (((unsigned __int128)1 << shift) - 1), half = (unsigned __int128)1 << (shift - 1);
+        up = low > half || (low == half && (r != 0 || (m & 1)));
+    }
+    if (up) ++m;
+    return (uint64_t)(m << shift);                                           // an integer already: ceil leaves it
+}
+
 }  // namespace
 
 extern "C" int ta3n_num_relation_tuples(int T) {
@@ -64,9 +86,9 @@ extern "C" int ta3n_relation_table(int T, int32_t *tuples, int32_t *scale_len, i
         const uint64_t n_total = binom(T, s);
         const int n_sel = (sid == 0) ? 1 : (int)(n_total < (uint64_t)kSubsample ? n_total : (uint64_t)kSubsample);
         for (int i = 0; i < n_sel; ++i) {
-            // TRNmodule.py:71  int(ceil(i * num_total / num_select)) in Python float arithmetic
+            // TRNmodule.py:71  int(ceil(i * num_total / num_select)) in Python arithmetic: exact integer product, true division
             uint64_t idx = 0;
-            if (sid != 0) idx = (uint64_t)std::ceil((double)((uint64_t)i * n_total) / (double)n_sel);
+            if (sid != 0) idx = ceil_of_rounded_quotient((unsigned __int128)i * n_total, (unsigned)n_sel);
             int32_t *row = tuples + (size_t)n_out * T;
             unrank(T, s, idx, row);
             for (int j = s; j < T; ++j) row[j] = -1;

@@ -321,6 +321,14 @@ class TrainEngine:
         self._mcd_native = self.ens_DA == "MCD" and os.environ.get("TA3N_NATIVE_MCD", "1") != "0"
         # fused: forward + loss + backward as ONE C-ABI call (ta3n_train_step, 7 launches) when the plan has it
         self.fused = bool(fused) and p.has_fused_step
+        # ... and where it has not (trn-m: fc_dim > 2048 - the heads kernel keeps ceil(F / 64) <= 32 frame channels per lane) the step runs
+        # as the unfused launch lists: the same results from about twice the launches.  Said once, not silently (describe()).
+        self.fused_fallback: Optional[str] = None
+        if fused and not p.has_fused_step:
+            self.fused_fallback = (f"no fused step for num_class {num_class}, fc_dim {self.F} (needs num_class <= 64 and fc_dim <= 2048): "
+                                   "forward / loss / backward run as the unfused launch lists")
+            if self.rank == 0:
+                print(f"[ta3n] {self.fused_fallback}", flush=True)
         # deferred update: the optimiser step of call s is enqueued at the start of call s + 1, split so that everything but
         # the shared frame FC updates on a side stream beside the next step's first launch (include/ta3n_hip.h: ta3n_sgd_range)
         self._pending = None
@@ -405,6 +413,13 @@ class TrainEngine:
         self.skip_collective = False
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._hyper = _lib.Hyper()
+
+    def describe(self) -> str:
+        """One line: the configuration this engine runs, the launch lists of its step included."""
+        arith = "bf16" if self.bf16 else "f32x3" if self._flags & _lib.FLAG_F32_SPLIT else "fp32"
+        step = "fused step" if self.fused else "unfused launch lists" + (f" ({self.fused_fallback})" if self.fused_fallback else "")
+        return (f"TrainEngine {self.Bs}+{self.Bt} videos x {self.T} segments, feature_dim {self.D}, fc_dim {self.F}, {self.C} classes, "
+                f"{self.aggregation}, {arith}{' on twins' if self.bf16_store else ''}, {self.optimizer}, world {self.world}: {step}")
 
     # ---- plumbing ----
     def _stream(self) -> C.c_void_p:

@@ -21,6 +21,9 @@ F32_GRAD_MAX_SCALE = 3e-2          # measured worst 7.7e-3
 # front of a 3 072-row weight gradient whose adversarial and classification parts cancel; 25 x tighter than the free-running bound)
 F32_MASKED_GRAD_REL_L2 = 2e-4
 F32_MASKED_GRAD_REL_L2_MEDIAN = 2e-5
+# (at the limits of the accepted shapes - 64 segments, 1 / 64 classes, fc_dim up to 2048 and past it, dimensions that are no multiples
+# of 4 - the same two bounds hold against the float64 oracle, and the logits are held to LOGIT_ATOL x max(1, max |logit| / 10): they
+# grow with the relation count, ~230 at 64 segments.  tests/test_gpu_limit_shapes.py; floors in profiles/limit_shapes_parity_floors.txt)
 # Against the reference's RECORDED multi-step trajectories (golden vectors): from the second step on the two sides stand on
 # parameters that differ by round-off, more ReLU units switch sides; the per-tensor bound is scaled by this factor there.
 GOLDEN_DRIFT_FACTOR = 2.0         # measured worst later-step tensor: 1.1e-3 (fp32), 1.6e-3 (f32x3)

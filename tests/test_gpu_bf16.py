@@ -206,6 +206,11 @@ def test_bf16_other_baseline_config_shapes(shape):
 def test_bf16_twins_fall_back_per_launch_on_odd_shapes(shape):
     """Dimensions that are not multiples of 8: the launches whose operands cannot move 16 bytes at a time keep rounding fp32
     operands in registers, the others read twins - and the whole step still matches the bf16-operand model of its plan."""
+    _twin_step_matches_the_bf16_operand_model_of_its_plan(shape)
+
+
+def _twin_step_matches_the_bf16_operand_model_of_its_plan(shape):
+    """(shared with tests/test_gpu_limit_shapes.py)"""
     from ta3n_amd.engine import TrainEngine
     eng = TrainEngine(shape["Bs"], shape["Bt"], shape["T"], shape["D"], shape["F"], shape["C"], dropout_i=0.0, dropout_v=0.0,
                       bf16=True, bf16_store=True)

@@ -58,14 +58,31 @@ def test_relation_tuples_bit_exact(T, c_oracle):
 
 
 def test_relation_tuples_large_T_unranking_only():
-    # T = 40: C(40,20) ~ 1.4e11 tuples per scale - enumeration is impossible, unranking is instant
-    rel = _lib.relation_table(40)
-    assert len(rel) == 39 and all(len(s) <= 3 for s in rel)
-    for s in rel:
-        for t in s:
-            assert list(t) == sorted(set(t)) and 0 <= t[0] and t[-1] < 40
-        assert s == sorted(s)
-    assert rel[-1][0] == (0, 1)
+    # T = 40: C(40,20) ~ 1.4e11 tuples per scale - enumeration is impossible, unranking is instant; T = 64: the largest plan accepted
+    for T in (40, 64):
+        rel = _lib.relation_table(T)
+        assert len(rel) == T - 1 and all(len(s) <= 3 for s in rel)
+        for s in rel:
+            for t in s:
+                assert list(t) == sorted(set(t)) and 0 <= t[0] and t[-1] < T
+            assert s == sorted(s)
+        assert rel[-1][0] == (0, 1)
+
+
+@pytest.mark.parametrize("T", list(range(2, 17)))
+def test_oracle_unranking_equals_its_enumeration(T):
+    """The oracle's enumeration-free selected_relations against the literal restatement of the reference (every tuple listed, then
+    indexed), as far as the fixtures from the reference itself go."""
+    assert orc.selected_relations(T) == orc.selected_relations_enumerated(T)
+
+
+@pytest.mark.parametrize("T", list(range(2, 65)))
+def test_relation_table_equals_the_oracle_unranking_over_the_accepted_range(T):
+    """Every num_segments a plan accepts: the library's table (128-bit integer quotient, rounded once to a double, then ceil) against
+    the oracle's unranking in Python integers with the index from the reference's expression evaluated by CPython.  From 57 segments
+    on i * C(T, s) passes 2^53 and a quotient of two rounded doubles lands on other tuples than int(ceil(i * n_total / n_select))."""
+    assert _lib.relation_table(T) == orc.selected_relations(T)
+    assert sum(len(s) for s in orc.selected_relations(T)) == _lib.lib().ta3n_num_relation_tuples(T)
 
 
 @pytest.mark.parametrize("T,new_length", [(5, 1), (3, 1), (9, 1), (25, 1), (5, 5), (12, 2)])
