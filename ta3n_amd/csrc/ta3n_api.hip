@@ -436,6 +436,12 @@ int ta3n_time_phases(ta3n_plan *p, const float *x, float *params, float *grads, 
     return n;
 }
 
+// The side job of a pipelined step's first GEMM launch: the update of everything but the shared frame FC, on the step's norm partials
+static SgdSide update_side(const Geom &g, float *params, float *momentum, float lr, float mu, float wd, float clip, int fused_norm) {
+    const NormSource ns = norm_source(g, fused_norm != 0);
+    return SgdSide{params, momentum, lr, mu, wd, clip, ns.off, ns.n, g.o_p16};
+}
+
 // The two launches that open a pipelined step (ta3n_train_step_after_update): the optimiser update of the shared frame FC,
 // and the first GEMM launch carrying the rest of the update as side workgroups.  Unlike ta3n_time_phases this APPLIES the
 // update `reps` times (a measurement aid for the end of a benchmark run).
@@ -453,8 +459,7 @@ int ta3n_time_update_launches(ta3n_plan *p, const float *x, float *params, float
     Hyper next;
     HIP_TRY(hipMemcpyAsync(&next, ws + g.o_hyper, sizeof(Hyper), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    SgdSide side{params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm ? g.o_sumsq : g.o_norm_part,
-                 fused_norm ? g.n_sumsq : g.n_norm_blocks, g.o_p16};
+    const SgdSide side = update_side(g, params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm);
     Ptrs ptrs = make_ptrs(p, x, params, grads, ws);
     HIP_TRY(hipEventRecord(ev[0], s));
     for (int k = 0; k < reps; ++k)
@@ -582,8 +587,7 @@ int ta3n_train_step_after_update(ta3n_plan *p, const float *x, float *params, fl
                          reinterpret_cast<const Hyper *>(next), s) != 0)
         return fail(TA3N_ERR_HIP, "sgd launch failed");
     // (2) the new step's first launch, with the rest of the update as side tasks; (3) the other launches of the step
-    SgdSide side{params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm ? g.o_sumsq : g.o_norm_part,
-                 fused_norm ? g.n_sumsq : g.n_norm_blocks, g.o_p16};
+    const SgdSide side = update_side(g, params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm);
     Ptrs ptrs = make_ptrs(p, x, params, grads, ws);
     rc = run_group(p, 5, ptrs, nullptr, nullptr, s, nullptr, 0, 1 << 30, &side);
     if (rc != TA3N_OK) return rc;
@@ -653,8 +657,7 @@ static int enqueue_pipelined_step(ta3n_plan *p, const Ptrs &ptrs, float *params,
                              reinterpret_cast<const Hyper *>(next), s) != 0)
             return fail(TA3N_ERR_HIP, "sgd launch failed");
     }
-    SgdSide side{params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm ? g.o_sumsq : g.o_norm_part,
-                 fused_norm ? g.n_sumsq : g.n_norm_blocks, g.o_p16};
+    const SgdSide side = update_side(g, params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm);
     if ((rc = run_group(p, 5, ptrs, nullptr, nullptr, s, nullptr, 0, 1 << 30, &side)) != TA3N_OK) return rc;
     if ((rc = run_group(p, 4, ptrs, nullptr, nullptr, s, nullptr, 1, 1 << 30)) != TA3N_OK) return rc;
     // data parallel: the step's single exchange, on the step's stream, between the last gradient launch and the update

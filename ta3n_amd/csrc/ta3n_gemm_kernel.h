@@ -772,8 +772,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         if (lane == 0 && wave < 4) lds[wave] = part;
         __syncthreads();
         const float total = sqrtf(((lds[0] + lds[1]) + lds[2]) + lds[3]);
-        float coef = 1.f;
-        if (side.clip > 0.f) coef = fminf(side.clip / (total + 1e-6f), 1.f);
+        const float coef = clip_coef(total, side.clip);
         float4 *__restrict__ p4 = reinterpret_cast<float4 *>(side.params);
         float4 *__restrict__ m4 = reinterpret_cast<float4 *>(side.momentum);
         const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(ptrs.g);
@@ -781,12 +780,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             const float4 p = p4[i], m = m4[i], gr = g4[i];
             float gg[4] = {gr.x, gr.y, gr.z, gr.w}, pp[4] = {p.x, p.y, p.z, p.w}, mm[4] = {m.x, m.y, m.z, m.w};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float d = fmaf(side.wd, pp[e], gg[e] * coef);
-                mm[e] = fmaf(side.mu, mm[e], d);
-                d = fmaf(side.mu, mm[e], d);
-                pp[e] = fmaf(-side.lr, d, pp[e]);
-            }
+            for (int e = 0; e < 4; ++e) nesterov_sgd(pp[e], mm[e], gg[e] * coef, side.lr, side.mu, side.wd);
             if (pub) st_pub(reinterpret_cast<float *>(p4 + i), f32x4{pp[0], pp[1], pp[2], pp[3]});
             else p4[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
             m4[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
@@ -829,10 +823,8 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             sq = fmaf(v, v, sq);
             if (OPT && side.p_new != nullptr && t.c_base == BASE_G) {     // fused update of these parameters (see the tile epilogue)
                 const size_t pi = (size_t)t.c_off + n;
-                const float p0 = ptrs.p[pi];
-                float d = fmaf(side.wd, p0, v), mm = fmaf(side.mu, side.momentum[pi], d);
-                d = fmaf(side.mu, mm, d);
-                const float p1 = fmaf(-side.lr, d, p0);
+                float p1 = ptrs.p[pi], mm = side.momentum[pi];
+                nesterov_sgd(p1, mm, v, side.lr, side.mu, side.wd);
                 side.p_new[pi] = p1; side.momentum[pi] = mm;
                 if (side.p16_new != nullptr) reinterpret_cast<unsigned short *>(side.p16_new)[pi] = (unsigned short)(pack_bf16(p1, 0.f) & 0xFFFF);
             }
@@ -1292,10 +1284,8 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             float pn[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float d = fmaf(side.wd, up[e], v[e]);
-                um[e] = fmaf(side.mu, um[e], d);
-                d = fmaf(side.mu, um[e], d);
-                pn[e] = fmaf(-side.lr, d, up[e]);
+                pn[e] = up[e];
+                nesterov_sgd(pn[e], um[e], v[e], side.lr, side.mu, side.wd);
             }
             if (nrem >= 4 && c_vec) {
                 *reinterpret_cast<float4 *>(side.p_new + pi) = make_float4(pn[0], pn[1], pn[2], pn[3]);
@@ -1377,10 +1367,8 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
                 sumsq = fmaf(b, b, sumsq);
                 if (upd && t.bias_base == BASE_G) {      // the bias gradient's own parameter entries
                     const size_t pi = (size_t)t.bias_off + m0 + tid;
-                    const float p0 = ptrs.p[pi];
-                    float d = fmaf(side.wd, p0, b), mm = fmaf(side.mu, side.momentum[pi], d);
-                    d = fmaf(side.mu, mm, d);
-                    const float p1 = fmaf(-side.lr, d, p0);
+                    float p1 = ptrs.p[pi], mm = side.momentum[pi];
+                    nesterov_sgd(p1, mm, b, side.lr, side.mu, side.wd);
                     side.p_new[pi] = p1; side.momentum[pi] = mm;
                     if (side.p16_new != nullptr) reinterpret_cast<unsigned short *>(side.p16_new)[pi] = (unsigned short)(pack_bf16(p1, 0.f) & 0xFFFF);
                 }

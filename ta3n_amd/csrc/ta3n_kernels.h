@@ -150,7 +150,33 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
 __device__ __forceinline__ unsigned pack_bf16_lo(float x0, float x1, unsigned hi) {
     return pack_bf16(x0 - __builtin_bit_cast(float, hi << 16), x1 - __builtin_bit_cast(float, hi & 0xFFFF0000u));
 }
+
+// The optimiser arithmetic, written ONCE: every training path (plain, deferred, pipelined, sharded, the EPI_SGD side job of gemm_tile, the
+// fused-update tiles) must produce the same bits, so each of them calls these (the Adam rule, adam_update, is beside its kernel).  Device code is compiled with contraction on: the fmaf
+// forms below are the arithmetic, keep every expression as written.
+// clip_grad_norm_: coef = clip / (total_norm + 1e-6) clamped to 1; clip <= 0: no clipping
+__device__ __forceinline__ float clip_coef(float total, float clip) {
+    float coef = 1.f;
+    if (clip > 0.f) coef = fminf(clip / (total + 1e-6f), 1.f);
+    return coef;
+}
+// torch.optim.SGD(nesterov=True) on one element, g_scaled = g * coef:  d = g_scaled + wd p;  m = mu m + d;  d += mu m;  p -= lr d
+__device__ __forceinline__ void nesterov_sgd(float &p, float &m, float g_scaled, float lr, float mu, float wd) {
+    float d = fmaf(wd, p, g_scaled);
+    m = fmaf(mu, m, d);
+    d = fmaf(mu, m, d);
+    p = fmaf(-lr, d, p);
+}
 #endif
+
+// Where an update finds the squared-norm partials of its step: the per-tile slots the fused step's gradient tiles left behind, or the
+// per-block partials of grad_norm_kernel (also the sharded update's per-rank slots)
+struct NormSource {
+    int32_t off, n;      // ws offset, count
+};
+inline NormSource norm_source(const Geom &g, bool fused_norm) {
+    return fused_norm ? NormSource{g.o_sumsq, g.n_sumsq} : NormSource{g.o_norm_part, g.n_norm_blocks};
+}
 
 int launch_to_bf16(const float *src, float *dst_twin, int64_t n, hipStream_t stream);   // n fp32 -> n bf16 (RNE), n % 4 == 0
 int launch_to_bf16_pair(const float *src, float *dst_hi, float *dst_lo, int64_t n, hipStream_t stream);   // ... and the lo plane

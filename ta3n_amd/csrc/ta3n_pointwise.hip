@@ -310,68 +310,126 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
     }
 }
 
+// acc + |v|^2, the four squares added in lane order (every sum of squares of the gradient norm uses this order)
+__device__ __forceinline__ float sumsq4(const float4 v, float acc) {
+    acc = fmaf(v.x, v.x, acc); acc = fmaf(v.y, v.y, acc); acc = fmaf(v.z, v.z, acc); acc = fmaf(v.w, v.w, acc);
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void grad_norm_kernel(const float *__restrict__ grads, float *__restrict__ part, int n4) {
     __shared__ float red[8];
     float acc = 0.f;
     const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
-        const float4 v = g4[i];
-        acc = fmaf(v.x, v.x, acc); acc = fmaf(v.y, v.y, acc); acc = fmaf(v.z, v.z, acc); acc = fmaf(v.w, v.w, acc);
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) acc = sumsq4(g4[i], acc);
     const float s = block_sum(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// clip_grad_norm_ (total_norm over all grads, coef = clip/(norm+1e-6) clamped to 1)
-// then torch.optim.SGD(nesterov=True): g += wd*p; buf = mu*buf + g; g += mu*buf; p -= lr*g.
-// norm_off / norm_n: the partial sums of squares to add up (grad_norm_kernel's per-block partials, or the
-// per-tile partials the fused step's gradient tiles left behind).
-__global__ __launch_bounds__(256) void sgd_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
-                                                  float *__restrict__ mom, float *__restrict__ ws, int n4, int norm_off, int norm_n) {
-    __shared__ float red[8];
-    const Hyper *__restrict__ hy = reinterpret_cast<const Hyper *>(ws + g.o_hyper);
-    float4 *__restrict__ p4 = reinterpret_cast<float4 *>(params);
-    float4 *__restrict__ m4 = reinterpret_cast<float4 *>(mom);
-    const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
-    // the first elements are requested before the norm partials are added up: every workgroup repeats that reduction
-    // (a fixed-order sum of a few thousand floats), and the stream should not wait behind it
-    const int stride = gridDim.x * blockDim.x;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, gr = p;
-    if (i < n4) { p = p4[i]; m = m4[i]; gr = g4[i]; }
-    float acc = 0.f;
-    acc = strided_partial_sum(ws + norm_off, norm_n, (int)threadIdx.x, (int)blockDim.x);
+// What every update launch does before it touches an element: adds up the step's squared-norm partials (norm_off / norm_n: see
+// norm_source) - every workgroup repeats that fixed-order sum of a few thousand floats - and forms the clip coefficient; block 0
+// records norm and coefficient if `record`, and leaves the per-step scalars of the NEXT step in ws.hyper if `has_next` (the
+// launch takes its own scalars by value and never reads ws.hyper).  Returns the coefficient.
+__device__ __forceinline__ float update_prologue(const Geom &g, float *__restrict__ ws, int norm_off, int norm_n, float clip, bool record,
+                                                 const Hyper &next, bool has_next, float *red) {
+    const float acc = strided_partial_sum(ws + norm_off, norm_n, (int)threadIdx.x, (int)blockDim.x);
     const float total = sqrtf(block_sum(acc, red));
-    float coef = 1.f;
-    if (hy->clip > 0.f) coef = fminf(hy->clip / (total + 1e-6f), 1.f);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const float coef = clip_coef(total, clip);
+    if (record && blockIdx.x == 0 && threadIdx.x == 0) {
         ws[g.o_grad_norm] = total;
         ws[g.o_grad_norm + 1] = coef;
     }
-    const float lr = hy->lr, mu = hy->momentum, wd = hy->weight_decay;
-    while (i < n4) {
-        const int nxt = i + stride;
-        float4 pn = p, mn = m, gn = gr;
-        if (nxt < n4) { pn = p4[nxt]; mn = m4[nxt]; gn = g4[nxt]; }   // next element in flight while this one is updated
-        float gg[4] = {gr.x, gr.y, gr.z, gr.w};
-        float pp[4] = {p.x, p.y, p.z, p.w};
-        float mm[4] = {m.x, m.y, m.z, m.w};
+    if (has_next && blockIdx.x == 0 && threadIdx.x < (int)(sizeof(Hyper) / 4))
+        reinterpret_cast<uint32_t *>(ws + g.o_hyper)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&next)[threadIdx.x];
+    return coef;
+}
+
+// torch.optim.Adam (amsgrad False, maximize False, L2 weight decay added to the gradient: reference main.py:84-86, 578-583) on one element:
+//     d = g_scaled + wd p;  m = b1 m + (1 - b1) d;  v = b2 v + (1 - b2) d d;  p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+// step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t) and the two complements 1 - b1, 1 - b2 come from the host, formed in double the way
+// torch forms them (a complement taken from the fp32 beta would be off by 1e-5 relative for b2 = 0.999).  Exact sqrtf and divide.
+struct AdamScalars {
+    float b1, omb1, b2, omb2, step_size, bc2_sqrt, eps, wd, clip;
+};
+__device__ __forceinline__ void adam_update(float &p, float &m, float &v, float g_scaled, const AdamScalars &a) {
+    const float d = fmaf(a.wd, p, g_scaled);
+    m = fmaf(a.b1, m, a.omb1 * d);
+    v = fmaf(a.b2, v, (a.omb2 * d) * d);
+    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+    p = fmaf(-a.step_size, m / denom, p);
+}
+
+// The element rule of an update launch: its scalars, its NS state arrays (beside the parameters) and the rule on one element.
+struct SgdRule {
+    static constexpr int NS = 1;      // momentum
+    float *state[NS];
+    float lr, mu, wd;
+    __device__ __forceinline__ void apply(float &p, float (&s)[NS], float g_scaled) const { nesterov_sgd(p, s[0], g_scaled, lr, mu, wd); }
+};
+struct AdamRule {
+    static constexpr int NS = 2;      // exp_avg, exp_avg_sq
+    float *state[NS];
+    AdamScalars a;
+    __device__ __forceinline__ void apply(float &p, float (&s)[NS], float g_scaled) const { adam_update(p, s[0], s[1], g_scaled, a); }
+};
+
+// clip_grad_norm_ + the rule's update over floats [4 i0, 4 i1) of the flat prefix, n_blocks workgroups striding it: THE update loop of
+// sgd_kernel, sgd_range_kernel, sgd_open_feed_kernel and adam_range_kernel.  The first element is requested before the norm partials
+// are added up (the stream should not wait behind that reduction), then the next element's loads are in flight while the current one
+// is updated; the bf16 twins of the new parameters (hi plane, lo plane with pair twins) are written in the same pass.
+// has_next: bit 0 = `next` is valid, bit 1 = this launch records the norm / clip coefficient although its range does not start at 0 (one
+// launch per rank and step records: the range that starts at 0, or - sharded update - whichever of the rank's own ranges is launched first)
+template <class Rule>
+__device__ __forceinline__ void update_range(const Geom &g, float *__restrict__ params, const float *__restrict__ grads, float *__restrict__ ws,
+                                             int i0, int i1, int norm_off, int norm_n, float clip, const Rule &rule, const Hyper &next,
+                                             int has_next, int n_blocks, float *red) {
+    constexpr int NS = Rule::NS;
+    float4 *__restrict__ p4 = reinterpret_cast<float4 *>(params);
+    const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
+    struct Elem { float4 p, s[NS], g; };      // parameters, the rule's state, gradients of one float4 element
+    auto load = [&](int j) {
+        Elem e;
+        e.p = p4[j];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float d = fmaf(wd, pp[e], gg[e] * coef);
-            mm[e] = fmaf(mu, mm[e], d);
-            d = fmaf(mu, mm[e], d);
-            pp[e] = fmaf(-lr, d, pp[e]);
-        }
+        for (int k = 0; k < NS; ++k) e.s[k] = reinterpret_cast<const float4 *>(rule.state[k])[j];
+        e.g = g4[j];
+        return e;
+    };
+    const int stride = n_blocks * blockDim.x;
+    int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    Elem cur = {};
+    if (i < i1) cur = load(i);      // in flight while the norm partials are added up
+    const float coef = update_prologue(g, ws, norm_off, norm_n, clip, i0 == 0 || (has_next & 2), next, has_next & 1, red);
+    while (i < i1) {
+        const int nxt = i + stride;
+        Elem nx = cur;
+        if (nxt < i1) nx = load(nxt);      // next element in flight while this one is updated
+        const float gg[4] = {cur.g.x, cur.g.y, cur.g.z, cur.g.w};
+        float pp[4] = {cur.p.x, cur.p.y, cur.p.z, cur.p.w};
+        float ss[4][NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) { ss[0][k] = cur.s[k].x; ss[1][k] = cur.s[k].y; ss[2][k] = cur.s[k].z; ss[3][k] = cur.s[k].w; }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rule.apply(pp[e], ss[e], gg[e] * coef);
         p4[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        m4[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+#pragma unroll
+        for (int k = 0; k < NS; ++k) reinterpret_cast<float4 *>(rule.state[k])[i] = make_float4(ss[0][k], ss[1][k], ss[2][k], ss[3][k]);
         if (g.o_p16 >= 0) {
             const unsigned h0 = pack_bf16(pp[0], pp[1]), h1 = pack_bf16(pp[2], pp[3]);
             reinterpret_cast<uint2 *>(ws + g.o_p16)[i] = make_uint2(h0, h1);
             if (g.pair_delta) reinterpret_cast<uint2 *>(ws + g.o_p16 + g.pair_delta)[i] = make_uint2(pack_bf16_lo(pp[0], pp[1], h0), pack_bf16_lo(pp[2], pp[3], h1));
         }
-        i = nxt; p = pn; m = mn; gr = gn;
+        i = nxt; cur = nx;
     }
+}
+
+// clip_grad_norm_ + torch.optim.SGD(nesterov=True) over the whole live prefix.  The step's scalars are read from ws.hyper when the
+// kernel RUNS: it follows the latest ta3n_set_hyper on the stream.  (No next step's scalars ride along: has_next = 0, `next` is not read.)
+__global__ __launch_bounds__(256) void sgd_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
+                                                  float *__restrict__ mom, float *__restrict__ ws, int n4, int norm_off, int norm_n) {
+    __shared__ float red[8];
+    const Hyper *__restrict__ hy = reinterpret_cast<const Hyper *>(ws + g.o_hyper);
+    update_range(g, params, grads, ws, 0, n4, norm_off, norm_n, hy->clip, SgdRule{{mom}, hy->lr, hy->momentum, hy->weight_decay}, *hy, 0,
+                 (int)gridDim.x, red);
 }
 
 
@@ -486,6 +544,11 @@ __global__ __launch_bounds__(256) void pool_avg_bwd_kernel(Geom g, Ptrs ptrs, in
 // TSNDataSet.__getitem__ for a whole batch on the device (reference dataset.py:103-116, 128-144, new_length 1):
 // one workgroup per output row (video v, segment x).  The segment index is computed in float64 exactly as the
 // reference's Python does (tick = n / T; int(tick / 2.0 + tick * x)); clips shorter than T repeat their last frame.
+__device__ __forceinline__ int segment_offset(int nf, int T, int x) {
+    if (nf < T) return x < nf ? x : nf - 1;
+    const double tick = (double)nf / (double)T;             // dataset.py:103-116, float64 like the reference's Python
+    return (int)(tick / 2.0 + tick * (double)x);
+}
 __device__ __forceinline__ void gather_row_f32(int row, const float *__restrict__ store, const int64_t *__restrict__ first_row,
                                                const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
                                                const int32_t *__restrict__ video_ids, int T, int D,
@@ -494,13 +557,7 @@ __device__ __forceinline__ void gather_row_f32(int row, const float *__restrict_
     const int v = row / T, x = row - v * T;
     const int vid = video_ids[v];
     const int nf = num_frames[vid];
-    int off;
-    if (nf >= T) {
-        const double tick = (double)nf / (double)T;
-        off = (int)(tick / 2.0 + tick * (double)x);
-    } else {
-        off = x < nf ? x : nf - 1;
-    }
+    const int off = segment_offset(nf, T, x);
     if (threadIdx.x == 0) {
         if (seg_out) seg_out[row] = off + 1;                    // the reference's ids are 1-based (img_00001.t7)
         if (labels_out && x == 0) labels_out[v] = labels[vid];
@@ -543,13 +600,7 @@ __device__ __forceinline__ void gather_row_bf16(int row, const uint4 *__restrict
     const int v = row / T, x = row - v * T;
     const int vid = video_ids[v];
     const int nf = num_frames[vid];
-    int off;
-    if (nf >= T) {
-        const double tick = (double)nf / (double)T;             // dataset.py:103-116, float64 like the reference's Python
-        off = (int)(tick / 2.0 + tick * (double)x);
-    } else {
-        off = x < nf ? x : nf - 1;
-    }
+    const int off = segment_offset(nf, T, x);
     if (threadIdx.x == 0 && labels_out && x == 0) labels_out[v] = labels[vid];
     const uint4 *__restrict__ src = store + (size_t)(first_row[vid] + off) * (D / 8);
     for (int i = threadIdx.x; i < D / 8; i += 256) {
@@ -615,129 +666,23 @@ __global__ __launch_bounds__(1024) void eval_metrics_kernel(Geom g, float *__res
     if (threadIdx.x == 3) ws[g.o_metrics + 3] = (reset ? 0.f : ws[g.o_metrics + 3]) + (float)n;
 }
 
-// The same update over floats [4 i0, 4 i1) of the flat prefix with the step's scalars passed by value: lets the host
-// split the update so that the first launch of the NEXT step (which only reads the shared frame FC) runs beside the rest
-// of this one on a second stream, and keeps it independent of a newer ta3n_set_hyper upload.
-__device__ __forceinline__ void sgd_range_body(const Geom &g, float *__restrict__ params, const float *__restrict__ grads,
-                                               float *__restrict__ mom, float *__restrict__ ws, int i0, int i1, int norm_off,
-                                               int norm_n, float lr, float mu, float wd, float clip, const Hyper &next, int has_next,
-                                               int n_blocks, float *red) {
-    float4 *__restrict__ p4 = reinterpret_cast<float4 *>(params);
-    float4 *__restrict__ m4 = reinterpret_cast<float4 *>(mom);
-    const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
-    const int stride = n_blocks * blockDim.x;
-    int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, gr = p;
-    if (i < i1) { p = p4[i]; m = m4[i]; gr = g4[i]; }      // in flight while the norm partials are added up
-    float acc = 0.f;
-    acc = strided_partial_sum(ws + norm_off, norm_n, (int)threadIdx.x, (int)blockDim.x);
-    const float total = sqrtf(block_sum(acc, red));
-    float coef = 1.f;
-    if (clip > 0.f) coef = fminf(clip / (total + 1e-6f), 1.f);
-    // has_next: bit 0 = `next` is valid, bit 1 = this launch records the norm / clip coefficient (one launch per rank and step does: the
-    // range that starts at 0, or - sharded update - whichever of the rank's own ranges is launched first)
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (i0 == 0 || (has_next & 2))) {
-        ws[g.o_grad_norm] = total;
-        ws[g.o_grad_norm + 1] = coef;
-    }
-    // the per-step scalars of the NEXT step ride along (this kernel takes its own by value and never reads ws.hyper)
-    if ((has_next & 1) && blockIdx.x == 0 && threadIdx.x < (int)(sizeof(Hyper) / 4))
-        reinterpret_cast<uint32_t *>(ws + g.o_hyper)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&next)[threadIdx.x];
-    while (i < i1) {
-        const int nxt = i + stride;
-        float4 pn = p, mn = m, gn = gr;
-        if (nxt < i1) { pn = p4[nxt]; mn = m4[nxt]; gn = g4[nxt]; }
-        float gg[4] = {gr.x, gr.y, gr.z, gr.w};
-        float pp[4] = {p.x, p.y, p.z, p.w};
-        float mm[4] = {m.x, m.y, m.z, m.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float d = fmaf(wd, pp[e], gg[e] * coef);
-            mm[e] = fmaf(mu, mm[e], d);
-            d = fmaf(mu, mm[e], d);
-            pp[e] = fmaf(-lr, d, pp[e]);
-        }
-        p4[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        m4[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        if (g.o_p16 >= 0) {
-            const unsigned h0 = pack_bf16(pp[0], pp[1]), h1 = pack_bf16(pp[2], pp[3]);
-            reinterpret_cast<uint2 *>(ws + g.o_p16)[i] = make_uint2(h0, h1);
-            if (g.pair_delta) reinterpret_cast<uint2 *>(ws + g.o_p16 + g.pair_delta)[i] = make_uint2(pack_bf16_lo(pp[0], pp[1], h0), pack_bf16_lo(pp[2], pp[3], h1));
-        }
-        i = nxt; p = pn; m = mn; gr = gn;
-    }
-}
+// The same update with the step's scalars passed by value: lets the host split the update so that the first launch of the NEXT step
+// (which only reads the shared frame FC) runs beside the rest of this one on a second stream, and keeps it independent of a newer
+// ta3n_set_hyper upload.
 __global__ __launch_bounds__(256) void sgd_range_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
                                                         float *__restrict__ mom, float *__restrict__ ws, int i0, int i1, int norm_off,
                                                         int norm_n, float lr, float mu, float wd, float clip, Hyper next, int has_next) {
     __shared__ float red[8];
-    sgd_range_body(g, params, grads, mom, ws, i0, i1, norm_off, norm_n, lr, mu, wd, clip, next, has_next, (int)gridDim.x, red);
+    update_range(g, params, grads, ws, i0, i1, norm_off, norm_n, clip, SgdRule{{mom}, lr, mu, wd}, next, has_next, (int)gridDim.x, red);
 }
 
-// clip_grad_norm_ + torch.optim.Adam (amsgrad False, maximize False, L2 weight decay added to the gradient: reference main.py:84-86, 578-583)
-// over floats [4 i0, 4 i1) of the flat prefix, on the contract of sgd_range_body: scalars by value, the norm partials added up by every
-// workgroup in the fixed order of strided_partial_sum, the next element's loads in flight while the current one is updated, the range that
-// starts at 0 records norm and coefficient, the next step's scalars ride along (bit 0 of has_next), bf16 twins written in the same pass.
-//     d = g coef + wd p;  m = b1 m + (1 - b1) d;  v = b2 v + (1 - b2) d d;  p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
-// step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t) and the two complements 1 - b1, 1 - b2 come from the host, formed in double the way
-// torch forms them (a complement taken from the fp32 beta would be off by 1e-5 relative for b2 = 0.999).  Exact sqrtf and divide.
-struct AdamScalars {
-    float b1, omb1, b2, omb2, step_size, bc2_sqrt, eps, wd, clip;
-};
-__device__ __forceinline__ void adam_range_body(const Geom &g, float *__restrict__ params, const float *__restrict__ grads,
-                                                float *__restrict__ exp_avg, float *__restrict__ exp_avg_sq, float *__restrict__ ws,
-                                                int i0, int i1, int norm_off, int norm_n, const AdamScalars &a, const Hyper &next,
-                                                int has_next, int n_blocks, float *red) {
-    float4 *__restrict__ p4 = reinterpret_cast<float4 *>(params);
-    float4 *__restrict__ m4 = reinterpret_cast<float4 *>(exp_avg);
-    float4 *__restrict__ v4 = reinterpret_cast<float4 *>(exp_avg_sq);
-    const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
-    const int stride = n_blocks * blockDim.x;
-    int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, v = p, gr = p;
-    if (i < i1) { p = p4[i]; m = m4[i]; v = v4[i]; gr = g4[i]; }      // in flight while the norm partials are added up
-    const float acc = strided_partial_sum(ws + norm_off, norm_n, (int)threadIdx.x, (int)blockDim.x);
-    const float total = sqrtf(block_sum(acc, red));
-    float coef = 1.f;
-    if (a.clip > 0.f) coef = fminf(a.clip / (total + 1e-6f), 1.f);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && i0 == 0) {
-        ws[g.o_grad_norm] = total;
-        ws[g.o_grad_norm + 1] = coef;
-    }
-    if ((has_next & 1) && blockIdx.x == 0 && threadIdx.x < (int)(sizeof(Hyper) / 4))
-        reinterpret_cast<uint32_t *>(ws + g.o_hyper)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&next)[threadIdx.x];
-    while (i < i1) {
-        const int nxt = i + stride;
-        float4 pn = p, mn = m, vn = v, gn = gr;
-        if (nxt < i1) { pn = p4[nxt]; mn = m4[nxt]; vn = v4[nxt]; gn = g4[nxt]; }
-        float gg[4] = {gr.x, gr.y, gr.z, gr.w};
-        float pp[4] = {p.x, p.y, p.z, p.w};
-        float mm[4] = {m.x, m.y, m.z, m.w};
-        float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = fmaf(a.wd, pp[e], gg[e] * coef);
-            mm[e] = fmaf(a.b1, mm[e], a.omb1 * d);
-            vv[e] = fmaf(a.b2, vv[e], (a.omb2 * d) * d);
-            const float denom = sqrtf(vv[e]) / a.bc2_sqrt + a.eps;
-            pp[e] = fmaf(-a.step_size, mm[e] / denom, pp[e]);
-        }
-        p4[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        m4[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        v4[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        if (g.o_p16 >= 0) {
-            const unsigned h0 = pack_bf16(pp[0], pp[1]), h1 = pack_bf16(pp[2], pp[3]);
-            reinterpret_cast<uint2 *>(ws + g.o_p16)[i] = make_uint2(h0, h1);
-            if (g.pair_delta) reinterpret_cast<uint2 *>(ws + g.o_p16 + g.pair_delta)[i] = make_uint2(pack_bf16_lo(pp[0], pp[1], h0), pack_bf16_lo(pp[2], pp[3], h1));
-        }
-        i = nxt; p = pn; m = mn; v = vn; gr = gn;
-    }
-}
+// clip_grad_norm_ + torch.optim.Adam (adam_update) on the same contract; only the range that starts at 0 records norm and coefficient.
 __global__ __launch_bounds__(256) void adam_range_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
                                                          float *__restrict__ exp_avg, float *__restrict__ exp_avg_sq, float *__restrict__ ws,
                                                          int i0, int i1, int norm_off, int norm_n, AdamScalars a, Hyper next, int has_next) {
     __shared__ float red[8];
-    adam_range_body(g, params, grads, exp_avg, exp_avg_sq, ws, i0, i1, norm_off, norm_n, a, next, has_next, (int)gridDim.x, red);
+    update_range(g, params, grads, ws, i0, i1, norm_off, norm_n, a.clip, AdamRule{{exp_avg, exp_avg_sq}, a}, next, has_next & 1,
+                 (int)gridDim.x, red);
 }
 
 // The launch that opens a pipelined step WITH its batch assembly (ta3n_train_steps with feeds): workgroups [0, sgd_blocks) are
@@ -765,7 +710,7 @@ __global__ __launch_bounds__(256) void sgd_open_feed_kernel(Geom g, float *__res
                                                             int sgd_blocks, FeedPair fp) {
     __shared__ float red[8];
     if ((int)blockIdx.x < sgd_blocks) {
-        sgd_range_body(g, params, grads, mom, ws, i0, i1, norm_off, norm_n, lr, mu, wd, clip, next, has_next, sgd_blocks, red);
+        update_range(g, params, grads, ws, i0, i1, norm_off, norm_n, clip, SgdRule{{mom}, lr, mu, wd}, next, has_next, sgd_blocks, red);
         return;
     }
     int row = (int)blockIdx.x - sgd_blocks;
@@ -790,17 +735,7 @@ __global__ __launch_bounds__(256) void sgd_fixup_kernel(Geom g, float *__restric
                                                         float *__restrict__ mom, float *__restrict__ ws, float *__restrict__ p16, int n4,
                                                         float lr, float mu, float clip, Hyper next, int has_next) {
     __shared__ float red[8];
-    float acc = 0.f;
-    acc = strided_partial_sum(ws + g.o_sumsq, g.n_sumsq, (int)threadIdx.x, (int)blockDim.x);
-    const float total = sqrtf(block_sum(acc, red));
-    float coef = 1.f;
-    if (clip > 0.f) coef = fminf(clip / (total + 1e-6f), 1.f);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ws[g.o_grad_norm] = total;
-        ws[g.o_grad_norm + 1] = coef;
-    }
-    if (has_next && blockIdx.x == 0 && threadIdx.x < (int)(sizeof(Hyper) / 4))
-        reinterpret_cast<uint32_t *>(ws + g.o_hyper)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&next)[threadIdx.x];
+    const float coef = update_prologue(g, ws, g.o_sumsq, g.n_sumsq, clip, true, next, has_next != 0, red);
     if (coef >= 1.f) return;                       // (uniform over the grid) the speculation held: nothing to correct
     const float c = 1.f - coef, a = lr * (1.f + mu) * c;
     float4 *__restrict__ p4 = reinterpret_cast<float4 *>(params);
@@ -1315,14 +1250,8 @@ __global__ __launch_bounds__(256) void shard_sumsq_kernel(const float *__restric
     float acc = 0.f;
     const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
     const int stride = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int i = a0 + t; i < a1; i += stride) {
-        const float4 v = g4[i];
-        acc = fmaf(v.x, v.x, acc); acc = fmaf(v.y, v.y, acc); acc = fmaf(v.z, v.z, acc); acc = fmaf(v.w, v.w, acc);
-    }
-    for (int i = b0 + t; i < b1; i += stride) {
-        const float4 v = g4[i];
-        acc = fmaf(v.x, v.x, acc); acc = fmaf(v.y, v.y, acc); acc = fmaf(v.z, v.z, acc); acc = fmaf(v.w, v.w, acc);
-    }
+    for (int i = a0 + t; i < a1; i += stride) acc = sumsq4(g4[i], acc);
+    for (int i = b0 + t; i < b1; i += stride) acc = sumsq4(g4[i], acc);
     const float s = block_sum(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
@@ -1342,13 +1271,20 @@ int launch_shard_sumsq(const Geom &g, const float *grads, float *ws, int64_t a0,
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// Pieces every update launcher shares: the grid of a range of float4 elements [i0, i1), and the next step's scalars as a kernel
+// argument (zeroed when there are none: the argument is copied whole at launch time)
+static int update_blocks(int i0, int i1) { return std::min((i1 - i0 + 255) / 256, 2048); }
+static Hyper next_or_zero(const Hyper *next) {
+    Hyper nh;
+    std::memset(&nh, 0, sizeof(nh));
+    if (next) nh = *next;
+    return nh;
+}
+
 int launch_sgd(const Geom &g, float *params, const float *grads, float *momentum, float *ws, hipStream_t stream, bool fused_norm) {
     const int n4 = g.live_floats / 4;
-    int blocks = (n4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, stream, g, params, grads, momentum, ws, n4,
-                       fused_norm ? g.o_sumsq : g.o_norm_part, fused_norm ? g.n_sumsq : g.n_norm_blocks);
+    const NormSource ns = norm_source(g, fused_norm);
+    hipLaunchKernelGGL(sgd_kernel, dim3(std::max(update_blocks(0, n4), 1)), dim3(256), 0, stream, g, params, grads, momentum, ws, n4, ns.off, ns.n);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1380,14 +1316,9 @@ int launch_sgd_range(const Geom &g, float *params, const float *grads, float *mo
                      bool fused_norm, float lr, float mu, float wd, float clip, const Hyper *next, hipStream_t stream, bool write_norm) {
     const int i0 = (int)(begin / 4), i1 = (int)(end / 4);
     if (i1 <= i0) return 0;
-    int blocks = (i1 - i0 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    Hyper nh;
-    std::memset(&nh, 0, sizeof(nh));
-    if (next) nh = *next;
-    hipLaunchKernelGGL(sgd_range_kernel, dim3(blocks), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1,
-                       fused_norm ? g.o_sumsq : g.o_norm_part, fused_norm ? g.n_sumsq : g.n_norm_blocks, lr, mu, wd, clip, nh,
-                       (next ? 1 : 0) | (write_norm ? 2 : 0));
+    const NormSource ns = norm_source(g, fused_norm);
+    hipLaunchKernelGGL(sgd_range_kernel, dim3(update_blocks(i0, i1)), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1, ns.off, ns.n,
+                       lr, mu, wd, clip, next_or_zero(next), (next ? 1 : 0) | (write_norm ? 2 : 0));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1396,27 +1327,19 @@ int launch_adam_range(const Geom &g, float *params, const float *grads, float *e
                       float clip, const Hyper *next, hipStream_t stream) {
     const int i0 = (int)(begin / 4), i1 = (int)(end / 4);
     if (i1 <= i0) return 0;
-    int blocks = (i1 - i0 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    Hyper nh;
-    std::memset(&nh, 0, sizeof(nh));
-    if (next) nh = *next;
+    const NormSource ns = norm_source(g, fused_norm);
     // torch hands the kernels beta and 1 - beta as fp32 roundings of the double values (lerp_ weight, mul_ / addcmul_ value)
     const AdamScalars a{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), step_size, bc2_sqrt, eps, wd, clip};
-    hipLaunchKernelGGL(adam_range_kernel, dim3(blocks), dim3(256), 0, stream, g, params, grads, exp_avg, exp_avg_sq, ws, i0, i1,
-                       fused_norm ? g.o_sumsq : g.o_norm_part, fused_norm ? g.n_sumsq : g.n_norm_blocks, a, nh, next ? 1 : 0);
+    hipLaunchKernelGGL(adam_range_kernel, dim3(update_blocks(i0, i1)), dim3(256), 0, stream, g, params, grads, exp_avg, exp_avg_sq, ws, i0, i1,
+                       ns.off, ns.n, a, next_or_zero(next), next ? 1 : 0);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int launch_sgd_open_feed(const Geom &g, float *params, const float *grads, float *momentum, float *ws, int64_t begin, int64_t end,
                          bool fused_norm, float lr, float mu, float wd, float clip, const Hyper *next, const FeedJob feeds[2], hipStream_t stream) {
     const int i0 = (int)(begin / 4), i1 = (int)(end / 4);
-    int blocks = (i1 - i0 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;      // (block 0 carries the step's scalars even when the range is empty)
-    Hyper nh;
-    std::memset(&nh, 0, sizeof(nh));
-    if (next) nh = *next;
+    const int blocks = std::max(update_blocks(i0, i1), 1);      // (block 0 carries the step's scalars even when the range is empty)
+    const NormSource ns = norm_source(g, fused_norm);
     FeedPair fp;
     std::memset(&fp, 0, sizeof(fp));
     fp.T = g.T; fp.D = g.D; fp.pair_delta = g.pair_delta;
@@ -1427,19 +1350,15 @@ int launch_sgd_open_feed(const Geom &g, float *params, const float *grads, float
         f.out = j.out; f.labels_out = j.labels_out; f.twin = j.twin; f.rows = j.n_videos > 0 ? j.n_videos * g.T : 0; f.bf16 = j.bf16;
     }
     const int rows = fp.half[0].rows + fp.half[1].rows;
-    hipLaunchKernelGGL(sgd_open_feed_kernel, dim3(blocks + rows), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1,
-                       fused_norm ? g.o_sumsq : g.o_norm_part, fused_norm ? g.n_sumsq : g.n_norm_blocks, lr, mu, wd, clip, nh, next ? 1 : 0,
-                       blocks, fp);
+    hipLaunchKernelGGL(sgd_open_feed_kernel, dim3(blocks + rows), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1, ns.off, ns.n,
+                       lr, mu, wd, clip, next_or_zero(next), next ? 1 : 0, blocks, fp);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int launch_sgd_fixup(const Geom &g, float *params, const float *grads, float *momentum, float *ws, float *p16, float lr, float mu,
                      float clip, const Hyper *next, hipStream_t stream) {
-    Hyper nx;
-    std::memset(&nx, 0, sizeof(nx));
-    if (next) nx = *next;
     hipLaunchKernelGGL(sgd_fixup_kernel, dim3(128), dim3(256), 0, stream, g, params, grads, momentum, ws, p16, g.live_floats / 4, lr, mu, clip,
-                       nx, next ? 1 : 0);
+                       next_or_zero(next), next ? 1 : 0);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -327,27 +327,38 @@ def test_other_baseline_config_shapes_match_oracle(shape):
         assert torch.allclose(newp[k].cpu(), v, rtol=RTOL, atol=ATOL), k
 
 
-def test_deferred_overlapped_update_is_the_same_arithmetic():
+@pytest.mark.parametrize("clip", [20.0, 1e6], ids=["clipped", "unclipped"])
+def test_deferred_overlapped_update_is_the_same_arithmetic(clip):
     """train_step_deferred (update of step s enqueued at the start of step s+1, all but the shared frame FC on a side
-    stream beside the next step's first launch) must give bit-identical parameters to the plain sequence."""
+    stream beside the next step's first launch) must give bit-identical parameters to the plain sequence.  Both branches of
+    the clip coefficient: the oracle's gradient norms of these four steps are 60.2, 49.9, 68.4 and 64.0, so the fixture's
+    clip of 20 clips at every step and 1e6 never does.  The bf16 run adds the parameter twins the update writes."""
     g = Golden("tiny_T5")
     c = case_config(g)
-    results = []
-    for mode in ("plain", "deferred", "pipelined"):
-        eng = _engine(c)
-        _load(eng, c)
-        for i in range(4):
-            xs, xt, ys, yt = synth_batch(c["C"], c["T"], c["D"], c["Bs"], c["Bt"], seed=5 + i)
-            eng.set_batch(xs.cuda(), xt.cuda(), ys.cuda())
-            if mode == "plain":
-                eng.train_step([0.75, 0.75, 0.5], 0.003, 1e-3 * (i + 1), seed=i)
-            elif mode == "deferred":
-                eng.train_step_deferred([0.75, 0.75, 0.5], 0.003, 1e-3 * (i + 1), seed=i)
-            else:       # update of step s = first launch of step s+1, which also delivers that step's scalars (ta3n_sgd_step_next)
-                eng.train_step_pipelined([0.75, 0.75, 0.5], 0.003, 1e-3 * (i + 1), seed=i)
-        eng.flush()
-        torch.cuda.synchronize()
-        results.append((eng.P.clone(), eng.M.clone(), eng.region("losses")[:6].clone()))
-    for other in results[1:]:
-        assert torch.equal(results[0][0], other[0]) and torch.equal(results[0][1], other[1])
-        assert torch.equal(results[0][2], other[2])
+    assert c["clip"] == 20.0
+    c = dict(c, clip=clip)
+    for kw, twins in (({}, False), (dict(bf16=True, bf16_store=True), True)):
+        results = []
+        for mode in ("plain", "deferred", "pipelined"):
+            eng = _engine(c, **kw)
+            _load(eng, c)
+            for i in range(4):
+                xs, xt, ys, yt = synth_batch(c["C"], c["T"], c["D"], c["Bs"], c["Bt"], seed=5 + i)
+                eng.set_batch(xs.cuda(), xt.cuda(), ys.cuda())
+                if mode == "plain":
+                    eng.train_step([0.75, 0.75, 0.5], 0.003, 1e-3 * (i + 1), seed=i)
+                elif mode == "deferred":
+                    eng.train_step_deferred([0.75, 0.75, 0.5], 0.003, 1e-3 * (i + 1), seed=i)
+                else:       # update of step s = first launch of step s+1, which also delivers that step's scalars (ta3n_sgd_step_next)
+                    eng.train_step_pipelined([0.75, 0.75, 0.5], 0.003, 1e-3 * (i + 1), seed=i)
+            eng.flush()
+            torch.cuda.synchronize()
+            coef = float(eng.region("grad_norm")[1])
+            assert coef < 1.0 if clip == 20.0 else coef == 1.0, (mode, coef)
+            results.append((eng.P.clone(), eng.M.clone(), eng.region("losses")[:6].clone(),
+                            eng.region("p16").clone() if twins else None))
+        for other in results[1:]:
+            assert torch.equal(results[0][0], other[0]) and torch.equal(results[0][1], other[1])
+            assert torch.equal(results[0][2], other[2])
+            if twins:       # compared as bits: the region holds bf16 pairs, not floats
+                assert torch.equal(results[0][3].view(torch.int32), other[3].view(torch.int32))
