@@ -628,6 +628,14 @@ int ta3n_debug_waits(const ta3n_plan *plan, const void **waits, int64_t *n_waits
  * the stream: a check for tests and for the end of a run, not for the step loop. */
 int ta3n_chain_status(ta3n_plan *plan, const float *ws, void *stream);
 
+/* The heads kernel of the fused step has a four-wave and an eight-wave variant of its video workgroups (the latter for one video
+ * per workgroup, at most 4 relations and fc_dim <= 512: the headline shape).  `waves` = 0 picks automatically (eight where it
+ * exists), 4 / 8 ask for one of them; a shape that has only the four-wave kernel runs it whatever is asked.  Process-wide; takes
+ * effect at the next launch; changes the kernel that is launched and nothing in any plan.  For A/B measurements and tests. */
+int ta3n_set_heads_waves(int waves);
+/* Waves per workgroup of the heads launch this plan's fused step would run now (4 or 8); 0 if it has no heads launch. */
+int ta3n_get_heads_waves(const ta3n_plan *plan);
+
 const char *ta3n_last_error(void);
 const char *ta3n_version(void);
 

@@ -46,6 +46,7 @@ SYMBOLS = [
     "ta3n_comm_attach_peer", "ta3n_has_fused_update", "ta3n_train_steps_fused_update",
     "ta3n_gaussian_kernel_scratch_floats", "ta3n_gaussian_kernel", "ta3n_mmd_rowdiff", "ta3n_discrepancy_scratch_floats", "ta3n_discrepancy",
     "ta3n_mcd_source_loss", "ta3n_mcd_second_loss",
+    "ta3n_set_heads_waves", "ta3n_get_heads_waves",
     "ta3n_shard_ranges", "ta3n_shard_sumsq", "ta3n_sgd_shard", "ta3n_shard_reduce_scatter", "ta3n_sharded_update", "ta3n_train_steps_sharded",
 ]
 
@@ -205,6 +206,9 @@ def lib() -> C.CDLL:
     L.ta3n_discrepancy_scratch_floats.restype = i64
     L.ta3n_discrepancy.argtypes = [vp, i64, C.c_int, i64, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_float, vp, i64, vp, vp]
+    if hasattr(L, "ta3n_set_heads_waves"):      # (absent from an older build directory loaded on purpose: TA3N_ALLOW_STALE_LIB=1, A/B runs)
+        L.ta3n_set_heads_waves.argtypes = [C.c_int]
+        L.ta3n_get_heads_waves.argtypes = [vp]
     L.ta3n_last_error.restype = C.c_char_p
     L.ta3n_version.restype = C.c_char_p
     _LIB = L

@@ -154,6 +154,18 @@ const char *ta3n_version(void) {
                             : "ta3n_hip 0.3 (gfx950, fp32 MFMA 32x32x2 | bf16 MFMA 32x32x16 with fp32 accumulation)";
 }
 
+int ta3n_set_heads_waves(int waves) {
+    if (set_heads_waves(waves) != 0) return fail(TA3N_ERR_INVALID, "heads waves: 0 (automatic), 4 or 8");
+    return TA3N_OK;
+}
+
+int ta3n_get_heads_waves(const ta3n_plan *plan) {
+    if (!plan) return fail(TA3N_ERR_INVALID, "null argument");
+    for (const Phase &ph : plan->phases)
+        if (ph.kind == PH_HEADS) return heads_waves(plan->geom);
+    return 0;
+}
+
 int ta3n_plan_create(const ta3n_config *cfg, ta3n_plan **out) {
     if (!cfg || !out) return fail(TA3N_ERR_INVALID, "null argument");
     ta3n_plan *p = new (std::nothrow) ta3n_plan();

@@ -34,6 +34,7 @@
 // results are bitwise reproducible and no atomics are used.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <mutex>
 
 #include "../../include/ta3n_hip.h"
@@ -64,9 +65,12 @@ constexpr int TROW = 260;          // padded row of the backward tile [64 n][256
 // (tools/heads_timing.py, round 4: 7-11 k of it in the relation stages A and G, ~13 k in B-F whatever the shape).  With VPW videos per
 // workgroup the per-video stages run one video per wave (or per wave pair) side by side and the 256x256 layer multiplies VPW vectors
 // from the one register copy of its weights.)
-template <int VPW>
+// NW: waves of the workgroup.  4 everywhere but in the one-relation-per-wave kernel of small relation counts, whose video workgroups
+// have 8 (two per SIMD, 32 float4 of Wdv per thread: section "eight waves" at video_wg).
+template <int VPW, int NW = 4>
 struct Lds {
     static_assert(VPW == 1 || VPW == 2, "1 or 2 videos per workgroup");
+    static_assert(NW == 4 || (NW == 8 && VPW == 1), "eight waves: one video per workgroup only");
     static constexpr int W = 0;                                 // weight tile (17408 floats)
     static constexpr int VD = W + NBH * WROW;                   // [VPW][256] dropped-out video feature
     static constexpr int HV = VD + VPW * NBH;                   // [VPW][256] video-discriminator hidden
@@ -76,16 +80,20 @@ struct Lds {
     static constexpr int PR = GY + VPW * 64;                    // [VPW][64][2] relation logits
     static constexpr int GPV = PR + VPW * 128;                  // [VPW][2]
     static constexpr int Y = GPV + 8;                           // [VPW][64] class logits
-    static constexpr int FPART = Y + VPW * 64;                  // [16][256] partial sums of the backward mini-GEMM (one video at a time)
-    static constexpr int VPART = FPART + 16 * NBH;              // [4 waves][256] per-wave partial sums of V
-    static constexpr int LOSS = VPART + 4 * NBH;                // [4 waves][8] loss partials
-    static constexpr int TOTAL = LOSS + 32;
-    static constexpr int WPV = 4 / VPW;                         // waves per video: they split the relations of the per-video stages
+    static constexpr int FROWS = 16;                            // partial sums per input channel in stage F (one per srow)
+    static constexpr int FPART = Y + VPW * 64;                  // [FROWS][256] partial sums of the backward mini-GEMM (one video at a time)
+    static constexpr int VPART = FPART + FROWS * NBH;           // [NW waves][256] per-wave partial sums of V
+    static constexpr int LOSS = VPART + NW * NBH;               // [NW waves][8] loss partials
+    static constexpr int TOTAL = LOSS + 8 * NW;
+    static constexpr int WPV = NW / VPW;                        // waves per video: they split the relations of the per-video stages
 };
+static_assert(Lds<1, 8>::TOTAL * sizeof(float) <= 160 * 1024 && Lds<2, 4>::TOTAL * sizeof(float) <= 160 * 1024, "LDS of a compute unit");
+static_assert(Lds<1, 4>::LOSS <= Lds<2, 4>::LOSS && Lds<1, 4>::LOSS + 32 <= Lds<1, 8>::TOTAL, "frame workgroups keep their loss slots at Lds<1>::LOSS in every variant");
 static_assert(64 * TROW <= NBH * WROW, "backward tile / classifier staging must fit in the weight tile");
 constexpr int S_LOSS_MIN = Lds<1>::LOSS;                        // (the frame workgroups' staging must stay below the loss slots of every variant)
 
-// -DTA3N_HEADS_TIMING: the 101st video workgroup stamps s_memtime at every stage boundary into ws["g_attn"] (debug builds only)
+// -DTA3N_HEADS_TIMING: the 101st video workgroup stamps s_memtime at every stage boundary into ws["g_attn"] (debug builds only);
+// stamp 9 is taken at kernel entry, stamp 0 once the top-of-kernel loads are issued (tools/heads_timing.py: "top loads")
 #ifdef TA3N_HEADS_TIMING
 #define STAMP(i) do { if ((int)blockIdx.x == g.n_frm_wg + 100 && threadIdx.x == 0) { reinterpret_cast<unsigned long long *>(ptrs.ws + g.o_gattn)[i] = __builtin_amdgcn_s_memtime(); } } while (0)
 #else
@@ -114,11 +122,16 @@ __device__ __forceinline__ StepScalars step_scalars(const Hyper *__restrict__ hy
 }
 
 // this workgroup's loss partials -> ws["loss_part"][wg][8] = {total, cls, rel, vid, frm, ent, 0, 0}
+// (NW: how many waves left a slot; every wave of the workgroup takes part in the barriers)
+template <int NW>
 __device__ __forceinline__ void write_loss_part(float *smem, float *ws, int o_loss_part, int wg, float gamma, int S_LOSS) {
     const int tid = threadIdx.x;
     __syncthreads();
     float v = 0.f;
-    if (tid < 8) v = (smem[S_LOSS + tid] + smem[S_LOSS + 8 + tid]) + (smem[S_LOSS + 16 + tid] + smem[S_LOSS + 24 + tid]);
+    if (tid < 8) {
+        v = (smem[S_LOSS + tid] + smem[S_LOSS + 8 + tid]) + (smem[S_LOSS + 16 + tid] + smem[S_LOSS + 24 + tid]);
+        if (NW == 8) v += (smem[S_LOSS + 32 + tid] + smem[S_LOSS + 40 + tid]) + (smem[S_LOSS + 48 + tid] + smem[S_LOSS + 56 + tid]);
+    }
     __syncthreads();
     if (tid < 8) smem[S_LOSS + tid] = v;
     __syncthreads();
@@ -132,9 +145,31 @@ __device__ __forceinline__ void write_loss_part(float *smem, float *ws, int o_lo
 // the current one is reduced, and stage G's first relation in front of stage F.  With one relation per wave (the headline shape: 5
 // segments, 4 relations, 4 waves) the bookkeeping of that pipeline cost 0.5 us per launch (profiles/r05_heads_tiles_ab.txt), so the
 // single-relation kernel keeps round 4's sequence: stage A's only relation requested at the top, stage G's inside stage G.
-template <int VPW, bool PIPE>
+//
+// Eight waves (NW == 8; VPW == 1 && !PIPE, n_rel <= 4: the headline shape).  The front of the kernel is a 272 KB burst of register loads
+// (Wdv, the classifier weights) that stage C cannot start without.  In the four-wave kernels it is not even REQUESTED before stage A's
+// operands have arrived (ISA: the conditional Zr loads sit in branches of their own, each behind s_waitcnt vmcnt(0), and the relation dot
+// products are hoisted above the weight loads - three to four dependent round trips, 12-13 k of the launch's 27 k ticks at the
+// headline shape, profiles/heads_waves_stage_timeline.txt), and a wave could not have all of its ~125 loads outstanding anyway (63 at most).
+// With 8 waves
+//   * thread (srow, c16) holds 8 of the 16 rows srow + 16 i of Wdv (threads 256.. those of i >= 8) as 32 float4 and 8 float4 of the classifier weights, so
+//     twice the waves pull the burst and a wave's share fits its counter; 205 of 256 registers per lane, two waves per SIMD, which
+//     also gives the dependent VALU chains of stages C and F a second wave to hide behind;
+//   * every load of the front is unconditional (see load_rel) and the front is straight-line code: stage A's relation is requested
+//     first, then the classifier weights and HALF of Wdv (50 loads); the small operands and the other half are issued behind stage
+//     A's arithmetic (scheduling barriers keep the compiler from moving either across), so stage A waits for its own 26 loads only;
+//   * the k partition of stage C is the 4-wave one (16 lanes x 4 k x 4 chunks, the same DPP sum): Hv and everything in front of it
+//     is bit-identical.  Stage F runs the four-wave kernel's chain over an srow's 16 rows in two halves, handed over through LDS: bit-identical too;
+//   * relations are dealt over 8 waves; a wave without one leaves +0 partials, added in a fixed order (x + 0 = x);
+//   * the thread <-> channel parts (V, class logits, gHv, gVt) run on threads 0..255 with the 4-wave arithmetic.
+template <int VPW, bool PIPE, int NW>
 __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *smem) {
-    using L = Lds<VPW>;
+    static_assert(NW == 4 || (VPW == 1 && !PIPE), "eight waves: the one-relation-per-wave kernel only");
+    using L = Lds<VPW, NW>;
+    constexpr int NTH = 64 * NW;                   // threads
+    constexpr int NI = 64 / NW;                    // rows of Wdv per thread and k chunk: 16 / 8
+    constexpr int NCW = 16 * 256 / NTH;            // float4 of the classifier weights per thread: 16 / 8
+    STAMP(9);
     constexpr int S_W = L::W, S_VD = L::VD, S_HV = L::HV, S_GHV = L::GHV, S_GVT = L::GVT, S_GY = L::GY, S_PR = L::PR, S_GPV = L::GPV, S_Y = L::Y,
                   S_FPART = L::FPART, S_VPART = L::VPART, S_LOSS = L::LOSS, WPV = L::WPV;
     float *__restrict__ ws = ptrs.ws;
@@ -144,6 +179,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     const int *__restrict__ tf = reinterpret_cast<const int *>(ptrs.ws + g.o_tuple_first);
     const int *__restrict__ labels = reinterpret_cast<const int *>(ptrs.ws + g.o_labels);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const bool ch = NW == 4 || tid < NBH;          // thread t <-> channel t parts: the first 256 threads
     const int NR = g.n_rel, NT = g.n_tuples, C = g.C;
     const int b0 = ((int)blockIdx.x - g.n_frm_wg) * VPW;
     const int nv = min(VPW, g.B - b0);
@@ -171,20 +207,31 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     // read with v_readlane afterwards: a load of tuple_first[j] inside load_rel made the compiler wait for EVERYTHING outstanding
     // (s_waitcnt vmcnt(0): the counter is in order) before it could form the next relation's addresses - a full round trip per relation
     // at the top of each loop iteration (found in the ISA in round 5).
-    const int tfv = lane <= NR ? tf[lane] : 0;
+    // (eight waves, one relation per wave: the wave's two range ends by scalar loads instead - no vector round trip in front of the
+    // Zr addresses - and every load below unconditional: a tuple past the range re-reads the relation's first tuple and is replaced by +0
+    // afterwards.  With the loads inside `if (tt < nt)` the compiler folds stage A's first additions into the branches, each behind
+    // a full s_waitcnt vmcnt(0): three to four dependent round trips BEFORE the weight burst was even issued, in the ISA of every
+    // four-wave instantiation.)
+    const int tfv = (NW == 4 && lane <= NR) ? tf[lane] : 0;
     struct RelIn { float hr[4], w0[4], w1[4], zr[3][4], b0, b1; int nt; };
     auto load_rel = [&](int j, RelIn &o) {
         const float *__restrict__ W2f = P + g.p_W2_0 + (size_t)j * g.p_W2_stride;
         const float *__restrict__ hrf = wsr + g.o_Hr + ((size_t)b * NR + j) * NBH;
         const int ju = __builtin_amdgcn_readfirstlane(j);
-        const int t_lo = __builtin_amdgcn_readlane(tfv, ju);
-        const int t_hi = __builtin_amdgcn_readlane(tfv, ju + 1);
+        const int t_lo = NW == 8 ? tf[ju] : __builtin_amdgcn_readlane(tfv, ju);
+        const int t_hi = NW == 8 ? tf[ju + 1] : __builtin_amdgcn_readlane(tfv, ju + 1);
         o.nt = t_hi - t_lo;
 #pragma unroll
         for (int q = 0; q < 4; ++q) { o.hr[q] = hrf[q * 64 + lane]; o.w0[q] = W2f[q * 64 + lane]; o.w1[q] = W2f[NBH + q * 64 + lane]; }
 #pragma unroll
         for (int tt = 0; tt < 3; ++tt) {         // a relation sums at most 3 tuples (TRNmodule.py:32 subsample_num); a tuple past the range reads as +0
             const bool on = tt < o.nt;
+            if (NW == 8) {
+                const float *__restrict__ zrf = wsr + g.o_Zr + ((size_t)b * NT + t_lo + (on ? tt : 0)) * NBH;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { const float z = zrf[q * 64 + lane]; o.zr[tt][q] = on ? z : 0.f; }
+                continue;
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) o.zr[tt][q] = on ? wsr[g.o_Zr + ((size_t)b * NT + t_lo + tt) * NBH + q * 64 + lane] : 0.f;
         }
@@ -195,37 +242,58 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     rel_cur.nt = 0; rel_cur.b0 = rel_cur.b1 = 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { rel_cur.hr[q] = rel_cur.w0[q] = rel_cur.w1[q] = 0.f; rel_cur.zr[0][q] = rel_cur.zr[1][q] = rel_cur.zr[2][q] = 0.f; }
-    if (have && sub < NR) load_rel(sub, rel_cur);
+    // (eight waves: unconditional as well - a wave without a relation requests the last one's operands and never uses them; inside a
+    // branch the compiler moves stage A's dot products in with the loads, in front of the weight burst)
+    if (NW == 8) load_rel(min(sub, NR - 1), rel_cur);
+    else if (have && sub < NR) load_rel(sub, rel_cur);
     // ---- address-independent loads ----
-    f32x4 cw[16];                                  // classifier weights [C][256]: float4 i*256+tid of the flat array
+    f32x4 cw[NCW];                                 // classifier weights [C][256]: float4 i*NTH+tid of the flat array
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
-        cw[i] = (i * 256 + tid < C * 64) ? *reinterpret_cast<const f32x4 *>(Wcv + (size_t)(i * 256 + tid) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < NCW; ++i) {
+        const int f = i * NTH + tid;
+        if (NW == 8) {                             // (unconditional: past the last class the last float4 is read and replaced by zeros)
+            const f32x4 w4 = *reinterpret_cast<const f32x4 *>(Wcv + (size_t)min(f, C * 64 - 1) * 4);
+            cw[i] = f < C * 64 ? w4 : f32x4{0.f, 0.f, 0.f, 0.f};
+        } else
+            cw[i] = (f < C * 64) ? *reinterpret_cast<const f32x4 *>(Wcv + (size_t)f * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     // The whole 256 x 256 video-discriminator weight matrix lives in this workgroup's registers (64 float4 per
     // thread; one wave per SIMD leaves 512 registers per lane): thread (srow, sk4) holds W[srow + 16 i][64 kc + sk4 ..]
-    // as wreg[16 kc + i].  Both the forward tiles (all n x 64 k) and the backward tiles (64 n x all k) are staged to
+    // as wreg[16 kc + i] (eight waves: 32 float4, W[row0 + 16 i][..] as wreg[8 kc + i]).  Both the forward tiles (all n x 64 k) and the backward tiles (64 n x all k) are staged to
     // LDS from it, so the matrix crosses the memory system once per workgroup and no stage waits on a load.
-    f32x4 wreg[64];
-    const int srow = tid >> 4, sk4 = (tid & 15) * 4;
+    f32x4 wreg[4 * NI];
+    // (eight waves: threads tid and tid + 256 share srow; the first holds the rows srow + 16 i of i < 8, the second those of i >= 8)
+    const int srow = (tid >> 4) & 15, sk4 = (tid & 15) * 4;
+    const int row0 = srow + (NW == 8 ? 128 * (tid >> 8) : 0);   // this thread's rows: row0 + 16 i
+    auto load_wdv = [&](int kc) {
 #pragma unroll
-    for (int kc = 0; kc < 4; ++kc)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            wreg[kc * 16 + i] = *reinterpret_cast<const f32x4 *>(Wdv + (size_t)(srow + 16 * i) * NBH + kc * 64 + sk4);
+        for (int i = 0; i < NI; ++i)
+            wreg[kc * NI + i] = *reinterpret_cast<const f32x4 *>(Wdv + (size_t)(row0 + 16 * i) * NBH + kc * 64 + sk4);
+    };
+    load_wdv(0); load_wdv(1);
+    if (NW == 4) { load_wdv(2); load_wdv(3); }     // (eight waves: behind stage A's arithmetic)
     const float *__restrict__ Wcdv = P + g.p_Wcdv;
     float wc0[4], wc1[4];                          // output layer of the video discriminator, this lane's channels
+    float wct0, wct1, bcv_c, bdv_n;
+    // small operands of the later stages, requested at the top as well (each used to cost its stage an exposed round trip):
+    // the output layer of the video discriminator, the class bias of this thread's class, the video-discriminator bias of its channel
+    auto load_small_a = [&]() {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { wc0[q] = Wcdv[q * 64 + lane]; wc1[q] = Wcdv[NBH + q * 64 + lane]; }
-    const float wct0 = Wcdv[tid], wct1 = Wcdv[NBH + tid];
+        for (int q = 0; q < 4; ++q) { wc0[q] = Wcdv[q * 64 + lane]; wc1[q] = Wcdv[NBH + q * 64 + lane]; }
+        const int tc = NW == 4 ? tid : tid & (NBH - 1);
+        wct0 = Wcdv[tc]; wct1 = Wcdv[NBH + tc];
+    };
+    auto load_small_b = [&]() {
+        bcv_c = ((tid >> 2) < C) ? P[g.p_bcv + (tid >> 2)] : 0.f;
+        bdv_n = ((tid & 15) < NI) ? P[g.p_bdv + row0 + 16 * (tid & 15)] : 0.f;
+    };
+    if (NW == 4) load_small_a();
     const float bcdv0 = P[g.p_bcdv], bcdv1 = P[g.p_bcdv + 1];
     // (a SCALAR load: as a vector load at the end of the burst above, its consumer `lane == label` - which the compiler hoists up here to
     // keep the result as a lane mask - waited for the whole 256 KB weight burst with s_waitcnt vmcnt(0) before stage A could start)
     const int label = (have && b < g.Bs) ? labels[__builtin_amdgcn_readfirstlane(b)] : -1;
-    // small operands of the later stages, requested now as well (each used to cost its stage an exposed round trip):
-    // the class bias of this thread's class, the video-discriminator bias of its channel, and for the first relation this
-    // wave handles the tuple range and the output-layer bias
-    const float bcv_c = (tid >> 2) < C ? P[g.p_bcv + (tid >> 2)] : 0.f;
-    const float bdv_n = P[g.p_bdv + (tid >> 4) + 16 * (tid & 15)];
+    if (NW == 4) load_small_b();
+    if (NW == 8) __builtin_amdgcn_sched_barrier(0);      // nothing below is issued in front of the loads above
 
     STAMP(0);
     // ---- A: relation logits, attention, R, V, Vd (WPV waves per video, relations dealt round-robin) ----
@@ -264,14 +332,22 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
                     smem[S_PR + (vloc * 64 + j) * 2 + 0] = d0;
                     smem[S_PR + (vloc * 64 + j) * 2 + 1] = d1;
                 }
+                if (NW == 8) break;                // (at most one relation per wave: no loop, whose preheader would wait for the whole burst)
             }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) smem[S_VPART + wv * NBH + q * 64 + lane] = vacc[q];
     }
+    if (NW == 8) {                                 // the second half of the weight burst, behind stage A's arithmetic
+        __builtin_amdgcn_sched_barrier(0);
+        load_small_a(); load_small_b();           // (in front of the weights: stage B ends on the class bias)
+        load_wdv(2); load_wdv(3);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     __syncthreads();
 #pragma unroll
     for (int v = 0; v < VPW; ++v) {                // thread t <-> channel t: add the waves' partial sums in a fixed order
+        if (!ch) break;
         float val = 0.f;
 #pragma unroll
         for (int s_ = 0; s_ < WPV; ++s_) val += smem[S_VPART + (v * WPV + s_) * NBH + tid];
@@ -286,8 +362,8 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     STAMP(1);
     // classifier weights -> LDS [C][TROW]
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int f = i * 256 + tid;               // float4 index: row c = f / 64, k4 = (f % 64) * 4
+    for (int i = 0; i < NCW; ++i) {
+        const int f = i * NTH + tid;               // float4 index: row c = f / 64, k4 = (f % 64) * 4
         if (f < C * 64) *reinterpret_cast<f32x4 *>(&smem[S_W + (f >> 6) * TROW + (f & 63) * 4]) = cw[i];
     }
     __syncthreads();
@@ -299,7 +375,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
 #pragma unroll
         for (int v = 0; v < VPW; ++v) {
             float acc = 0.f;
-            if (c < C) {
+            if (c < C && ch) {
                 const float *wr = &smem[S_W + c * TROW + part * 64];
                 const float *vd = &smem[S_VD + v * NBH + part * 64];
 #pragma unroll
@@ -311,7 +387,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
             }
             acc += dpp_move<0xB1, 0xF>(0.f, acc);      // quad_perm [1,0,3,2]
             acc += dpp_move<0x4E, 0xF>(0.f, acc);      // quad_perm [2,3,0,1]: every lane of the quad holds the class logit
-            if (c < C && part == 0) {
+            if (c < C && part == 0 && ch) {
                 const float yc = acc + bcv_c;
                 smem[S_Y + v * 64 + c] = yc;
                 if (v < nv) ws[g.o_Y + (size_t)(b0 + v) * C + c] = yc;
@@ -325,9 +401,10 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     // ---- C: Hv = relu(Wdv Vd + bdv) straight from the register copy of Wdv, for the workgroup's VPW videos ----
     // Thread (srow, c16) holds W[srow + 16 i][64 kc + 4 c16 .. +3]: 16 partial dot products over its 16 k, then a sum over the
     // 16 lanes of its DPP row (they share srow and cover all 256 k).  Lane c16 keeps output channel srow + 16 c16.
+    // (eight waves: 8 rows row0 + 16 i per thread, lanes c16 < 8 keep channel row0 + 16 c16; the sum per row is the same.)
     {
         const int c16 = tid & 15;
-        const int n = srow + 16 * c16;
+        const int n = row0 + 16 * c16;
 #pragma unroll
         for (int v = 0; v < VPW; ++v) {
             f32x4 xk[4];
@@ -335,11 +412,11 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
             for (int kc = 0; kc < 4; ++kc) xk[kc] = *reinterpret_cast<const f32x4 *>(&smem[S_VD + v * NBH + kc * 64 + sk4]);
             float hv = 0.f;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
+            for (int i = 0; i < NI; ++i) {
                 float p = 0.f;
 #pragma unroll
                 for (int kc = 0; kc < 4; ++kc) {
-                    const f32x4 w4 = wreg[kc * 16 + i];
+                    const f32x4 w4 = wreg[kc * NI + i];
                     p = fmaf(w4.x, xk[kc].x, p); p = fmaf(w4.y, xk[kc].y, p); p = fmaf(w4.z, xk[kc].z, p); p = fmaf(w4.w, xk[kc].w, p);
                 }
                 p += dpp_move<0xB1, 0xF>(0.f, p);      // quad_perm [1,0,3,2]
@@ -349,8 +426,10 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
                 if (c16 == i) hv = p;
             }
             const float h = fmaxf(hv + bdv_n, 0.f);
-            smem[S_HV + v * NBH + n] = h;
-            if (v < nv) ws[g.o_Hv + (size_t)(b0 + v) * NBH + n] = h;
+            if (NW == 4 || c16 < NI) {
+                smem[S_HV + v * NBH + n] = h;
+                if (v < nv) ws[g.o_Hv + (size_t)(b0 + v) * NBH + n] = h;
+            }
         }
     }
     __syncthreads();
@@ -419,6 +498,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     // ---- E: gHv = (gPv Wcdv) * [Hv > 0] ----
 #pragma unroll
     for (int v = 0; v < VPW; ++v) {
+        if (!ch) break;
         const float gh = smem[S_HV + v * NBH + tid] > 0.f ? smem[S_GPV + v * 2] * wct0 + smem[S_GPV + v * 2 + 1] * wct1 : 0.f;
         smem[S_GHV + v * NBH + tid] = gh;
         if (v < nv) ws[g.o_gHv + (size_t)(b0 + v) * NBH + tid] = gh;
@@ -450,20 +530,30 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     // k = 64 kc + 4 c16 + e; the 16 threads that share c16 (one per srow) are added through LDS, thread t <-> channel t.
 #pragma unroll
     for (int v = 0; v < VPW; ++v) {
-        float gh[16];
+        float gh[NI];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) gh[i] = smem[S_GHV + v * NBH + srow + 16 * i];
+        for (int i = 0; i < NI; ++i) gh[i] = smem[S_GHV + v * NBH + row0 + 16 * i];
+        // (eight waves: the four-wave kernel's chain over the 16 rows of an srow in two halves - threads 0..255 start it from zero, a
+        // barrier, threads 256..511 continue it from their partner's partial sum: the same fmas in the same order, bit-identical)
 #pragma unroll
-        for (int kc = 0; kc < 4; ++kc) {
-            f32x4 p = {0.f, 0.f, 0.f, 0.f};
+        for (int half = 0; half < NW / 4; ++half) {
+            if (NW == 4 || (tid >> 8) == half) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const f32x4 w4 = wreg[kc * 16 + i];
-                p.x = fmaf(gh[i], w4.x, p.x); p.y = fmaf(gh[i], w4.y, p.y); p.z = fmaf(gh[i], w4.z, p.z); p.w = fmaf(gh[i], w4.w, p.w);
+                for (int kc = 0; kc < 4; ++kc) {
+                    f32x4 p = {0.f, 0.f, 0.f, 0.f};
+                    if (half == 1) p = *reinterpret_cast<const f32x4 *>(&smem[S_FPART + srow * NBH + kc * 64 + sk4]);
+#pragma unroll
+                    for (int i = 0; i < NI; ++i) {
+                        const f32x4 w4 = wreg[kc * NI + i];
+                        p.x = fmaf(gh[i], w4.x, p.x); p.y = fmaf(gh[i], w4.y, p.y); p.z = fmaf(gh[i], w4.z, p.z); p.w = fmaf(gh[i], w4.w, p.w);
+                    }
+                    *reinterpret_cast<f32x4 *>(&smem[S_FPART + srow * NBH + kc * 64 + sk4]) = p;
+                }
             }
-            *reinterpret_cast<f32x4 *>(&smem[S_FPART + srow * NBH + kc * 64 + sk4]) = p;
+            if (half + 1 < NW / 4) __syncthreads();
         }
         __syncthreads();
+        if (ch) {
         float acc = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc += smem[S_FPART + r * NBH + tid];
@@ -475,6 +565,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
         gv *= inv_keep_v;
         smem[S_GVT + v * NBH + tid] = gv;
         if (v < nv) ws[g.o_gVt + (size_t)(b0 + v) * NBH + tid] = gv;
+        }
         if (VPW > 1) __syncthreads();      // (the partial-sum block is reused by the next video)
     }
     if (VPW == 1) __syncthreads();
@@ -526,6 +617,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
                 ws[g.o_gRa + bj * NBH + c] = w1 * gv[q];
                 ws[g.o_gHr + bj * NBH + c] = hrv[q] > 0.f ? g0 * w20[q] + g1 * w21[q] : 0.f;
             }
+            if (NW == 8) break;
         }
     }
     {
@@ -541,14 +633,15 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
         }
     }
     STAMP(7);
-    write_loss_part(smem, ws, g.o_loss_part, (int)blockIdx.x - g.n_frm_wg, hs.gamma, S_LOSS);
+    write_loss_part<NW>(smem, ws, g.o_loss_part, (int)blockIdx.x - g.n_frm_wg, hs.gamma, S_LOSS);
     STAMP(8);
 }
 
 // Frame rows: Pf, frame adversarial CE, gPf, gHf = (gPf Wcd) * [Hf > 0], and this workgroup's
 // partial sums of dWcd = gPf^T Hf and dbcd.  FQ = ceil(F / 64) channels per lane; each wave keeps
-// its 4 rows in registers.
-template <int FQ>
+// its 4 rows in registers.  In the grid of the eight-wave kernel (NW == 8) waves 4..7 of a frame workgroup only take part in the
+// barriers: the rows, their order and every sum are those of the four-wave kernel.
+template <int FQ, int NW>
 __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *smem, int wg) {
     float *__restrict__ ws = ptrs.ws;
     const float *__restrict__ wsr = ptrs.ws;       // Hf is only read
@@ -557,6 +650,9 @@ __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *s
     const StepScalars hs = step_scalars(hy);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int F = g.F, T = g.T, BT = g.B * g.T;
+    const bool act = NW == 4 || wv < 4;
+    constexpr int FP = FQ * 64;
+    if (act) {
     const float *__restrict__ W0 = P + g.p_Wcd, *__restrict__ W1 = W0 + F;
     const float bc0 = P[g.p_bcd], bc1 = P[g.p_bcd + 1];
     const bool adv = (g.flags & TA3N_FLAG_ADV_FRAME) != 0;
@@ -636,7 +732,6 @@ __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *s
     }
     }   // row groups
     // cross-wave sums through LDS: [4 waves][2][FQ*64] then [4][2] for the bias partials
-    constexpr int FP = FQ * 64;
 #pragma unroll
     for (int q = 0; q < FQ; ++q) {
         smem[(wv * 2 + 0) * FP + q * 64 + lane] = a0[q];
@@ -644,7 +739,9 @@ __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *s
     }
     if (lane == 0) { smem[8 * FP + wv * 2] = sg0; smem[8 * FP + wv * 2 + 1] = sg1; }
     if (lane < 8) smem[S_LOSS_MIN + wv * 8 + lane] = lane == 4 ? l_frm : 0.f;
+    }   // act
     __syncthreads();
+    if (act) {
     float *__restrict__ part = ws + g.o_fh_part + (size_t)wg * 2 * F;
     for (int i = tid; i < 2 * F; i += 256) {
         const int c = i / F, k = i - c * F;
@@ -652,38 +749,54 @@ __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *s
     }
     if (tid < 2)
         ws[g.o_fh_bpart + (size_t)wg * 2 + tid] = (smem[8 * FP + tid] + smem[8 * FP + 2 + tid]) + (smem[8 * FP + 4 + tid] + smem[8 * FP + 6 + tid]);
-    write_loss_part(smem, ws, g.o_loss_part, g.n_vid_wg + wg, hs.gamma, S_LOSS_MIN);
+    }
+    write_loss_part<4>(smem, ws, g.o_loss_part, g.n_vid_wg + wg, hs.gamma, S_LOSS_MIN);
 }
 
-template <int FQ, int VPW, bool PIPE>
-__global__ __launch_bounds__(256) void heads_kernel(Geom g, Ptrs ptrs) {
+template <int FQ, int VPW, bool PIPE, int NW>
+__global__ __launch_bounds__(64 * NW) void heads_kernel(Geom g, Ptrs ptrs) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // the (short) frame workgroups come first in the grid: if the grid does not fit on the chip at once, the workgroups that
     // start late are video workgroups behind finished frame workgroups, not frame workgroups behind finished video ones
-    if ((int)blockIdx.x < g.n_frm_wg) frame_wg<FQ>(g, ptrs, smem, (int)blockIdx.x);
-    else video_wg<VPW, PIPE>(g, ptrs, smem);
+    if ((int)blockIdx.x < g.n_frm_wg) frame_wg<FQ, NW>(g, ptrs, smem, (int)blockIdx.x);
+    else video_wg<VPW, PIPE, NW>(g, ptrs, smem);
 }
 
-template <int FQ, int VPW, bool PIPE>
+template <int FQ, int VPW, bool PIPE, int NW>
 int launch_fq_vpw_pipe(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
     static_assert(8 * FQ * 64 + 16 <= S_LOSS_MIN, "the frame partials must stay below the loss slots");
     static std::once_flag attr_once;   // > 64 KiB of dynamic LDS needs the opt-in once per process; callers may be DataParallel's
                                        // one-thread-per-replica workers (re-entrancy), hence call_once and no plain flag
     std::call_once(attr_once, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(heads_kernel<FQ, VPW, PIPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(heads_kernel<FQ, VPW, PIPE, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
-    hipLaunchKernelGGL((heads_kernel<FQ, VPW, PIPE>), dim3(g.n_vid_wg + g.n_frm_wg), dim3(256), (size_t)Lds<VPW>::TOTAL * sizeof(float), stream, g, ptrs);
+    constexpr size_t lds_bytes = (size_t)Lds<VPW, NW>::TOTAL * sizeof(float);
+    hipLaunchKernelGGL((heads_kernel<FQ, VPW, PIPE, NW>), dim3(g.n_vid_wg + g.n_frm_wg), dim3(64 * NW), lds_bytes, stream, g, ptrs);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 template <int FQ, int VPW>
 int launch_fq_vpw(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
-    return g.n_rel > 4 / VPW ? launch_fq_vpw_pipe<FQ, VPW, true>(g, ptrs, stream) : launch_fq_vpw_pipe<FQ, VPW, false>(g, ptrs, stream);
+    return g.n_rel > 4 / VPW ? launch_fq_vpw_pipe<FQ, VPW, true, 4>(g, ptrs, stream) : launch_fq_vpw_pipe<FQ, VPW, false, 4>(g, ptrs, stream);
+}
+
+// The eight-wave kernel exists where a frame wave's registers fit the 256 a lane has with two waves per SIMD (FQ <= EIGHT_MAX_FQ:
+// fc_dim <= 512; wider frame layers keep four waves), for one video per workgroup and at most one relation per FOUR-wave wave.
+constexpr int EIGHT_MAX_FQ = 8;
+std::atomic<int> g_heads_waves{0};     // ta3n_set_heads_waves: 0 automatic, 4, 8
+
+int waves_for(const Geom &g) {
+    const int fq = (g.F + 63) / 64;
+    const bool can8 = g.heads_vpw != 2 && g.n_rel >= 1 && g.n_rel <= 4 && fq <= EIGHT_MAX_FQ;
+    return can8 && g_heads_waves.load(std::memory_order_relaxed) != 4 ? 8 : 4;
 }
 
 template <int FQ>
 int launch_fq(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
     if (g.heads_vpw == 2) return launch_fq_vpw<FQ, 2>(g, ptrs, stream);
+    if constexpr (FQ <= EIGHT_MAX_FQ) {
+        if (waves_for(g) == 8) return launch_fq_vpw_pipe<FQ, 1, false, 8>(g, ptrs, stream);
+    }
     return launch_fq_vpw<FQ, 1>(g, ptrs, stream);
 }
 
@@ -692,6 +805,14 @@ int launch_fq(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
 namespace ta3n {
 
 bool heads_supported(int NB, int C, int F) { return NB == NBH && C <= 64 && F <= 2048; }
+
+int heads_waves(const Geom &g) { return heads_supported(g.NB, g.C, g.F) ? waves_for(g) : 0; }
+
+int set_heads_waves(int waves) {
+    if (waves != 0 && waves != 4 && waves != 8) return -1;
+    g_heads_waves.store(waves, std::memory_order_relaxed);
+    return 0;
+}
 
 int launch_heads(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
     if (!heads_supported(g.NB, g.C, g.F)) return -1;

@@ -182,6 +182,8 @@ int launch_to_bf16(const float *src, float *dst_twin, int64_t n, hipStream_t str
 int launch_to_bf16_pair(const float *src, float *dst_hi, float *dst_lo, int64_t n, hipStream_t stream);   // ... and the lo plane
 bool heads_supported(int NB, int C, int F);   // configurations the fused heads kernel (ta3n_heads.hip) covers
 int launch_heads(const Geom &g, const Ptrs &ptrs, hipStream_t stream);
+int set_heads_waves(int waves);               // 0 automatic / 4 / 8 waves per workgroup of the heads kernel, where a shape has both; -1: no such value
+int heads_waves(const Geom &g);               // what launch_heads would launch for this geometry now (0: no heads kernel)
 int launch_pool_cls(const Geom &g, const Ptrs &ptrs, hipStream_t stream);   // TA3N_AGG_AVGPOOL: between F1 and gZ1
 int launch_pool_avg_fwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream);
 int launch_pool_avg_bwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream);
