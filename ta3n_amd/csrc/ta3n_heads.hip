@@ -100,10 +100,6 @@ constexpr int S_LOSS_MIN = Lds<1>::LOSS;                        // (the frame wo
 #define STAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ bool video_valid(int Bs, int valid_source, int valid_target, int b) {
-    return b < Bs ? (b < valid_source) : (b - Bs < valid_target);
-}
-
 // The per-step scalars a workgroup uses, read ONCE at its top.  `hy` points into the workspace the kernel also stores to, so a read of
 // hy->x inside a loop is re-issued after every store - and each such read came with s_waitcnt vmcnt(0), i.e. it also waited for the
 // operands requested ahead for the NEXT relation / row (found in the ISA in round 5: one dependent round trip per relation in stage G
@@ -319,7 +315,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
                 d1 = wave_allreduce_sum(d1) + rel_cur.b1;
                 if (PIPE) rel_cur = rel_nxt;
                 float w = 0.f;
-                if (attn_on) w = 1.f - soft2(d0, d1).H;
+                if (attn_on) w = attn_weight(soft2(d0, d1));
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     ws[g.o_R + ((size_t)b * NR + j) * NBH + q * 64 + lane] = r[q];
@@ -446,11 +442,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
         }
         d0 = wave_allreduce_sum(d0) + bcdv0;
         d1 = wave_allreduce_sum(d1) + bcdv1;
-        // class softmax over lanes (lanes >= C hold -inf)
-        const float m = wave_allreduce_max(y);
-        const float e = lane < C ? expf(y - m) : 0.f;
-        const float ls = logf(wave_allreduce_sum(e));
-        const float lp = lane < C ? y - m - ls : 0.f;
+        const float lp = lane_log_softmax(y, lane < C).lp;      // class softmax over lanes (lanes >= C hold -inf)
         const float pr = lane < C ? expf(lp) : 0.f;
         const float Hc = wave_allreduce_sum(-pr * lp);
         float gy = 0.f, g0 = 0.f, g1 = 0.f;
@@ -462,23 +454,21 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
             const bool ent_on = (g.flags & TA3N_FLAG_ATTN_ENTROPY) && valid;
             const float ce = hs.gamma * hs.inv_n_ent;
             if (cls_on) {                                                              // main.py:446
-                gy = (pr - (lane == label ? 1.f : 0.f)) * hs.inv_n_cls;
+                gy = class_ce_grad(pr, lane == label, hs.inv_n_cls);
                 if (lane == label) l_cls = -lp * hs.inv_n_cls;
             }
             if (ent_on) {                                                              // loss.py:20-24
-                gy += ce * (1.f + s.H) * (-pr * (lp + Hc));                            // dH/dz_i = -p_i (log p_i + H)
+                gy += ce * (1.f + s.H) * dH_dz(pr, lp, Hc);
                 if (lane == 0) l_ent = (1.f + s.H) * Hc * hs.inv_n_ent;
             }
             if (lane >= C) gy = 0.f;
             if ((g.flags & TA3N_FLAG_ADV_VIDEO) && valid) {                           // main.py:508-538, l = 1
-                const int d = is_src ? 0 : 1;
-                if (lane == 0) l_vid = -(d ? s.lp1 : s.lp0) * hs.inv_n_vid;
-                g0 = (s.p0 - (d == 0 ? 1.f : 0.f)) * hs.inv_n_vid;
-                g1 = (s.p1 - (d == 1 ? 1.f : 0.f)) * hs.inv_n_vid;
+                const DomainCe c = domain_ce(s, is_src, hs.inv_n_vid);
+                g0 = c.g0; g1 = c.g1; if (lane == 0) l_vid = c.l;
             }
             if (ent_on) {
-                g0 += ce * Hc * (-s.p0 * (s.lp0 + s.H));
-                g1 += ce * Hc * (-s.p1 * (s.lp1 + s.H));
+                g0 += ce * Hc * dH_dz(s.p0, s.lp0, s.H);
+                g1 += ce * Hc * dH_dz(s.p1, s.lp1, s.H);
             }
             if (lane < C) ws[g.o_gY + (size_t)b * C + lane] = gy;
             if (lane == 0) {
@@ -593,10 +583,8 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
             const Soft2 s = soft2(z0, z1);
             float g0 = 0.f, g1 = 0.f;
             if (adv_rel) {                                                             // main.py:508-538, l = 0
-                const int d = is_src ? 0 : 1;
-                if (lane == 0) l_rel += -(d ? s.lp1 : s.lp0) * hs.inv_n_rel;
-                g0 = (s.p0 - (d == 0 ? 1.f : 0.f)) * hs.inv_n_rel;
-                g1 = (s.p1 - (d == 1 ? 1.f : 0.f)) * hs.inv_n_rel;
+                const DomainCe c = domain_ce(s, is_src, hs.inv_n_rel);
+                g0 = c.g0; g1 = c.g1; if (lane == 0) l_rel += c.l;
             }
             if (lane == 0) { ws[g.o_gPr + bj * 2] = g0; ws[g.o_gPr + bj * 2 + 1] = g1; }
             float w1 = 1.f;
@@ -606,16 +594,15 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
 #pragma unroll
                 for (int q = 0; q < 4; ++q) dot = fmaf(rv[q], gv[q], dot);
                 dot = wave_allreduce_sum(dot);
-                g0 += dot * s.p0 * (s.lp0 + s.H);
-                g1 += dot * s.p1 * (s.lp1 + s.H);
-                w1 = 1.f + (1.f - s.H);
+                attn_back(s, dot, g0, g1);
+                w1 = attn_scale(s);
             }
             if (lane == 0) { ws[g.o_gPrT + bj * 2] = g0; ws[g.o_gPrT + bj * 2 + 1] = g1; }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int c = q * 64 + lane;
                 ws[g.o_gRa + bj * NBH + c] = w1 * gv[q];
-                ws[g.o_gHr + bj * NBH + c] = hrv[q] > 0.f ? g0 * w20[q] + g1 * w21[q] : 0.f;
+                ws[g.o_gHr + bj * NBH + c] = relu_back2(hrv[q], g0, w20[q], g1, w21[q]);
             }
             if (NW == 8) break;
         }
@@ -700,10 +687,8 @@ __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *s
             float g0 = 0.f, g1 = 0.f;
             if (adv && valid) {                                                        // main.py:508-538, l = 2
                 const Soft2 s = soft2(d0[i], d1[i]);
-                const int d = b < g.Bs ? 0 : 1;
-                l_frm += -(d ? s.lp1 : s.lp0) * hs.inv_n_frm;
-                g0 = (s.p0 - (d == 0 ? 1.f : 0.f)) * hs.inv_n_frm;
-                g1 = (s.p1 - (d == 1 ? 1.f : 0.f)) * hs.inv_n_frm;
+                const DomainCe c = domain_ce(s, b < g.Bs, hs.inv_n_frm);
+                g0 = c.g0; g1 = c.g1; l_frm += c.l;
             }
             if (lane == 0) {
                 ws[g.o_Pf + (size_t)r * 2] = d0[i]; ws[g.o_Pf + (size_t)r * 2 + 1] = d1[i];
@@ -715,15 +700,10 @@ __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *s
                 const int k = q * 64 + lane;
                 const float h = hf[i][q];
                 if (k < F) {
-                    const float gh = h > 0.f ? g0 * w0[q] + g1 * w1[q] : 0.f;
+                    const float gh = relu_back2(h, g1, w1[q], g0, w0[q]);      // (this site has always rounded g0 w0 on its own, the others g1 w1: both forms are kept)
                     ws[g.o_gHf + (size_t)r * F + k] = gh;
                     if (g.o_ws16 >= 0)   // bf16 twin (TA3N_FLAG_BF16_STORE): the gradient launch reads it as a GEMM operand
-                    {
-                        const unsigned hb = pack_bf16(gh, 0.f);
-                        unsigned short *tw = reinterpret_cast<unsigned short *>(ws + g.o_ws16) + g.o_gHf + (size_t)r * F + k;
-                        *tw = (unsigned short)hb;
-                        if (g.pair_delta) tw[2 * (size_t)g.pair_delta] = (unsigned short)pack_bf16_lo(gh, 0.f, hb);      // pair twins: the lo plane
-                    }
+                        twin1(reinterpret_cast<unsigned short *>(ws + g.o_ws16) + g.o_gHf + (size_t)r * F + k, g.pair_delta, gh);
                 }
                 a0[q] = fmaf(g0, h, a0[q]);
                 a1[q] = fmaf(g1, h, a1[q]);

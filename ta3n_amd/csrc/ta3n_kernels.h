@@ -167,6 +167,48 @@ __device__ __forceinline__ void nesterov_sgd(float &p, float &m, float g_scaled,
     d = fmaf(mu, m, d);
     p = fmaf(-lr, d, p);
 }
+
+// The loss and attention rules, written ONCE under the same contract (keep every expression as written, association included): the fused heads
+// kernel, the unfused lists (pool_fwd / loss / pool_bwd, frame_attn_*, pool_cls), the MCD glue and the validation metrics call these, and every new variant does.
+// Is video b of the batch [Bs source | Bt target] a real row, not the padding of a ragged batch (source-only steps pass valid_target = 0)
+__device__ __forceinline__ bool video_valid(int Bs, int valid_source, int valid_target, int b) { return b < Bs ? (b < valid_source) : (b - Bs < valid_target); }
+// Domain cross-entropy of a 2-logit row (source: label 0, target: 1), mean over 1 / inv_n rows (main.py:508-538): loss term and logit gradient
+struct DomainCe { float l, g0, g1; };
+__device__ __forceinline__ DomainCe domain_ce(const Soft2 &s, bool is_src, float inv_n) {
+    const int d = is_src ? 0 : 1;
+    return {-(d ? s.lp1 : s.lp0) * inv_n, (s.p0 - (d == 0 ? 1.f : 0.f)) * inv_n, (s.p1 - (d == 1 ? 1.f : 0.f)) * inv_n};
+}
+__device__ __forceinline__ float dH_dz(float p, float lp, float H) { return -p * (lp + H); }   // of the entropy H of softmax(z) (loss.py:20-24)
+// Transferable attention (models.py:351-357): w = 1 - H(softmax z) and the features scaled by 1 + w.  The weights are not detached: with
+// dot = dL/dw, dot dw/dz_i = dot p_i (log p_i + H) joins the logit gradients; the gradient behind the scale is 1 + (1 - H) times the one in front.
+__device__ __forceinline__ float attn_weight(const Soft2 &s) { return 1.f - s.H; }
+__device__ __forceinline__ float attn_scale(const Soft2 &s) { return 1.f + (1.f - s.H); }
+__device__ __forceinline__ void attn_back(const Soft2 &s, float dot, float &g0, float &g1) {
+    g0 += dot * s.p0 * (s.lp0 + s.H);
+    g1 += dot * s.p1 * (s.lp1 + s.H);
+}
+// log_softmax of <= 64 logits over the lanes of a wave (lane c = class c where `on`) as torch takes it: m = max, e = exp(y - m), sum, ls = log sum,
+// lp = y - m - ls (0 off).  The softmax stays at the site: expf(lp) in the step's kernels, e / sum (torch's) in row_soft - they differ in the last bit.
+struct LaneSoft { float m, e, sum, ls, lp; };
+__device__ __forceinline__ LaneSoft lane_log_softmax(float y, bool on) {
+    const float m = wave_allreduce_max(on ? y : -INFINITY), e = on ? expf(y - m) : 0.f;
+    const float sum = wave_allreduce_sum(e), ls = logf(sum);
+    return {m, e, sum, ls, on ? y - m - ls : 0.f};
+}
+// gH = (ga wa + gb wb) [h > 0]: the way back through a 2-wide output layer and the ReLU in front of it.  The fmaf is written out (gb wb is rounded on its own): left to contraction, which product that is changes with the code around the sum.
+__device__ __forceinline__ float relu_back2(float h, float ga, float wa, float gb, float wb) { return h > 0.f ? fmaf(ga, wa, gb * wb) : 0.f; }
+__device__ __forceinline__ float class_ce_grad(float p, bool is_label, float inv_n_cls) { return (p - (is_label ? 1.f : 0.f)) * inv_n_cls; }   // main.py:446
+// One value / four values to the bf16 twin (TA3N_FLAG_BF16_STORE): the hi plane and, with pair twins (Geom::pair_delta floats further on), the lo plane
+__device__ __forceinline__ void twin1(unsigned short *__restrict__ tw, int64_t pair_delta, float v) {
+    const unsigned h = pack_bf16(v, 0.f);
+    *tw = (unsigned short)h;
+    if (pair_delta) tw[2 * (size_t)pair_delta] = (unsigned short)pack_bf16_lo(v, 0.f, h);
+}
+struct Twin4 { uint2 hi, lo; };
+__device__ __forceinline__ Twin4 twin4(const float4 v) {
+    const unsigned h0 = pack_bf16(v.x, v.y), h1 = pack_bf16(v.z, v.w);
+    return {make_uint2(h0, h1), make_uint2(pack_bf16_lo(v.x, v.y, h0), pack_bf16_lo(v.z, v.w, h1))};
+}
 #endif
 
 // Where an update finds the squared-norm partials of its step: the per-tile slots the fused step's gradient tiles left behind, or the

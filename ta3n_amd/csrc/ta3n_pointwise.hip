@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(Geom g, Ptrs ptrs) {
         d0 = wave_allreduce_sum(d0) + b2[0];
         d1 = wave_allreduce_sum(d1) + b2[1];
         float w = 0.f;
-        if (attn_on) w = 1.f - soft2(d0, d1).H;
+        if (attn_on) w = attn_weight(soft2(d0, d1));
         float r0 = 0.f;
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
@@ -107,16 +107,14 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(Geom g, Ptrs ptrs) {
         float g0 = ws[g.o_gPr + bj * 2 + 0], g1 = ws[g.o_gPr + bj * 2 + 1];
         float w1 = 1.f;
         if (attn_on) {
-            // dL/dw_j = <R_j, dL/dV> (+ upstream gradient on the attention output);
-            // dw/dz_i = p_i (log p_i + H)   (the weights are not detached, models.py:351-357)
+            // dL/dw_j = <R_j, dL/dV> (+ upstream gradient on the attention output), on to the logits by attn_back
             float dot = 0.f;
 #pragma unroll
             for (int q = 0; q < Q; ++q) dot = fmaf(ws[g.o_R + bj * NB + q * 64 + lane], gv[q], dot);
             dot = wave_allreduce_sum(dot) + ws[g.o_gattn + bj];
             const Soft2 s = soft2(ws[g.o_Pr + bj * 2 + 0], ws[g.o_Pr + bj * 2 + 1]);
-            g0 += dot * s.p0 * (s.lp0 + s.H);
-            g1 += dot * s.p1 * (s.lp1 + s.H);
-            w1 = 1.f + (1.f - s.H);
+            attn_back(s, dot, g0, g1);
+            w1 = attn_scale(s);
         }
         if (lane == 0) {
             ws[g.o_gPrT + bj * 2 + 0] = g0;
@@ -126,8 +124,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(Geom g, Ptrs ptrs) {
         for (int q = 0; q < Q; ++q) {
             const int c = q * 64 + lane;
             ws[g.o_gRa + bj * NB + c] = w1 * gv[q];
-            const float gh = g0 * W2[c] + g1 * W2[NB + c];
-            ws[g.o_gHr + bj * NB + c] = ws[g.o_Hr + bj * NB + c] > 0.f ? gh : 0.f;
+            ws[g.o_gHr + bj * NB + c] = relu_back2(ws[g.o_Hr + bj * NB + c], g0, W2[c], g1, W2[NB + c]);
         }
     }
 }
@@ -142,25 +139,26 @@ __global__ __launch_bounds__(256) void frame_attn_fwd_kernel(Geom g, Ptrs ptrs, 
     if (r >= g.B * g.T) return;
     float *__restrict__ ws = ptrs.ws;
     const int F = g.F;
-    const float w = 1.f - soft2(ws[g.o_Pf + (size_t)r * 2], ws[g.o_Pf + (size_t)r * 2 + 1]).H;   // get_trans_attn on the row's own logits
+    const float w = attn_weight(soft2(ws[g.o_Pf + (size_t)r * 2], ws[g.o_Pf + (size_t)r * 2 + 1]));   // get_trans_attn on the row's own logits
     const float w1 = w + 1.f;
     if (lane == 0) ws[o_attn_frame + r] = w;
     const float *__restrict__ src = ws + g.o_F1 + (size_t)r * F;
     float *__restrict__ dst = ws + o_F1a + (size_t)r * F;
-    // bf16 twin (TA3N_FLAG_BF16_STORE): the tuple launch and the TRN weight gradients read it as an operand (build_plan_trn)
+    // bf16 twin (TA3N_FLAG_BF16_STORE): the tuple launch and the TRN weight gradients read it as an operand (build_plan_trn).  The hi plane only: pair
+    // twins (Geom::pair_delta != 0) come with TA3N_FLAG_F32_SPLIT alone, which the plan builder refuses together with frame attention (frame_attn_refusal).
     unsigned short *__restrict__ tw = g.o_ws16 >= 0 ? reinterpret_cast<unsigned short *>(ws + g.o_ws16) + o_F1a + (size_t)r * F : nullptr;
     if ((F & 3) == 0) {
         for (int c = lane * 4; c < F; c += 256) {
             const float4 v = *reinterpret_cast<const float4 *>(src + c);
             const float4 y = make_float4(w1 * v.x, w1 * v.y, w1 * v.z, w1 * v.w);
             *reinterpret_cast<float4 *>(dst + c) = y;
-            if (tw) *reinterpret_cast<uint2 *>(tw + c) = make_uint2(pack_bf16(y.x, y.y), pack_bf16(y.z, y.w));
+            if (tw) *reinterpret_cast<uint2 *>(tw + c) = twin4(y).hi;
         }
     } else {
         for (int c = lane; c < F; c += 64) {
             const float y = w1 * src[c];
             dst[c] = y;
-            if (tw) tw[c] = (unsigned short)(pack_bf16(y, 0.f) & 0xFFFFu);
+            if (tw) twin1(tw + c, 0, y);
         }
     }
 }
@@ -179,7 +177,7 @@ __global__ __launch_bounds__(256) void frame_attn_bwd_kernel(Geom g, Ptrs ptrs, 
     float *__restrict__ ws = ptrs.ws;
     const int F = g.F;
     const Soft2 s = soft2(ws[g.o_Pf + (size_t)r * 2], ws[g.o_Pf + (size_t)r * 2 + 1]);
-    const float w1 = 1.f + (1.f - s.H);
+    const float w1 = attn_scale(s);
     const float *__restrict__ f1 = ws + g.o_F1 + (size_t)r * F;
     const float *__restrict__ gin = ws + o_gF1a + (size_t)r * F;
     float *__restrict__ gout = ws + o_gFs + (size_t)r * F;
@@ -200,8 +198,9 @@ __global__ __launch_bounds__(256) void frame_attn_bwd_kernel(Geom g, Ptrs ptrs, 
     }
     dot = wave_allreduce_sum(dot);
     if (lane == 0) {
-        ws[o_gPfT + (size_t)r * 2 + 0] = ws[g.o_gPf + (size_t)r * 2 + 0] + dot * s.p0 * (s.lp0 + s.H);
-        ws[o_gPfT + (size_t)r * 2 + 1] = ws[g.o_gPf + (size_t)r * 2 + 1] + dot * s.p1 * (s.lp1 + s.H);
+        float g0 = ws[g.o_gPf + (size_t)r * 2 + 0], g1 = ws[g.o_gPf + (size_t)r * 2 + 1];
+        attn_back(s, dot, g0, g1);
+        ws[o_gPfT + (size_t)r * 2 + 0] = g0; ws[o_gPfT + (size_t)r * 2 + 1] = g1;
     }
 }
 
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
     if (rid < n_vid) {
         const int b = rid;
         const bool is_src = b < g.Bs;
-        const bool valid = is_src ? (b < hy->valid_source) : (b - g.Bs < hy->valid_target);
+        const bool valid = video_valid(g.Bs, hy->valid_source, hy->valid_target, b);
         const float *__restrict__ y = ws + g.o_Y + (size_t)b * C;
         float *__restrict__ gy = ws + g.o_gY + (size_t)b * C;
         float *__restrict__ gpv = ws + g.o_gPv + (size_t)b * 2;
@@ -255,8 +254,8 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
             const float lp = y[i] - m - ls;
             const float p = expf(lp);
             float gi = 0.f;
-            if (cls_on) gi = (p - (i == lab ? 1.f : 0.f)) * hy->inv_n_cls;
-            if (ent_on) gi += ce * (1.f + s.H) * (-p * (lp + Hc));                    // dH/dz_i = -p_i (log p_i + H)
+            if (cls_on) gi = class_ce_grad(p, i == lab, hy->inv_n_cls);
+            if (ent_on) gi += ce * (1.f + s.H) * dH_dz(p, lp, Hc);
             gy[i] = gi;
         }
         float g0 = 0.f, g1 = 0.f;
@@ -264,14 +263,12 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
         // ("add dummy tensors", models.py:707-708), so place_adv[0] = 'Y' adds the video-level CE a second time.
         const float vmult = ((g.flags & TA3N_FLAG_ADV_VIDEO) ? 1.f : 0.f) + ((NR == 0 && (g.flags & TA3N_FLAG_ADV_RELATION)) ? 1.f : 0.f);
         if (vmult > 0.f && valid) {                                                  // main.py:508-538, l = 1 (and l = 0 for avgpool)
-            const int d = is_src ? 0 : 1;
-            l_vid = -(d ? s.lp1 : s.lp0) * hy->inv_n_vid * vmult;
-            g0 = (s.p0 - (d == 0 ? 1.f : 0.f)) * hy->inv_n_vid * vmult;
-            g1 = (s.p1 - (d == 1 ? 1.f : 0.f)) * hy->inv_n_vid * vmult;
+            const DomainCe c = domain_ce(s, is_src, hy->inv_n_vid);
+            l_vid = c.l * vmult; g0 = c.g0 * vmult; g1 = c.g1 * vmult;
         }
         if (ent_on) {
-            g0 += ce * Hc * (-s.p0 * (s.lp0 + s.H));
-            g1 += ce * Hc * (-s.p1 * (s.lp1 + s.H));
+            g0 += ce * Hc * dH_dz(s.p0, s.lp0, s.H);
+            g1 += ce * Hc * dH_dz(s.p1, s.lp1, s.H);
         }
         gpv[0] = g0; gpv[1] = g1;
     } else if (rid < n_vid + n_rel + n_frm) {
@@ -279,19 +276,15 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
         const int row = is_rel ? rid - n_vid : rid - n_vid - n_rel;
         const int b = is_rel ? row / NR : row / T;
         const bool is_src = b < g.Bs;
-        const bool valid = is_src ? (b < hy->valid_source) : (b - g.Bs < hy->valid_target);
+        const bool valid = video_valid(g.Bs, hy->valid_source, hy->valid_target, b);
         const float *__restrict__ z = ws + (is_rel ? g.o_Pr : g.o_Pf) + (size_t)row * 2;
         float *__restrict__ gz = ws + (is_rel ? g.o_gPr : g.o_gPf) + (size_t)row * 2;
         const bool on = valid && (g.flags & (is_rel ? TA3N_FLAG_ADV_RELATION : TA3N_FLAG_ADV_FRAME));
         float g0 = 0.f, g1 = 0.f;
         if (on) {
             const float inv_n = is_rel ? hy->inv_n_rel : hy->inv_n_frm;
-            const Soft2 s = soft2(z[0], z[1]);
-            const int d = is_src ? 0 : 1;
-            const float l = -(d ? s.lp1 : s.lp0) * inv_n;
-            if (is_rel) l_rel = l; else l_frm = l;
-            g0 = (s.p0 - (d == 0 ? 1.f : 0.f)) * inv_n;
-            g1 = (s.p1 - (d == 1 ? 1.f : 0.f)) * inv_n;
+            const DomainCe c = domain_ce(soft2(z[0], z[1]), is_src, inv_n);
+            g0 = c.g0; g1 = c.g1; if (is_rel) l_rel = c.l; else l_frm = c.l;
         }
         gz[0] = g0; gz[1] = g1;
     }
@@ -414,9 +407,9 @@ __device__ __forceinline__ void update_range(const Geom &g, float *__restrict__ 
 #pragma unroll
         for (int k = 0; k < NS; ++k) reinterpret_cast<float4 *>(rule.state[k])[i] = make_float4(ss[0][k], ss[1][k], ss[2][k], ss[3][k]);
         if (g.o_p16 >= 0) {
-            const unsigned h0 = pack_bf16(pp[0], pp[1]), h1 = pack_bf16(pp[2], pp[3]);
-            reinterpret_cast<uint2 *>(ws + g.o_p16)[i] = make_uint2(h0, h1);
-            if (g.pair_delta) reinterpret_cast<uint2 *>(ws + g.o_p16 + g.pair_delta)[i] = make_uint2(pack_bf16_lo(pp[0], pp[1], h0), pack_bf16_lo(pp[2], pp[3], h1));
+            const Twin4 t = twin4(make_float4(pp[0], pp[1], pp[2], pp[3]));      // (the float4 just stored)
+            reinterpret_cast<uint2 *>(ws + g.o_p16)[i] = t.hi;
+            if (g.pair_delta) reinterpret_cast<uint2 *>(ws + g.o_p16 + g.pair_delta)[i] = t.lo;
         }
         i = nxt; cur = nx;
     }
@@ -473,14 +466,10 @@ __global__ __launch_bounds__(256) void pool_cls_kernel(Geom g, Ptrs ptrs) {
     }
     __syncthreads();
     if (wave == 0) {                              // softmax cross-entropy on the C <= 64 logits
-        const bool on = b < g.Bs && b < hy->valid_source;
+        const bool on = video_valid(g.Bs, hy->valid_source, 0, b);
         const int label = on ? reinterpret_cast<const int32_t *>(ws + g.o_labels)[b] : -1;
-        const float y = lane < C ? s_y[lane] : -INFINITY;
-        const float m = wave_allreduce_max(y);
-        const float e = lane < C ? expf(y - m) : 0.f;
-        const float ls = logf(wave_allreduce_sum(e));
-        const float lp = lane < C ? y - m - ls : 0.f;
-        const float gy = (on && lane < C) ? (expf(lp) - (lane == label ? 1.f : 0.f)) * hy->inv_n_cls : 0.f;
+        const float lp = lane_log_softmax(lane < C ? s_y[lane] : -INFINITY, lane < C).lp;
+        const float gy = (on && lane < C) ? class_ce_grad(expf(lp), lane == label, hy->inv_n_cls) : 0.f;
         const float l = wave_allreduce_sum((on && lane == label) ? -lp * hy->inv_n_cls : 0.f);
         if (lane < C) ws[g.o_gY + (size_t)b * C + lane] = gy;
         if (lane < 8) ws[g.o_loss_part + (size_t)b * 8 + lane] = lane < 2 ? l : 0.f;   // {loss, loss_c, 0 ...}: losses region layout
@@ -497,11 +486,7 @@ __global__ __launch_bounds__(256) void pool_cls_kernel(Geom g, Ptrs ptrs) {
             const size_t idx = ((size_t)b * T + t) * F + k;
             const float gz = ws[g.o_F1 + idx] > 0.f ? gf : 0.f;
             ws[g.o_gZ1 + idx] = gz;
-            if (twin) {
-                const unsigned h = pack_bf16(gz, 0.f);
-                twin[g.o_gZ1 + idx] = (unsigned short)h;
-                if (g.pair_delta) twin[2 * (size_t)g.pair_delta + g.o_gZ1 + idx] = (unsigned short)pack_bf16_lo(gz, 0.f, h);
-            }
+            if (twin) twin1(twin + g.o_gZ1 + idx, g.pair_delta, gz);
         }
     }
 }
@@ -572,9 +557,9 @@ __device__ __forceinline__ void gather_row_f32(int row, const float *__restrict_
             const float4 v4 = s4[i];
             d4[i] = v4;
             if (t2) {
-                const unsigned h0 = pack_bf16(v4.x, v4.y), h1 = pack_bf16(v4.z, v4.w);
-                t2[i] = make_uint2(h0, h1);
-                if (pair_delta) t2[pair_delta / 2 + i] = make_uint2(pack_bf16_lo(v4.x, v4.y, h0), pack_bf16_lo(v4.z, v4.w, h1));   // (uint2 = 2 floats)
+                const Twin4 t = twin4(v4);
+                t2[i] = t.hi;
+                if (pair_delta) t2[pair_delta / 2 + i] = t.lo;   // (uint2 = 2 floats)
             }
         }
     } else {
@@ -641,17 +626,16 @@ __global__ __launch_bounds__(1024) void eval_metrics_kernel(Geom g, float *__res
     for (int b = wv; b < n; b += 16) {
         const float y = lane < C ? ws[g.o_Y + (size_t)b * C + lane] : -INFINITY;
         const int lab = labels[b];
-        const float m = wave_allreduce_max(y);
-        const float ls = logf(wave_allreduce_sum(lane < C ? expf(y - m) : 0.f));
+        const LaneSoft sm = lane_log_softmax(y, lane < C);
         const float ylab = wave_allreduce_sum(lane == lab ? y : 0.f);
         // rank of the label among the logits, torch.topk order
         const float ahead = wave_allreduce_sum((lane < C && (y > ylab || (y == ylab && lane < lab))) ? 1.f : 0.f);
         // argmax with the same tie rule: the class that has nobody ahead of it
-        const float myahead_key = (lane < C && y == m) ? (float)lane : 1e9f;
+        const float myahead_key = (lane < C && y == sm.m) ? (float)lane : 1e9f;
         float amin = myahead_key;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) amin = fminf(amin, __shfl_xor(amin, off, 64));
-        ce += -(ylab - m - ls);
+        ce += -(ylab - sm.m - sm.ls);
         t1 += ahead < 1.f ? 1.f : 0.f;
         t5 += ahead < 5.f ? 1.f : 0.f;
         if (lane == 0 && lab >= 0 && lab < C) atomicAdd(&conf[lab * C + (int)amin], 1);
@@ -747,23 +731,20 @@ __global__ __launch_bounds__(256) void sgd_fixup_kernel(Geom g, float *__restric
         p.x = fmaf(a, gr.x, p.x); p.y = fmaf(a, gr.y, p.y); p.z = fmaf(a, gr.z, p.z); p.w = fmaf(a, gr.w, p.w);
         m.x = fmaf(-c, gr.x, m.x); m.y = fmaf(-c, gr.y, m.y); m.z = fmaf(-c, gr.z, m.z); m.w = fmaf(-c, gr.w, m.w);
         p4[i] = p; m4[i] = m;
-        if (p16 != nullptr) reinterpret_cast<uint2 *>(p16)[i] = make_uint2(pack_bf16(p.x, p.y), pack_bf16(p.z, p.w));
+        if (p16 != nullptr) reinterpret_cast<uint2 *>(p16)[i] = twin4(p).hi;
     }
 }
 
 __global__ void to_bf16_kernel(const float4 *__restrict__ src, uint2 *__restrict__ dst, int64_t n4) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const float4 v = src[i];
-        dst[i] = make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w));
+        dst[i] = twin4(src[i]).hi;
     }
 }
 
 __global__ void to_bf16_pair_kernel(const float4 *__restrict__ src, uint2 *__restrict__ hi, uint2 *__restrict__ lo, int64_t n4) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const float4 v = src[i];
-        const unsigned h0 = pack_bf16(v.x, v.y), h1 = pack_bf16(v.z, v.w);
-        hi[i] = make_uint2(h0, h1);
-        lo[i] = make_uint2(pack_bf16_lo(v.x, v.y, h0), pack_bf16_lo(v.z, v.w, h1));
+        const Twin4 t = twin4(src[i]);
+        hi[i] = t.hi; lo[i] = t.lo;
     }
 }
 
@@ -848,9 +829,9 @@ __device__ __forceinline__ BnRow bn_load(const float *__restrict__ row, int c0) 
 __device__ __forceinline__ void bn_store(float *__restrict__ row, unsigned short *__restrict__ tw, int pair_delta, int c0, const BnRow &y) {
     *reinterpret_cast<float4 *>(row + c0) = make_float4(y.v[0], y.v[1], y.v[2], y.v[3]);
     if (tw) {      // bf16 twin (TA3N_FLAG_BF16_STORE): the next GEMM launch reads it as an operand (ta3n_plan_twins.cpp: add_bf16_twins)
-        const unsigned h0 = pack_bf16(y.v[0], y.v[1]), h1 = pack_bf16(y.v[2], y.v[3]);
-        *reinterpret_cast<uint2 *>(tw + c0) = make_uint2(h0, h1);
-        if (pair_delta) *reinterpret_cast<uint2 *>(tw + c0 + 2 * (size_t)pair_delta) = make_uint2(pack_bf16_lo(y.v[0], y.v[1], h0), pack_bf16_lo(y.v[2], y.v[3], h1));
+        const Twin4 t = twin4(make_float4(y.v[0], y.v[1], y.v[2], y.v[3]));
+        *reinterpret_cast<uint2 *>(tw + c0) = t.hi;
+        if (pair_delta) *reinterpret_cast<uint2 *>(tw + c0 + 2 * (size_t)pair_delta) = t.lo;
     }
 }
 // NV per-thread values summed over the workgroup; every thread receives every total (wave butterfly, then waves 0 .. 15 in order)
@@ -1117,14 +1098,9 @@ int launch_bn_shared_bwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
 // A row of <= 64 class logits on one wave (lane c = class c): softmax, log_softmax and entropy the way torch takes them.
 struct RowSoft { float p, lp, H; };
 __device__ __forceinline__ RowSoft row_soft(float z, bool on) {
-    const float m = wave_allreduce_max(on ? z : -INFINITY);
-    const float e = on ? expf(z - m) : 0.f;
-    const float sum = wave_allreduce_sum(e);
-    RowSoft r;
-    r.p = e / sum;
-    r.lp = on ? z - m - logf(sum) : 0.f;
-    r.H = -wave_allreduce_sum(on ? r.p * r.lp : 0.f);
-    return r;
+    const LaneSoft s = lane_log_softmax(z, on);
+    const float p = s.e / s.sum;      // torch's softmax; the step's kernels take expf(lp)
+    return {p, s.lp, -wave_allreduce_sum(on ? p * s.lp : 0.f)};
 }
 // + CrossEntropy(out_source_2, label) over the valid source rows (main.py:447-448): its logit gradient to gY2 (rows without a label: 0), the
 // per-row loss terms to part[b]; with the attentive entropy on, the target rows of gY are cleared - that term moves to the second pass
@@ -1137,10 +1113,10 @@ __global__ __launch_bounds__(256) void mcd_source_loss_kernel(Geom g, float *__r
     const float inv = hy->inv_n_cls;
     const bool on = lane < C;
     float g2 = 0.f, term = 0.f;
-    if (b < ns) {
+    if (video_valid(g.Bs, ns, 0, b)) {
         const int label = reinterpret_cast<const int *>(ws + g.o_labels)[b];
         const RowSoft r = row_soft(on ? ws[g.o_Y2 + (size_t)b * C + lane] : 0.f, on);
-        g2 = (expf(r.lp) - (lane == label ? 1.f : 0.f)) * inv;
+        g2 = class_ce_grad(expf(r.lp), lane == label, inv);
         term = -wave_allreduce_sum(lane == label ? r.lp : 0.f);
     }
     if (on) {
@@ -1177,10 +1153,10 @@ __global__ __launch_bounds__(256) void mcd_second_loss_kernel(Geom g, float *__r
         const Soft2 pv = soft2(ws[g.o_Pv + (size_t)b * 2], ws[g.o_Pv + (size_t)b * 2 + 1]);
         const float w = 1.f + pv.H;
         e_new = w * a.H; e_old = w * f.H;
-        g1 += on ? scale * w * (-a.p * (a.lp + a.H)) : 0.f;                  // d H(z) / d z_k = -p_k (log p_k + H)
+        g1 += on ? scale * w * dH_dz(a.p, a.lp, a.H) : 0.f;
         if (lane < 2) {
             const float pj = lane == 0 ? pv.p0 : pv.p1, lpj = lane == 0 ? pv.lp0 : pv.lp1;
-            ws[g.o_gPv + (size_t)b * 2 + lane] += scale * (a.H - f.H) * (-pj * (lpj + pv.H));
+            ws[g.o_gPv + (size_t)b * 2 + lane] += scale * (a.H - f.H) * dH_dz(pj, lpj, pv.H);
         }
     }
     if (on) {
