@@ -706,7 +706,9 @@ __device__ __forceinline__ const float *base_ptr(const Ptrs &p, int base) {
 // 16 x 8-byte stamps in the workspace region "stamps", which the plan builder of such a build lays out directly in front of "zeros" (the
 // kernel knows zeros_off): [0] entry, [1] descriptors / bias loaded, [2] K loop done, [3] all waves done, [4] accumulators in LDS, [5] stores
 // issued, [6] the task's cost (its K), [7] its Seg count, [8] cycles thread 0 spent in the K loop waiting for "stage landed + barrier",
-// [9] cycles it spent issuing the next stage's DMA + LDS reads + MFMAs, [10] stages.  (Round 6: the stamps used to live in a __device__
+// [9] cycles it spent issuing the next stage's DMA + LDS reads + MFMAs, [10] stages, [11] (second wave, first store pass): the pass's
+// LDS sum is there.  The compiler puts its wait for the pass's global operands (residual, mask) in front of that sum's first use, so [11] - [4]
+// of a masked tile against a plain tile of the same launch is the exposed wait for them.  (Round 6: the stamps used to live in a __device__
 // array, of which every instantiation unit has its own copy - the reader only saw the launcher's.)
 #ifdef TA3N_GEMM_STAMPS
 #define TA3N_STAMP_SLOTS 16
@@ -714,6 +716,8 @@ __device__ __forceinline__ const float *base_ptr(const Ptrs &p, int base) {
 #define GSTAMP_PTR (reinterpret_cast<unsigned long long *>(const_cast<float *>(ptrs.ws) + zeros_off - TA3N_STAMP_FLOATS))
 #define GSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < 8192) GSTAMP_PTR[blockIdx.x * TA3N_STAMP_SLOTS + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #define GSTAMP_VAL(i, v) do { if (threadIdx.x == 0 && blockIdx.x < 8192) GSTAMP_PTR[blockIdx.x * TA3N_STAMP_SLOTS + (i)] = (unsigned long long)(v); } while (0)
+// a value stamped by the second wave, which has no stamp stores of thread 0 in flight (stores count in vmcnt too)
+#define GSTAMP_W1(i, v) do { if (threadIdx.x == 64 && blockIdx.x < 8192) GSTAMP_PTR[blockIdx.x * TA3N_STAMP_SLOTS + (i)] = (unsigned long long)(v); } while (0)
 #define KSTAMP_DECL unsigned long long ks_wait = 0, ks_comp = 0, ks_t = 0; int ks_n = 0
 #define KSTAMP_BEGIN_WAIT do { ks_t = __builtin_amdgcn_s_memtime(); } while (0)
 #define KSTAMP_END_WAIT do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); ks_wait += n_ - ks_t; ks_t = n_; ++ks_n; } while (0)
@@ -914,6 +918,84 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         }
     }
 
+    // The epilogue's other operands - the residual (EPI_ADD), the ReLU / dropout mask (EPI_MASK) and the up to three masks of a
+    // fan-out tile - get the bias's treatment: none of their addresses depends on the accumulators, so every thread requests the
+    // float4 positions of its own epilogue passes at the head of the K loop (request_epilogue_operands below) and the store loop
+    // consumes them from registers, in its old order and with its old arithmetic.  In the store loop their latency overlapped
+    // ~100 ns of LDS reads, and the mask of a gradient-at-F1 tile (F1, written by another XCD two launches earlier) comes from
+    // the Infinity Cache or HBM, not from this XCD's L2.
+    // Predicates and vector / scalar paths are the store loop's own (epi_fetch4 is the one copy of them): no address is requested
+    // that the store loop would not have read.
+    // Sound because a launch of the default library is one dependency level: no task of a launch reads (operands, bias, add,
+    // aux, fan masks) what another task of the same launch writes.  Only chained launches, split-K pairs and the fused update
+    // have such pairs (Builder::end_chain lays the intervals out and orders them), and all three exist in the experiments build
+    // alone (OPT; chain_off >= 0: launch_gemm refuses them on the default library), which keeps the old sequence.
+    // tests/test_epilogue_operands_cpu.py lays out the same intervals for every un-chained GEMM launch of the benchmarked and
+    // the tested plans and finds no add / aux / fan-mask interval inside another task's stores.
+    // Registers: 4 per operand and pass.  Tiles of one pass (32x64 on eight waves) carry add + aux + three fan masks = 20, tiles
+    // of two passes (64x64 on eight waves) add + aux = 16, and these request their fan masks at the head of each pass, in front
+    // of the tile's own store.  That is 14 - 21 VGPRs more in the K loop (profiles/epilogue_prefetch_isa.txt), which the
+    // kind-specialised backward kernels of the twin steps (KV = 26; 104 - 106 VGPRs) take without reaching 128; of the general
+    // kernels (KV = 63) 21 would cross an occupancy step (the fp32 64x64 tile 113 -> 129), so they keep the old sequence and
+    // the parent's registers; and so does the forward kind kernel (KV = 1), whose tiles carry a bias and nothing else - with
+    // the request code compiled in, its three launches measured 0.1 - 0.3 us longer each.
+    constexpr bool EPI_EARLY = TA3N_EXPERIMENTS == 0 && KV != 63 && KV != 1;
+    constexpr int PF_IT = (EPI_EARLY && ITER_E <= 2) ? ITER_E : 0;     // passes whose add / aux are requested at the head of the K loop
+    constexpr bool PF_FAN = PF_IT == 1;                                 // ... and whose fan masks are
+    struct EpiOperands { const float *aux, *add; bool aux_vec, add_vec; int nfan; };      // workgroup-uniform
+    auto epi_operands = [&]() {      // (called at the request by the kernels that request early, behind the K loop by the others: nothing of it lives through their loop)
+        return EpiOperands{(epi & EPI_MASK) ? base_ptr(ptrs, t.aux_base) + t.aux_off : nullptr,
+                           (epi & EPI_ADD) ? base_ptr(ptrs, t.add_base) + t.add_off : nullptr,
+                           ((t.aux_off | t.aux_ld) & 3) == 0, ((t.add_off | t.add_ld) & 3) == 0, t.fan_count};
+    };
+    auto epi_fetch4 = [](float (&o)[4], const float *__restrict__ p, int nrem, bool vec) {   // o keeps its defaults where nothing is read
+        if (nrem >= 4 && vec) { const float4 q4 = *reinterpret_cast<const float4 *>(p); o[0] = q4.x; o[1] = q4.y; o[2] = q4.z; o[3] = q4.w; }
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e < nrem) o[e] = p[e];
+        }
+    };
+    auto fetch_add_aux = [&](const EpiOperands &eo, float (&av)[4], float (&mv)[4], int m, int n, int nrem) {      // nrem <= 0: nothing is read
+        if (eo.add != nullptr && nrem > 0) epi_fetch4(av, eo.add + (size_t)m * t.add_ld + n, nrem, eo.add_vec);
+        if (eo.aux != nullptr && nrem > 0) epi_fetch4(mv, eo.aux + (size_t)m * t.aux_ld + n, nrem, eo.aux_vec);
+    };
+    auto fetch_fan = [&](const EpiOperands &eo, float (&fm)[3][4], int m, int n, int nrem) {      // all mask loads of a fan-out tile
+        if (eo.nfan > 0 && nrem > 0) {
+            const bool fan_vec = (t.fan_ld & 3) == 0;
+#pragma unroll
+            for (int f = 0; f < 3; ++f)
+                if (f < eo.nfan)
+                    epi_fetch4(fm[f], ptrs.ws + (size_t)t.fan_mask_off[f] + (size_t)m * t.fan_ld + n, nrem, fan_vec && (t.fan_mask_off[f] & 3) == 0);
+        }
+    };
+    EpiOperands eo_early{nullptr, nullptr, false, false, 0};
+    // (filled by request_epilogue_operands, which every K loop the kernel holds calls: a task whose operand kinds are outside the kernel's
+    // KV set would skip the loop and read them unset - launch_gemm puts a launch on a kind kernel only if (kinds & ~KV) == 0)
+    float add_e[PF_IT > 0 ? PF_IT : 1][4], aux_e[PF_IT > 0 ? PF_IT : 1][4], fan_e[3][4];
+    // Called by the K loop right behind the issue of its FIRST stage: the requests' address arithmetic and predicates (0.5 - 0.6 us of
+    // instructions for two passes x two operands) then run under that stage's flight instead of in front of it, and the requests are out
+    // long before the first `s_waitcnt vmcnt(0)` of the loop, which waits for them together with the stage.
+    auto request_epilogue_operands = [&]() {
+        eo_early = epi_operands();
+#pragma unroll
+        for (int it = 0; it < PF_IT; ++it) {
+            const int idx = tid + it * NT;
+            const int mm_ = t.m0 + idx / (BN / 4), nn_ = t.n0 + (idx % (BN / 4)) * 4;
+            const int nr_ = (idx < BM * BN / 4 && mm_ < t.m_valid) ? t.n_valid - nn_ : 0;      // the store loop's nrem
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { add_e[it][e] = 0.f; aux_e[it][e] = 1.f; }
+            fetch_add_aux(eo_early, add_e[it], aux_e[it], mm_, nn_, nr_);
+            if constexpr (PF_FAN) {
+#pragma unroll
+                for (int f = 0; f < 3; ++f)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) fan_e[f][e] = 0.f;
+                fetch_fan(eo_early, fan_e, mm_, nn_, nr_);
+            }
+        }
+    };
+    static_assert(PF_IT == 0 || NS == 2, "the early requests are issued from the two-stage K loop (every kind-specialised backward kernel has two stages)");
+
     f32x16 acc[RM][RN];
 #pragma unroll
     for (int i = 0; i < RM; ++i)
@@ -976,6 +1058,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             int buf = 0;
             open_seg(cseg);
             issue(0, 0);
+            if constexpr (PF_IT > 0) request_epilogue_operands();
             for (;;) {
                 const int n_chunks = (klen + CH - 1) / CH;
                 for (int c = 0; c < n_chunks - 1; ++c) {             // chunks whose successor is in the same Seg (all full)
@@ -1182,20 +1265,21 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     const float dp = (epi & EPI_DROP_I) ? hh.p_drop_i : hh.p_drop_v;
     const uint32_t doff = drop_on ? (uint32_t)t.pad2 : 0u;      // stream offset of a stacked shared layer (--add_fc; 0 otherwise)
     float *__restrict__ cbase = const_cast<float *>(base_ptr(ptrs, t.c_base)) + (size_t)t.c_off;
-    const float *__restrict__ aux = (epi & EPI_MASK) ? base_ptr(ptrs, t.aux_base) + t.aux_off : nullptr;
-    const float *__restrict__ add = (epi & EPI_ADD) ? base_ptr(ptrs, t.add_base) + t.add_off : nullptr;
+    const EpiOperands eo = PF_IT > 0 ? eo_early : epi_operands();
+    const int nfan = eo.nfan;
     const bool c_vec = ((t.c_off | t.c_ld) & 3) == 0;
-    const bool aux_vec = ((t.aux_off | t.aux_ld) & 3) == 0, add_vec = ((t.add_off | t.add_ld) & 3) == 0;
-    const int nfan = t.fan_count;
     // Fused update (SgdSide::p_new): a gradient tile is also the optimiser step of its block of parameters.  torch.optim.SGD with
     // nesterov and weight decay (main.py:83, 583) in the arithmetic of sgd_kernel with the clip coefficient taken as 1:
     //   d = wd p + g;  m = mu m + d;  p_new = p - lr (d + mu m)
     // (a step whose gradient norm exceeds clip_gradient is corrected afterwards by sgd_fixup_kernel: the update is linear in g).
     const bool upd = OPT && side.p_new != nullptr && t.c_base == BASE_G;      // workgroup-uniform
     float sumsq = 0.f;   // EPI_SUMSQ: this thread's share of the tile's sum of squares
-    // Every flag test below is workgroup-uniform: a tile without bias / mask / residual issues no load for it (the
-    // bias and the per-step scalars were fetched before the K loop, so the first dependent global access of a plain
-    // tile is its store).
+    // Every flag test below is workgroup-uniform: a tile without bias / mask / residual / fan-out issues no load for it.  The
+    // bias and the per-step scalars were requested before the K loop, and in the kind-specialised kernels (EPI_EARLY) so were
+    // the residual and the mask (one-pass tiles: the fan-out masks too; two-pass tiles request those at the head of the pass, in
+    // front of the tile's own store): the first dependent global access of such a tile is its store.  The general kernels and
+    // the experiments build request residual and mask at the head of the pass and the fan-out masks behind the tile's own store,
+    // as before - see the request site above the K loop.
     constexpr int ITER = (BM * BN / 4 + NT - 1) / NT;
     constexpr int UNR = ITER <= 4 ? ITER : 2;
 #pragma unroll UNR
@@ -1212,21 +1296,22 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         const bool row_ok = m < m_valid;
         const int nrem = row_ok ? n_valid - n : 0;   // number of valid columns of this float4 (<= 0: none)
         float av[4] = {0.f, 0.f, 0.f, 0.f}, mv[4] = {1.f, 1.f, 1.f, 1.f};
-        if (add != nullptr && nrem > 0) {           // issued first: their latency overlaps the LDS reads below
-            const float *ap = add + (size_t)m * t.add_ld + n;
-            if (nrem >= 4 && add_vec) { const float4 q4 = *reinterpret_cast<const float4 *>(ap); av[0] = q4.x; av[1] = q4.y; av[2] = q4.z; av[3] = q4.w; }
-            else {
+        float fm[3][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        if constexpr (PF_IT > 0) {                  // requested before the K loop (ITER == PF_IT: the loop is unrolled, `it` a constant)
+            // (the empty asm makes the value opaque HERE: without it the compiler moves the mask's `> 0` up to the request - a compare
+            // folded into the merge with the default 1.0 - and waits for the load in front of the K loop: measured, +1.2 us per tile)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nrem) av[e] = ap[e];
-            }
+            for (int e = 0; e < 4; ++e) { av[e] = add_e[PF_IT > 0 ? it : 0][e]; mv[e] = aux_e[PF_IT > 0 ? it : 0][e]; asm volatile("" : "+v"(mv[e])); }
+        } else {
+            fetch_add_aux(eo, av, mv, m, n, nrem);  // requested here: their latency overlaps the LDS reads below
         }
-        if (aux != nullptr && nrem > 0) {
-            const float *xp = aux + (size_t)m * t.aux_ld + n;
-            if (nrem >= 4 && aux_vec) { const float4 q4 = *reinterpret_cast<const float4 *>(xp); mv[0] = q4.x; mv[1] = q4.y; mv[2] = q4.z; mv[3] = q4.w; }
-            else {
+        if constexpr (PF_FAN) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) if (e < nrem) mv[e] = xp[e];
-            }
+            for (int f = 0; f < 3; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { fm[f][e] = fan_e[f][e]; asm volatile("" : "+v"(fm[f][e])); }
+        } else if constexpr (EPI_EARLY) {
+            fetch_fan(eo, fm, m, n, nrem);          // in front of the tile's own store
         }
         float up[4] = {0.f, 0.f, 0.f, 0.f}, um[4] = {0.f, 0.f, 0.f, 0.f};      // fused update: old parameters and momentum of these entries
         if (upd_early) {                          // requested before the K loop
@@ -1255,6 +1340,12 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             v4.x += part.x; v4.y += part.y; v4.z += part.z; v4.w += part.w;
         }
         if (split_other != nullptr) { v4.x += other4[0]; v4.y += other4[1]; v4.z += other4[2]; v4.w += other4[3]; }
+#ifdef TA3N_GEMM_STAMPS
+        if (it == 0) {      // [11]: the first pass's LDS sum is there - and, the compiler's own wait for them standing in front of it, so are its global operands
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            GSTAMP_W1(11, __builtin_amdgcn_s_memtime());
+        }
+#endif
         float v[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -1310,18 +1401,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         }
         if (nfan > 0) {
             const bool fan_vec = nrem >= 4 && (t.fan_ld & 3) == 0;
-            float fm[3][4];
-#pragma unroll
-            for (int f = 0; f < 3; ++f) {   // all mask loads first
-                if (f < nfan) {
-                    const float *mp = ptrs.ws + (size_t)t.fan_mask_off[f] + (size_t)m * t.fan_ld + n;
-                    if (fan_vec && (t.fan_mask_off[f] & 3) == 0) { const float4 q4 = *reinterpret_cast<const float4 *>(mp); fm[f][0] = q4.x; fm[f][1] = q4.y; fm[f][2] = q4.z; fm[f][3] = q4.w; }
-                    else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) fm[f][e] = e < nrem ? mp[e] : 0.f;
-                    }
-                }
-            }
+            if constexpr (!EPI_EARLY) fetch_fan(eo, fm, m, n, nrem);      // general and forward kernels, experiments build: all mask loads here, behind the tile's own store, as before
 #pragma unroll
             for (int f = 0; f < 3; ++f) {   // same value through several ReLU masks (TRN tuples of one scale)
                 if (f < nfan) {

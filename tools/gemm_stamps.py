@@ -3,7 +3,8 @@
     TA3N_LIBDIR=$PWD/ta3n_amd/lib_stamps python tools/gemm_stamps.py [bf16|f32] [config 2|4|5]
 ): per-workgroup s_memtime stamps of every GEMM launch of the fused step - entry / descriptors loaded / K loop done / epilogue done,
 and inside the K loop the time thread 0 spends WAITING for a stage (s_waitcnt + s_barrier) against the time it spends issuing the next
-stage's DMA, LDS reads and MFMAs - printed per launch and per tile length: where a launch's time goes."""
+stage's DMA, LDS reads and MFMAs - printed per launch and per tile length: where a launch's time goes.  TA3N_KIND_KERNELS=0 runs the
+general kernels, which request a tile's residual and mask inside the store loop; the default runs the kind-specialised ones."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -54,4 +55,5 @@ for i, ph in enumerate(phases):
         ns = np.maximum(st[m, 10], 1)
         print(f"    K {cst:5d} x{m.sum():4d}: desc {d(1, 0):5.2f}  kloop {d(2, 1):6.2f} (thread 0: waiting for stage+barrier {np.mean(st[m, 8]) * TICK:6.2f}, issue+compute {np.mean(st[m, 9]) * TICK:6.2f}, "
               f"{np.mean(ns):.1f} stages -> {np.mean(st[m, 8] / ns) * TICK * 1e3:5.0f} + {np.mean(st[m, 9] / ns) * TICK * 1e3:5.0f} ns per stage)  wait-waves {d(3, 2):5.2f}  to-lds {d(4, 3):5.2f}  "
-              f"combine+store {d(5, 4):5.2f}  | finish {np.mean(st[m, 5] - t0) * TICK:6.2f} us")
+              f"combine+store {d(5, 4):5.2f} (second wave, first pass: LDS sum and global operands there {d(11, 4):5.2f} after [4])"
+              f"  | finish {np.mean(st[m, 5] - t0) * TICK:6.2f} us")

@@ -54,17 +54,20 @@ def main():
           f"min {min(wall):.1f}  max {max(wall):.1f}")
     print("step walls in order, us: " + " ".join(f"{w:.0f}" for w in wall))
     print(f"kernel-busy us per step: median {statistics.median(busy):.1f}; idle per step: median {statistics.median(w - b for w, b in zip(wall, busy)):.1f}")
-    n = len(steps[0])
-    if all(len(st) == n for st in steps):
-        print("per launch (median over the steps): duration us | gap before it us")
-        for k in range(n):
-            d = statistics.median((st[k][1] - st[k][0]) / 1e3 for st in steps)
-            gaps = []
-            for j, st in enumerate(steps):
-                prev_end = st[k - 1][1] if k > 0 else (steps[j - 1][-1][1] if j > 0 else None)
-                if prev_end is not None:
-                    gaps.append((st[k][0] - prev_end) / 1e3)
-            print(f"  {k:2d} {steps[0][k][2]:34s} {d:8.2f} | {statistics.median(gaps):7.2f}  (max gap {max(gaps):7.2f})")
+    # per launch over the steps with the usual launch count (a step that also carries a one-off launch - the region's first - is left out)
+    n = statistics.mode(len(st) for st in steps)
+    usual = [j for j, st in enumerate(steps) if len(st) == n]
+    if len(usual) < len(steps):
+        print(f"{len(steps) - len(usual)} of {len(steps)} steps have another launch count than {n}: not in the per-launch medians")
+    print("per launch (median over the steps): duration us | gap before it us")
+    for k in range(n):
+        d = statistics.median((steps[j][k][1] - steps[j][k][0]) / 1e3 for j in usual)
+        gaps = []
+        for j in usual:
+            prev_end = steps[j][k - 1][1] if k > 0 else (steps[j - 1][-1][1] if j > 0 else None)
+            if prev_end is not None:
+                gaps.append((steps[j][k][0] - prev_end) / 1e3)
+        print(f"  {k:2d} {steps[usual[0]][k][2]:34s} {d:8.2f} | {statistics.median(gaps):7.2f}  (max gap {max(gaps):7.2f})")
     for st in steps[-nshow:]:
         t0 = st[0][0]
         print("step:")
