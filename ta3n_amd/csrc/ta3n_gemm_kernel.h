@@ -718,7 +718,13 @@ __device__ __forceinline__ const float *base_ptr(const Ptrs &p, int base) {
 #define GSTAMP_VAL(i, v) do { if (threadIdx.x == 0 && blockIdx.x < 8192) GSTAMP_PTR[blockIdx.x * TA3N_STAMP_SLOTS + (i)] = (unsigned long long)(v); } while (0)
 // a value stamped by the second wave, which has no stamp stores of thread 0 in flight (stores count in vmcnt too)
 #define GSTAMP_W1(i, v) do { if (threadIdx.x == 64 && blockIdx.x < 8192) GSTAMP_PTR[blockIdx.x * TA3N_STAMP_SLOTS + (i)] = (unsigned long long)(v); } while (0)
-#define KSTAMP_DECL unsigned long long ks_wait = 0, ks_comp = 0, ks_t = 0; int ks_n = 0
+#define KSTAMP_DECL unsigned long long ks_wait = 0, ks_comp = 0, ks_t = 0, ks_bnd = 0, ks_int = 0, ks_mfull = 0, ks_mlast = 0, ks_m0 = 0; int ks_n = 0
+// Seg boundary (profiles/seg_boundary_stamps.txt): [12] barrier -> the stage's DMAs issued, on chunks that start the NEXT Seg's stream, [13] the same
+// on chunks that continue a Seg, [14] LDS reads + MFMAs of a FULL chunk, [15] of a Seg's last chunk that holds all CH k.  Each slot: cycles in
+// the low 40 bits, the number of stretches above them.
+#define KSTAMP_ISSUED(acc) do { acc += (__builtin_amdgcn_s_memtime() - ks_t) + (1ull << 40); } while (0)
+#define KSTAMP_COMP_BEGIN do { ks_m0 = __builtin_amdgcn_s_memtime(); } while (0)
+#define KSTAMP_COMP_DONE(acc) do { acc += (__builtin_amdgcn_s_memtime() - ks_m0) + (1ull << 40); } while (0)
 #define KSTAMP_BEGIN_WAIT do { ks_t = __builtin_amdgcn_s_memtime(); } while (0)
 #define KSTAMP_END_WAIT do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); ks_wait += n_ - ks_t; ks_t = n_; ++ks_n; } while (0)
 #define KSTAMP_END_COMP do { if (ks_t != 0) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); ks_comp += n_ - ks_t; } } while (0)
@@ -729,6 +735,13 @@ __device__ __forceinline__ const float *base_ptr(const Ptrs &p, int base) {
 #define KSTAMP_BEGIN_WAIT do { } while (0)
 #define KSTAMP_END_WAIT do { } while (0)
 #define KSTAMP_END_COMP do { } while (0)
+#define KSTAMP_ISSUED(acc) do { } while (0)
+#define KSTAMP_COMP_BEGIN do { } while (0)
+#define KSTAMP_COMP_DONE(acc) do { } while (0)
+#endif
+
+#ifndef TA3N_SEG_FAST
+#define TA3N_SEG_FAST 1      // gemm_tile: SEG_EARLY
 #endif
 
 namespace ta3n {
@@ -996,6 +1009,13 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     };
     static_assert(PF_IT == 0 || NS == 2, "the early requests are issued from the two-stage K loop (every kind-specialised backward kernel has two stages)");
 
+    // Seg boundaries of the kind-specialised twin kernels on two stages - the backward launches of the twin steps.  The general
+    // kernels and the experiments build keep the old sequence, as with EPI_EARLY; so do the three-stage forward kernels, whose issue cursor
+    // already opens a Seg behind a DMA, and the two kind kernels that round fp32 operands in registers: they hold 126 VGPRs, and the loop
+    // below takes them past 128, from two resident workgroups to one (profiles/seg_boundary_isa.txt).  -DTA3N_SEG_FAST=0 builds the old
+    // sequence everywhere (the "before" rows of profiles/seg_boundary_stamps.txt).
+    constexpr bool SEG_EARLY = TA3N_EXPERIMENTS == 0 && KV != 63 && (BF == 2 || BF == 4) && NS == 2 && (TA3N_SEG_FAST) != 0;
+
     f32x16 acc[RM][RN];
 #pragma unroll
     for (int i = 0; i < RM; ++i)
@@ -1024,7 +1044,114 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     constexpr int KVE = BM > 128 ? (KV & (1 | 2 | 32)) : KV;      // tiles taller than 128 rows: K-contiguous A only (the plan keeps them off other launches)
     auto k_loop = [&](auto akm, auto bkm, auto rsum) {
         constexpr bool AKM = decltype(akm)::value, BKM = decltype(bkm)::value, RS = decltype(rsum)::value;
-        if constexpr (NS == 2) {
+        if constexpr (SEG_EARLY) {
+            // Two stages, two cursors (as in the loop of three stages below): the issue cursor prepares the next Seg's stream state the
+            // moment it has sent a Seg's last chunk - under that chunk's flight, one chunk before the state is used - so no iteration has
+            // address arithmetic between its barrier and its DMA (the old loop: ~130 instructions, 0.26 us per boundary on the critical
+            // path of a gradient-at-F1 tile; profiles/seg_boundary_stamps.txt).  Same DMAs, same MFMAs on the same operands in the same order.
+            OperandStream<BM, NW, TW, PAIR, HS> oa;
+            OperandStream<BN, NW, TW, PAIR, HS> ob;
+            int i_seg = cseg, i_klen = 0, i_scale = SK_ONE, i_nchunks = 0, i_chunk = 0;
+            int p_klen = 0, p_scale = SK_ONE;        // (klen, scale) of the Seg the issue cursor left last: the compute cursor is in it or in the cursor's
+            Seg nx = t.seg0;                         // descriptor of the Seg the issue cursor opens next, fetched one Seg ahead ...
+            bool fetch = false;                      // ... by fetch_next, which the iteration that opened a Seg calls BEHIND its matrix instructions: a scalar
+                                                     // load in front of them is waited for with their LDS reads (one counter), and it comes from the L2
+            auto fetch_next = [&]() {
+                if (fetch) {
+                    if (i_seg + 1 < seg_end) nx = segs[i_seg + 1];
+                    fetch = false;
+                }
+            };
+            auto open_issue_seg = [&]() {            // wave-uniform: Seg fields live in SGPRs
+                const Seg sg = nx;
+                fetch = true;
+                i_klen = sg.klen; i_scale = sg.scale_kind; i_nchunks = (sg.klen + CH - 1) / CH; i_chunk = 0;
+                oa.setup(base_ptr(ptrs, sg.a_base) + (size_t)sg.a_off, sg.a_ld, AKM, sg.klen, m0, sg.pad[0] > 0 ? sg.pad[0] : m_valid,
+                         wave, lane, pair_delta);
+                ob.setup(base_ptr(ptrs, sg.b_base) + (size_t)sg.b_off, sg.b_ld, BKM, sg.klen, n0, n_valid, wave, lane, pair_delta);
+            };
+            auto issue_one = [&](int buf) {          // stream the chunk under the issue cursor, advance the cursor
+                const unsigned st = lds_base + (unsigned)(buf * STAGE * 4);
+                const int k0 = i_chunk * CH;
+                oa.issue(k0, i_klen - k0, st, wave, lane, zeros);
+                ob.issue(k0, i_klen - k0, st + BM * ROWF * 4, wave, lane, zeros);
+            };
+            auto advance = [&]() {                   // ... which opens the next Seg behind a Seg's last chunk
+                if (++i_chunk == i_nchunks) {
+                    p_klen = i_klen; p_scale = i_scale;
+                    if (++i_seg < seg_end) open_issue_seg();
+                }
+            };
+            auto stage_ready = [&]() {
+                KSTAMP_END_COMP;
+                KSTAMP_BEGIN_WAIT;
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the current stage have landed
+                __builtin_amdgcn_s_barrier();                        // ... everyone's; and everyone is done reading the other stage
+                asm volatile("" ::: "memory");
+                KSTAMP_END_WAIT;
+            };
+            auto scale_acc = [&](int kind) {
+                if (kind != SK_ONE) {
+                    const float sc = scale_of(kind);
+    #pragma unroll
+                    for (int i = 0; i < RM; ++i)
+    #pragma unroll
+                        for (int j = 0; j < RN; ++j)
+    #pragma unroll
+                            for (int r = 0; r < 16; ++r) acc[i][j][r] *= sc;
+                }
+            };
+            int buf = 0;
+            open_issue_seg();
+            fetch_next();
+            issue_one(0);
+            advance();
+            fetch_next();
+            if constexpr (PF_IT > 0) request_epilogue_operands();
+            for (;;) {
+                // the issue cursor is one chunk ahead: in this Seg, or - having sent its only or last chunk - in the next one
+                const int klen = i_seg == cseg ? i_klen : p_klen, c_scale = i_seg == cseg ? i_scale : p_scale;
+                // The Seg's full chunks run one body, whatever follows them - a chunk of this Seg, the first chunk of the next, or nothing;
+                // a K tail runs the body with the skip tests.  (The parent ran that body on EVERY Seg's last chunk: in a gradient-at-F1
+                // tile, whose Segs are two full chunks, on every second one.)
+                const int n_full = klen / CH, tail = klen - n_full * CH;
+                for (int c = 0; c < n_full; ++c) {
+                    stage_ready();
+                    const float *sa = lds + buf * STAGE;
+                    if (i_seg < seg_end) {                          // the issue cursor has not run off the task's last Seg
+#ifdef TA3N_GEMM_STAMPS
+                        const bool ks_first = i_chunk == 0;
+#endif
+                        issue_one(buf ^ 1);
+#ifdef TA3N_GEMM_STAMPS
+                        if (ks_first) KSTAMP_ISSUED(ks_bnd); else KSTAMP_ISSUED(ks_int);
+#endif
+                        advance();
+                    }
+                    KSTAMP_COMP_BEGIN;
+                    compute_stage<BM, BN, WK, AKM, BKM, true, RS, BF, RM, RN>(acc, rs, sa, sa + BM * ROWF, ra, rb, wk, lh, CH);
+#ifdef TA3N_GEMM_STAMPS
+                    if (c + 1 < n_full || tail) KSTAMP_COMP_DONE(ks_mfull); else KSTAMP_COMP_DONE(ks_mlast);
+#endif
+                    fetch_next();
+                    buf ^= 1;
+                }
+                if (tail) {
+                    stage_ready();
+                    const float *sa = lds + buf * STAGE;
+                    if (i_seg < seg_end) {
+                        issue_one(buf ^ 1);
+                        KSTAMP_ISSUED(ks_bnd);
+                        advance();
+                    }
+                    compute_stage<BM, BN, WK, AKM, BKM, false, RS, BF, RM, RN>(acc, rs, sa, sa + BM * ROWF, ra, rb, wk, lh, tail);
+                    fetch_next();
+                    buf ^= 1;
+                }
+                scale_acc(c_scale);
+                if (++cseg >= seg_end) break;
+            }
+        } else if constexpr (NS == 2) {
             // Two stages: chunk c + 1 is streamed while chunk c is computed.  Per Seg, the iterations whose successor is in
             // the same Seg run in a tight loop; the iteration that computes the Seg's last chunk opens the next Seg.
             OperandStream<BM, NW, TW, PAIR, HS> oa;
@@ -1065,7 +1192,10 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
                     stage_ready();
                     const float *sa = lds + buf * STAGE;
                     issue(buf ^ 1, (c + 1) * CH);
+                    KSTAMP_ISSUED(ks_int);
+                    KSTAMP_COMP_BEGIN;
                     compute_stage<BM, BN, WK, AKM, BKM, true, RS, BF, RM, RN>(acc, rs, sa, sa + BM * ROWF, ra, rb, wk, lh, CH);
+                    KSTAMP_COMP_DONE(ks_mfull);
                     buf ^= 1;
                 }
                 // last chunk of this Seg; the next Seg (if any) starts streaming underneath it
@@ -1076,9 +1206,12 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
                 if (more) {
                     open_seg(cseg);
                     issue(buf ^ 1, 0);
+                    KSTAMP_ISSUED(ks_bnd);
                 }
                 const float *sa = lds + buf * STAGE;
+                KSTAMP_COMP_BEGIN;
                 compute_stage<BM, BN, WK, AKM, BKM, false, RS, BF, RM, RN>(acc, rs, sa, sa + BM * ROWF, ra, rb, wk, lh, krem);
+                if (krem == CH) KSTAMP_COMP_DONE(ks_mlast);
                 if (c_scale != SK_ONE) {
                     const float sc = scale_of(c_scale);
     #pragma unroll
@@ -1152,7 +1285,10 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
                         const float *sa = lds + c_buf * STAGE;
                         oa.issue(k0, klen - k0, st, wave, lane, zeros);
                         ob.issue(k0, klen - k0, st + BM * ROWF * 4, wave, lane, zeros);
+                        KSTAMP_ISSUED(ks_int);
+                        KSTAMP_COMP_BEGIN;
                         compute_stage<BM, BN, WK, AKM, BKM, true, RS, BF, RM, RN>(acc, rs, sa, sa + BM * ROWF, ra, rb, wk, lh, CH);
+                        KSTAMP_COMP_DONE(ks_mfull);
                         i_buf = (i_buf + 1 == NS) ? 0 : i_buf + 1;
                         c_buf = (c_buf + 1 == NS) ? 0 : c_buf + 1;
                     }
@@ -1163,12 +1299,26 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     #pragma unroll 1
                 for (; c < n_chunks; ++c) {
                     wait_landed(ahead - 1);
+#ifdef TA3N_GEMM_STAMPS
+                    const bool ks_first = i_chunk == 0;      // this iteration starts a Seg's stream
+                    const int ks_ahead = ahead;
+#endif
                     if (i_seg < seg_end) issue_one();
+#ifdef TA3N_GEMM_STAMPS
+                    if (ahead == ks_ahead) { }
+                    else if (ks_first) KSTAMP_ISSUED(ks_bnd);
+                    else KSTAMP_ISSUED(ks_int);
+#endif
                     const float *sa = lds + c_buf * STAGE;
+                    KSTAMP_COMP_BEGIN;
                     if (c < n_chunks - 1)
                         compute_stage<BM, BN, WK, AKM, BKM, true, RS, BF, RM, RN>(acc, rs, sa, sa + BM * ROWF, ra, rb, wk, lh, CH);
                     else
                         compute_stage<BM, BN, WK, AKM, BKM, false, RS, BF, RM, RN>(acc, rs, sa, sa + BM * ROWF, ra, rb, wk, lh, klen - c * CH);
+#ifdef TA3N_GEMM_STAMPS
+                    if (c < n_chunks - 1) KSTAMP_COMP_DONE(ks_mfull);
+                    else if (klen - c * CH == CH) KSTAMP_COMP_DONE(ks_mlast);
+#endif
                     c_buf = (c_buf + 1 == NS) ? 0 : c_buf + 1;
                     --ahead;
                 }
@@ -1205,6 +1355,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     GSTAMP(2);
 #ifdef TA3N_GEMM_STAMPS
     GSTAMP_VAL(8, ks_wait); GSTAMP_VAL(9, ks_comp); GSTAMP_VAL(10, ks_n);
+    GSTAMP_VAL(12, ks_bnd); GSTAMP_VAL(13, ks_int); GSTAMP_VAL(14, ks_mfull); GSTAMP_VAL(15, ks_mlast);
 #endif
     __syncthreads();
     GSTAMP(3);

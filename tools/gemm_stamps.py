@@ -3,7 +3,9 @@
     TA3N_LIBDIR=$PWD/ta3n_amd/lib_stamps python tools/gemm_stamps.py [bf16|f32] [config 2|4|5]
 ): per-workgroup s_memtime stamps of every GEMM launch of the fused step - entry / descriptors loaded / K loop done / epilogue done,
 and inside the K loop the time thread 0 spends WAITING for a stage (s_waitcnt + s_barrier) against the time it spends issuing the next
-stage's DMA, LDS reads and MFMAs - printed per launch and per tile length: where a launch's time goes.  TA3N_KIND_KERNELS=0 runs the
+stage's DMA, LDS reads and MFMAs - printed per launch and per tile length: where a launch's time goes; and around a Seg boundary: from the
+barrier to the stage's DMAs issued on chunks that start a Seg's stream against chunks inside a Seg, and the LDS reads + MFMAs of a Seg's last
+chunk against an interior one (-DTA3N_SEG_FAST=0 beside -DTA3N_GEMM_STAMPS builds the old boundary sequence).  TA3N_KIND_KERNELS=0 runs the
 general kernels, which request a tile's residual and mask inside the store loop; the default runs the kind-specialised ones."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,3 +59,9 @@ for i, ph in enumerate(phases):
               f"{np.mean(ns):.1f} stages -> {np.mean(st[m, 8] / ns) * TICK * 1e3:5.0f} + {np.mean(st[m, 9] / ns) * TICK * 1e3:5.0f} ns per stage)  wait-waves {d(3, 2):5.2f}  to-lds {d(4, 3):5.2f}  "
               f"combine+store {d(5, 4):5.2f} (second wave, first pass: LDS sum and global operands there {d(11, 4):5.2f} after [4])"
               f"  | finish {np.mean(st[m, 5] - t0) * TICK:6.2f} us")
+        # Seg boundary stamps (slots 12 - 15: cycles in the low 40 bits, stretches counted above them): ns per stretch over the class
+        def per(slot):
+            cyc, cnt = (st[m, slot] & ((1 << 40) - 1)).sum(), (st[m, slot] >> 40).sum()
+            return f"{cyc / cnt * TICK * 1e3:4.0f} ns x{cnt / m.sum():4.1f}" if cnt else "   - "
+        print(f"          {np.mean(st[m, 7]):4.1f} Segs | barrier -> stage's DMAs issued: starting a Seg {per(12)}, inside a Seg {per(13)} | LDS reads + MFMAs: "
+              f"FULL chunk {per(14)}, a Seg's last chunk that holds a whole chunk {per(15)}")
