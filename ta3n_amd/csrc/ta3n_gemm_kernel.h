@@ -718,6 +718,13 @@ __device__ __forceinline__ const float *base_ptr(const Ptrs &p, int base) {
 #define GSTAMP_VAL(i, v) do { if (threadIdx.x == 0 && blockIdx.x < 8192) GSTAMP_PTR[blockIdx.x * TA3N_STAMP_SLOTS + (i)] = (unsigned long long)(v); } while (0)
 // a value stamped by the second wave, which has no stamp stores of thread 0 in flight (stores count in vmcnt too)
 #define GSTAMP_W1(i, v) do { if (threadIdx.x == 64 && blockIdx.x < 8192) GSTAMP_PTR[blockIdx.x * TA3N_STAMP_SLOTS + (i)] = (unsigned long long)(v); } while (0)
+// Front of the tile (profiles/task_front_stamps.txt), thread 0, cycles since [0], 16 bits each: first Task word there / per-step scalars there (kernels
+// that wait for them in the front; the others stamp without waiting) / bias requested / first stage's (stages') DMAs issued.  They share slots with two
+// small values: [6] = cost | f0 << 24 | f1 << 40, [7] = Seg count | f2 << 16 | f3 << 32.  Store pass, second wave: [11] = low 48 bits of the old stamp |
+// cycles since "Task fields and scalars of the store loop in registers, nothing of the pass read yet" << 48.
+#define FSTAMP_DECL unsigned long long ks_f0 = __builtin_amdgcn_s_memtime(), ks_f[4] = {0, 0, 0, 0}, ks_e = 0
+#define FSTAMP(i, dep) do { asm volatile("" ::"s"(dep)); ks_f[i] = (__builtin_amdgcn_s_memtime() - ks_f0) & 0xFFFFull; } while (0)
+#define ESTAMP(a, b, c) do { asm volatile("" ::"s"(a), "s"(b), "s"(c)); ks_e = __builtin_amdgcn_s_memtime(); } while (0)
 #define KSTAMP_DECL unsigned long long ks_wait = 0, ks_comp = 0, ks_t = 0, ks_bnd = 0, ks_int = 0, ks_mfull = 0, ks_mlast = 0, ks_m0 = 0; int ks_n = 0
 // Seg boundary (profiles/seg_boundary_stamps.txt): [12] barrier -> the stage's DMAs issued, on chunks that start the NEXT Seg's stream, [13] the same
 // on chunks that continue a Seg, [14] LDS reads + MFMAs of a FULL chunk, [15] of a Seg's last chunk that holds all CH k.  Each slot: cycles in
@@ -731,6 +738,9 @@ __device__ __forceinline__ const float *base_ptr(const Ptrs &p, int base) {
 #else
 #define GSTAMP(i) do { } while (0)
 #define GSTAMP_VAL(i, v) do { } while (0)
+#define FSTAMP_DECL ((void)0)      // (no statement of their own: an empty loop is a basic block, and the kernels without stamps compile as they did)
+#define FSTAMP(i, dep) ((void)0)
+#define ESTAMP(a, b, c) ((void)0)
 #define KSTAMP_DECL do { } while (0)
 #define KSTAMP_BEGIN_WAIT do { } while (0)
 #define KSTAMP_END_WAIT do { } while (0)
@@ -743,6 +753,17 @@ __device__ __forceinline__ const float *base_ptr(const Ptrs &p, int base) {
 #ifndef TA3N_SEG_FAST
 #define TA3N_SEG_FAST 1      // gemm_tile: SEG_EARLY
 #endif
+#ifndef TA3N_TASK_FAST
+#define TA3N_TASK_FAST 1     // gemm_tile: TASK_LANES (0: the Task is read field by field, where it is used - A/B builds in ta3n_amd/lib_ab)
+#endif
+
+// A Task field / array element / per-step scalar of gemm_tile.  Kernels that hold the descriptor in lanes (TASK_LANES: lane i of `tv` is
+// dword i of the Task, lane i of `hv` dword i of Hyper) select the lane into an SGPR at the use; the others read memory, as they always did.
+// The switch is a constant, so each kernel contains one of the two forms.
+#define TASK_F(f) (TASK_LANES ? static_cast<decltype(t.f)>(__builtin_amdgcn_readlane(tv, (int)(offsetof(Task, f) / 4))) : t.f)
+#define TASK_A(a, i) (TASK_LANES ? __builtin_amdgcn_readlane(tv, (int)(offsetof(Task, a) / 4) + (i)) : t.a[i])
+#define HYPER_F(f) (TASK_LANES ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(hv, (int)(offsetof(Hyper, f) / 4))) : hh.f)
+#define HYPER_U(f) (TASK_LANES ? (uint32_t)__builtin_amdgcn_readlane(hv, (int)(offsetof(Hyper, f) / 4)) : hh.f)
 
 namespace ta3n {
 
@@ -778,9 +799,37 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     const int wk = wave % WK, wn = (wave / WK) % WN, wm = wave / (WK * WN);
 
     GSTAMP(0);
+    FSTAMP_DECL;
+    // The descriptor and the per-step scalars in lanes: the kind-specialised kernels of the default library (scoped as EPI_EARLY and
+    // SEG_EARLY are; -DTA3N_TASK_FAST=0 builds the old reads everywhere) fetch the whole Task with ONE vector load - lane i of every wave
+    // takes dword i - and the first 20 dwords of Hyper (through `train`) with a second one in the same issue group; both addresses follow
+    // from the kernel arguments alone.  A field is then a v_readlane at its use (TASK_F / TASK_A / HYPER_F), in the front, between Segs
+    // and in the epilogue: no access to the Task reaches memory again.  Read field by field through `const Task &`, the descriptor cost
+    // the tile a dozen dependent scalar round trips in front of its first DMA and another series behind the K loop, and `train` a
+    // vector round trip of its own in front of everything else (profiles/task_front_isa.txt, profiles/task_front_stamps.txt).
+    constexpr bool TASK_LANES = TA3N_EXPERIMENTS == 0 && KV != 63 && (TA3N_TASK_FAST) != 0;
+    static_assert(sizeof(Task) == 200 && sizeof(Task) / 4 <= 64, "a Task is 50 dwords: one per lane of a wave");
+    static_assert(offsetof(Hyper, train) / 4 == 19, "the per-step scalars the tiles use are the first 20 dwords of Hyper");
+    int tv = 0, hv = 0;
+    if constexpr (TASK_LANES) {
+        __builtin_memcpy(&tv, reinterpret_cast<const char *>(&t) + 4 * (lane < (int)(sizeof(Task) / 4) ? lane : 0), 4);
+        __builtin_memcpy(&hv, reinterpret_cast<const char *>(ptrs.ws + hyper_off) + 4 * (lane < 20 ? lane : 0), 4);
+        // Both are waited for HERE, once, before the first field is looked at - they were issued back to back and arrive together.  Left to its
+        // first use, `hv` is waited for by the compiler with `s_waitcnt vmcnt(0)` behind the first scaled Seg INSIDE the K loop, which waits for
+        // the stages in flight as well: measured, the forward launches' K loops grew by 0.1 - 0.5 us per tile (profiles/task_front_stamps.txt).
+        asm volatile("" ::"v"(tv), "v"(hv));
+    }
+    FSTAMP(0, TASK_F(epi));
+    auto task_seg0 = [&]() -> Seg {      // TASK_LANES: the Task's copy of its first Seg (what of it is not used costs nothing)
+        Seg s;
+        s.a_base = TASK_F(seg0.a_base); s.b_base = TASK_F(seg0.b_base); s.a_off = TASK_F(seg0.a_off); s.b_off = TASK_F(seg0.b_off);
+        s.a_ld = TASK_F(seg0.a_ld); s.b_ld = TASK_F(seg0.b_ld); s.a_kmajor = TASK_F(seg0.a_kmajor); s.b_kmajor = TASK_F(seg0.b_kmajor);
+        s.klen = TASK_F(seg0.klen); s.scale_kind = TASK_F(seg0.scale_kind); s.pad[0] = TASK_A(seg0.pad, 0); s.pad[1] = TASK_A(seg0.pad, 1);
+        return s;
+    };
     constexpr bool OPT = TA3N_EXPERIMENTS != 0 && (KV & 32) != 0;      // fused update / split-K / chained-launch stores compiled in (experiments build only)
-    const bool pub = OPT && t.sig >= 0 && !(side.p16_off == -12345);    // chained launch: another task of this launch reads what this one writes -> write-through stores
-    if (t.epi & EPI_SGD) {          // optimiser side job (uniform for the workgroup): arithmetic and summation order of sgd_range_kernel
+    const bool pub = OPT && TASK_F(sig) >= 0 && !(side.p16_off == -12345);    // chained launch: another task of this launch reads what this one writes -> write-through stores
+    if (TASK_F(epi) & EPI_SGD) {          // optimiser side job (uniform for the workgroup): arithmetic and summation order of sgd_range_kernel
         if (side.params == nullptr) return;   // launched without an update to apply (ta3n_time_phases)
         float part = 0.f;
         if (tid < 256)
@@ -793,7 +842,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         float4 *__restrict__ p4 = reinterpret_cast<float4 *>(side.params);
         float4 *__restrict__ m4 = reinterpret_cast<float4 *>(side.momentum);
         const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(ptrs.g);
-        for (int i = t.pad[0] + tid; i < t.pad[1]; i += NT) {
+        for (int i = TASK_A(pad, 0) + tid; i < TASK_A(pad, 1); i += NT) {
             const float4 p = p4[i], m = m4[i], gr = g4[i];
             float gg[4] = {gr.x, gr.y, gr.z, gr.w}, pp[4] = {p.x, p.y, p.z, p.w}, mm[4] = {m.x, m.y, m.z, m.w};
 #pragma unroll
@@ -815,17 +864,17 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         }
         return;
     }
-    if (t.epi & EPI_COLSUM) {       // exact column sums of a [rows][ld] table of partials (uniform for the workgroup)
-        float *__restrict__ dst = const_cast<float *>(base_ptr(ptrs, t.c_base)) + (size_t)t.c_off;
-        const float *__restrict__ src = ptrs.ws + t.pad[0];
+    if (TASK_F(epi) & EPI_COLSUM) {       // exact column sums of a [rows][ld] table of partials (uniform for the workgroup)
+        float *__restrict__ dst = const_cast<float *>(base_ptr(ptrs, TASK_F(c_base))) + (size_t)TASK_F(c_off);
+        const float *__restrict__ src = ptrs.ws + TASK_A(pad, 0);
         float sq = 0.f;
-        for (int n = t.n0 + tid; n < t.n_valid; n += NT) {
+        for (int n = TASK_F(n0) + tid; n < TASK_F(n_valid); n += NT) {
             float v = 0.f;
             // rows added in order, EIGHT loads in flight per round trip (the plain loop compiled to load - s_waitcnt vmcnt(0) - add per
             // row: 32 - 72 dependent L2 round trips, longer than every tile of the launch this task rides in; ISA pass of round 5)
             const float *__restrict__ col = src + n;
-            const int R = t.pad[1];
-            const size_t ld = (size_t)t.pad[2];
+            const int R = TASK_A(pad, 1);
+            const size_t ld = (size_t)TASK_A(pad, 2);
             int r = 0;
 #pragma unroll 1
             for (; r + 8 <= R; r += 8) {
@@ -838,69 +887,76 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             for (; r < R; ++r) v += col[(size_t)r * ld];
             dst[n] = v;
             sq = fmaf(v, v, sq);
-            if (OPT && side.p_new != nullptr && t.c_base == BASE_G) {     // fused update of these parameters (see the tile epilogue)
-                const size_t pi = (size_t)t.c_off + n;
+            if (OPT && side.p_new != nullptr && TASK_F(c_base) == BASE_G) {     // fused update of these parameters (see the tile epilogue)
+                const size_t pi = (size_t)TASK_F(c_off) + n;
                 float p1 = ptrs.p[pi], mm = side.momentum[pi];
                 nesterov_sgd(p1, mm, v, side.lr, side.mu, side.wd);
                 side.p_new[pi] = p1; side.momentum[pi] = mm;
                 if (side.p16_new != nullptr) reinterpret_cast<unsigned short *>(side.p16_new)[pi] = (unsigned short)(pack_bf16(p1, 0.f) & 0xFFFF);
             }
         }
-        if (t.epi & EPI_SUMSQ) {
+        if (TASK_F(epi) & EPI_SUMSQ) {
             sq = wave_allreduce_sum(sq);
             if (lane == 0) lds[wave] = sq;
             __syncthreads();
             if (tid == 0) {
                 float tot = 0.f;
                 for (int i = 0; i < NW; ++i) tot += lds[i];
-                ptrs.ws[t.pad[3]] = tot;
+                ptrs.ws[TASK_A(pad, 3)] = tot;
             }
         }
         return;
     }
-    if (t.seg_count == 0) return;   // padding task of the XCD-aware ordering (uniform for the workgroup)
-    if (t.epi & EPI_SUMROWS8) {   // side job of one workgroup per fused step: add up the heads kernel's loss partials in a fixed order
-        const float *__restrict__ src = ptrs.ws + t.pad[1];
+    if (TASK_F(seg_count) == 0) return;   // padding task of the XCD-aware ordering (uniform for the workgroup)
+    if (TASK_F(epi) & EPI_SUMROWS8) {   // side job of one workgroup per fused step: add up the heads kernel's loss partials in a fixed order
+        const float *__restrict__ src = ptrs.ws + TASK_A(pad, 1);
         float sacc = 0.f;
-        for (int r = tid >> 3; r < t.pad[2]; r += NT / 8) sacc += src[r * 8 + (tid & 7)];
+        for (int r = tid >> 3; r < TASK_A(pad, 2); r += NT / 8) sacc += src[r * 8 + (tid & 7)];
         lds[tid] = sacc;
         __syncthreads();
         if (tid < 8) {
             float v = 0.f;
             for (int i = 0; i < NT / 8; ++i) v += lds[i * 8 + tid];
-            ptrs.ws[t.pad[0] + tid] = v;
+            ptrs.ws[TASK_A(pad, 0) + tid] = v;
         }
         __syncthreads();
     }
     const Hyper *__restrict__ hy = reinterpret_cast<const Hyper *>(ptrs.ws + hyper_off);
     const float *__restrict__ zeros = ptrs.ws + zeros_off;   // 64 floats that are never written
-    // What the epilogue needs that does not depend on the accumulators is REQUESTED now and consumed after the K loop:
-    // the per-step scalars (one unconditional block load, independent of the Task - it travels beside the descriptor
-    // instead of behind it; which of them the tile uses is decided in the epilogue) and this thread's four bias entries
-    // (its column group is the same in every epilogue iteration).
-    const uint32_t epi = t.epi;
+    // What the epilogue needs that does not depend on the accumulators is REQUESTED ahead of the K loop and consumed after it: the
+    // per-step scalars and this thread's four bias entries (its column group is the same in every epilogue iteration).
+    // The scalars: with the descriptor in lanes (TASK_LANES) they are the register `hv`, requested at kernel entry in the Task's issue
+    // group and there since the Task is.  The other kernels read them here - the first 12 dwords as a block of scalar loads and `train`
+    // by a load of its own, which the compiler issues as a vector load and waits for (a round trip of its own) in front of the bias.
+    // The bias keeps its place in front of the first stage in every kernel: requested behind the first stages' issue - where EPI_EARLY
+    // puts the residual and the mask - it cost the step 1.3 us (its loads stand between the stages' DMAs in the one counter the
+    // three-stage loop's counted waits use).
+    const uint32_t epi = TASK_F(epi);
     struct HyperHead { float beta[3], gamma, lr, momentum, weight_decay, clip, p_drop_i, p_drop_v; uint32_t seed_i, seed_v; };
-    const HyperHead hh = *reinterpret_cast<const HyperHead *>(hy);      // first 12 dwords of Hyper (ta3n_types.h)
-    const int h_train = hy->train;
+    const HyperHead hh = TASK_LANES ? HyperHead{} : *reinterpret_cast<const HyperHead *>(hy);      // first 12 dwords of Hyper (ta3n_types.h)
+    const int h_train_mem = TASK_LANES ? 0 : hy->train;
+#define HYPER_TRAIN (TASK_LANES ? __builtin_amdgcn_readlane(hv, (int)(offsetof(Hyper, train) / 4)) : h_train_mem)
+    FSTAMP(1, TASK_LANES ? 0 : h_train_mem);
     auto scale_of = [&](int kind) -> float {
         switch (kind) {
-            case SK_NEG_BETA_REL: return -hh.beta[0];
-            case SK_NEG_BETA_VID: return -hh.beta[1];
-            case SK_NEG_BETA_FRM: return -hh.beta[2];
-            case SK_INV_KEEP_I: return (h_train && hh.p_drop_i > 0.f) ? (hh.p_drop_i < 1.f ? 1.f / (1.f - hh.p_drop_i) : 0.f) : 1.f;
-            case SK_INV_KEEP_V: return (h_train && hh.p_drop_v > 0.f) ? (hh.p_drop_v < 1.f ? 1.f / (1.f - hh.p_drop_v) : 0.f) : 1.f;
+            case SK_NEG_BETA_REL: return -HYPER_F(beta[0]);
+            case SK_NEG_BETA_VID: return -HYPER_F(beta[1]);
+            case SK_NEG_BETA_FRM: return -HYPER_F(beta[2]);
+            case SK_INV_KEEP_I: return (HYPER_TRAIN && HYPER_F(p_drop_i) > 0.f) ? (HYPER_F(p_drop_i) < 1.f ? 1.f / (1.f - HYPER_F(p_drop_i)) : 0.f) : 1.f;
+            case SK_INV_KEEP_V: return (HYPER_TRAIN && HYPER_F(p_drop_v) > 0.f) ? (HYPER_F(p_drop_v) < 1.f ? 1.f / (1.f - HYPER_F(p_drop_v)) : 0.f) : 1.f;
             case SK_REVERSE_MU: return hy->reverse ? -hy->mu : 1.f;      // (read here: only the one tile kind that needs it pays the load)
             default: return 1.f;
         }
     };
     float ebias[4] = {0.f, 0.f, 0.f, 0.f};
     if (epi & EPI_BIAS) {
-        const float *__restrict__ bias = base_ptr(ptrs, t.bias_base) + t.bias_off;
-        const int n = t.n0 + (tid % (BN / 4)) * 4;
+        const float *__restrict__ bias = base_ptr(ptrs, TASK_F(bias_base)) + TASK_F(bias_off);
+        const int n = TASK_F(n0) + (tid % (BN / 4)) * 4;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            if (n + e < t.n_valid) ebias[e] = bias[n + e];
+            if (n + e < TASK_F(n_valid)) ebias[e] = bias[n + e];
     }
+    FSTAMP(2, 0);
 
     // Fused update (SgdSide::p_new, gradient tiles only): the old parameter and momentum entries this thread will update are
     // requested NOW, like the bias, and consumed in the epilogue - in the epilogue itself the two dependent loads were ~1.5 us on
@@ -908,16 +964,16 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     // 128-wide tiles) load them in the epilogue instead: 8 registers per pass are too many to carry through the K loop.
     constexpr int ITER_E = (BM * BN / 4 + NT - 1) / NT;
     constexpr bool UPD_PREFETCH = ITER_E <= 2;
-    const bool upd_early = OPT && UPD_PREFETCH && side.p_new != nullptr && t.c_base == BASE_G;
+    const bool upd_early = OPT && UPD_PREFETCH && side.p_new != nullptr && TASK_F(c_base) == BASE_G;
     float up_e[UPD_PREFETCH ? ITER_E : 1][4], um_e[UPD_PREFETCH ? ITER_E : 1][4];
     if (upd_early) {
-        const bool cv = ((t.c_off | t.c_ld) & 3) == 0;
+        const bool cv = ((TASK_F(c_off) | TASK_F(c_ld)) & 3) == 0;
 #pragma unroll
         for (int it = 0; it < (UPD_PREFETCH ? ITER_E : 1); ++it) {
             const int idx = tid + it * NT;
-            const int mm_ = t.m0 + idx / (BN / 4), nn_ = t.n0 + (idx % (BN / 4)) * 4;
-            const int nr_ = (idx < BM * BN / 4 && mm_ < t.m_valid) ? t.n_valid - nn_ : 0;
-            const size_t pi = (size_t)t.c_off + (size_t)mm_ * t.c_ld + nn_;
+            const int mm_ = TASK_F(m0) + idx / (BN / 4), nn_ = TASK_F(n0) + (idx % (BN / 4)) * 4;
+            const int nr_ = (idx < BM * BN / 4 && mm_ < TASK_F(m_valid)) ? TASK_F(n_valid) - nn_ : 0;
+            const size_t pi = (size_t)TASK_F(c_off) + (size_t)mm_ * TASK_F(c_ld) + nn_;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { up_e[it][e] = 0.f; um_e[it][e] = 0.f; }
             if (nr_ >= 4 && cv) {
@@ -957,9 +1013,9 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     constexpr bool PF_FAN = PF_IT == 1;                                 // ... and whose fan masks are
     struct EpiOperands { const float *aux, *add; bool aux_vec, add_vec; int nfan; };      // workgroup-uniform
     auto epi_operands = [&]() {      // (called at the request by the kernels that request early, behind the K loop by the others: nothing of it lives through their loop)
-        return EpiOperands{(epi & EPI_MASK) ? base_ptr(ptrs, t.aux_base) + t.aux_off : nullptr,
-                           (epi & EPI_ADD) ? base_ptr(ptrs, t.add_base) + t.add_off : nullptr,
-                           ((t.aux_off | t.aux_ld) & 3) == 0, ((t.add_off | t.add_ld) & 3) == 0, t.fan_count};
+        return EpiOperands{(epi & EPI_MASK) ? base_ptr(ptrs, TASK_F(aux_base)) + TASK_F(aux_off) : nullptr,
+                           (epi & EPI_ADD) ? base_ptr(ptrs, TASK_F(add_base)) + TASK_F(add_off) : nullptr,
+                           ((TASK_F(aux_off) | TASK_F(aux_ld)) & 3) == 0, ((TASK_F(add_off) | TASK_F(add_ld)) & 3) == 0, TASK_F(fan_count)};
     };
     auto epi_fetch4 = [](float (&o)[4], const float *__restrict__ p, int nrem, bool vec) {   // o keeps its defaults where nothing is read
         if (nrem >= 4 && vec) { const float4 q4 = *reinterpret_cast<const float4 *>(p); o[0] = q4.x; o[1] = q4.y; o[2] = q4.z; o[3] = q4.w; }
@@ -969,16 +1025,16 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         }
     };
     auto fetch_add_aux = [&](const EpiOperands &eo, float (&av)[4], float (&mv)[4], int m, int n, int nrem) {      // nrem <= 0: nothing is read
-        if (eo.add != nullptr && nrem > 0) epi_fetch4(av, eo.add + (size_t)m * t.add_ld + n, nrem, eo.add_vec);
-        if (eo.aux != nullptr && nrem > 0) epi_fetch4(mv, eo.aux + (size_t)m * t.aux_ld + n, nrem, eo.aux_vec);
+        if (eo.add != nullptr && nrem > 0) epi_fetch4(av, eo.add + (size_t)m * TASK_F(add_ld) + n, nrem, eo.add_vec);
+        if (eo.aux != nullptr && nrem > 0) epi_fetch4(mv, eo.aux + (size_t)m * TASK_F(aux_ld) + n, nrem, eo.aux_vec);
     };
     auto fetch_fan = [&](const EpiOperands &eo, float (&fm)[3][4], int m, int n, int nrem) {      // all mask loads of a fan-out tile
         if (eo.nfan > 0 && nrem > 0) {
-            const bool fan_vec = (t.fan_ld & 3) == 0;
+            const bool fan_vec = (TASK_F(fan_ld) & 3) == 0;
 #pragma unroll
             for (int f = 0; f < 3; ++f)
                 if (f < eo.nfan)
-                    epi_fetch4(fm[f], ptrs.ws + (size_t)t.fan_mask_off[f] + (size_t)m * t.fan_ld + n, nrem, fan_vec && (t.fan_mask_off[f] & 3) == 0);
+                    epi_fetch4(fm[f], ptrs.ws + (size_t)TASK_A(fan_mask_off, f) + (size_t)m * TASK_F(fan_ld) + n, nrem, fan_vec && (TASK_A(fan_mask_off, f) & 3) == 0);
         }
     };
     EpiOperands eo_early{nullptr, nullptr, false, false, 0};
@@ -993,8 +1049,8 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
 #pragma unroll
         for (int it = 0; it < PF_IT; ++it) {
             const int idx = tid + it * NT;
-            const int mm_ = t.m0 + idx / (BN / 4), nn_ = t.n0 + (idx % (BN / 4)) * 4;
-            const int nr_ = (idx < BM * BN / 4 && mm_ < t.m_valid) ? t.n_valid - nn_ : 0;      // the store loop's nrem
+            const int mm_ = TASK_F(m0) + idx / (BN / 4), nn_ = TASK_F(n0) + (idx % (BN / 4)) * 4;
+            const int nr_ = (idx < BM * BN / 4 && mm_ < TASK_F(m_valid)) ? TASK_F(n_valid) - nn_ : 0;      // the store loop's nrem
 #pragma unroll
             for (int e = 0; e < 4; ++e) { add_e[it][e] = 0.f; aux_e[it][e] = 1.f; }
             fetch_add_aux(eo_early, add_e[it], aux_e[it], mm_, nn_, nr_);
@@ -1025,9 +1081,9 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     GSTAMP(1);
 
-    const int m0 = t.m0, n0 = t.n0, m_valid = t.m_valid, n_valid = t.n_valid;
-    const int seg_end = t.seg_begin + t.seg_count;
-    int cseg = t.seg_begin;
+    const int m0 = TASK_F(m0), n0 = TASK_F(n0), m_valid = TASK_F(m_valid), n_valid = TASK_F(n_valid);
+    const int seg_end = TASK_F(seg_begin) + TASK_F(seg_count);
+    int cseg = TASK_F(seg_begin);
     // K loop: NS stages, chunk c + NS - 1 is streamed while chunk c is computed, across Seg boundaries.  All Segs of a
     // task have the same operand kinds (the plan builder guarantees it), so the whole loop nest is instantiated per
     // kind combination and selected once per task: the register allocation is the maximum over the combinations,
@@ -1053,7 +1109,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             OperandStream<BN, NW, TW, PAIR, HS> ob;
             int i_seg = cseg, i_klen = 0, i_scale = SK_ONE, i_nchunks = 0, i_chunk = 0;
             int p_klen = 0, p_scale = SK_ONE;        // (klen, scale) of the Seg the issue cursor left last: the compute cursor is in it or in the cursor's
-            Seg nx = t.seg0;                         // descriptor of the Seg the issue cursor opens next, fetched one Seg ahead ...
+            Seg nx = TASK_LANES ? task_seg0() : t.seg0;                         // descriptor of the Seg the issue cursor opens next, fetched one Seg ahead ...
             bool fetch = false;                      // ... by fetch_next, which the iteration that opened a Seg calls BEHIND its matrix instructions: a scalar
                                                      // load in front of them is waited for with their LDS reads (one counter), and it comes from the L2
             auto fetch_next = [&]() {
@@ -1107,6 +1163,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             issue_one(0);
             advance();
             fetch_next();
+            FSTAMP(3, 0);
             if constexpr (PF_IT > 0) request_epilogue_operands();
             for (;;) {
                 // the issue cursor is one chunk ahead: in this Seg, or - having sent its only or last chunk - in the next one
@@ -1160,7 +1217,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             // The descriptor of the NEXT Seg is fetched while the current one streams (scalar loads, consumed at the next
             // open): opening a Seg used to start with a dependent global load between "stage landed" and "next DMA issued" -
             // pure load-path idle time, once per Seg, and the gradient-at-F1 tiles have a Seg every two chunks.
-            Seg nx = t.seg0;
+            Seg nx = TASK_LANES ? task_seg0() : t.seg0;
             auto open_seg = [&](int sidx) {            // wave-uniform: Seg fields live in SGPRs
                 const Seg sg = nx;
                 if (sidx + 1 < seg_end) nx = segs[sidx + 1];
@@ -1185,6 +1242,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             int buf = 0;
             open_seg(cseg);
             issue(0, 0);
+            FSTAMP(3, 0);
             if constexpr (PF_IT > 0) request_epilogue_operands();
             for (;;) {
                 const int n_chunks = (klen + CH - 1) / CH;
@@ -1232,7 +1290,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             constexpr int LPW = OperandStream<BM, NW, TW, PAIR, HS>::NP + OperandStream<BN, NW, TW, PAIR, HS>::NP;   // DMAs per lane and chunk (16-byte path;
                                                                                          // the 4-byte path issues more, never fewer)
             int i_seg = cseg, i_chunk = 0, i_nchunks = 0, i_klen = 0, i_buf = 0, ahead = 0;
-            Seg nx = t.seg0;                         // descriptor of the Seg the issue cursor opens next, fetched one Seg ahead
+            Seg nx = TASK_LANES ? task_seg0() : t.seg0;                         // descriptor of the Seg the issue cursor opens next, fetched one Seg ahead
             auto open_issue_seg = [&]() {            // wave-uniform: Seg fields live in SGPRs
                 const Seg sg = nx;
                 if (i_seg + 1 < seg_end) nx = segs[i_seg + 1];
@@ -1268,9 +1326,10 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             open_issue_seg();
     #pragma unroll 1
             for (int sidx = 0; sidx < NS - 1 && i_seg < seg_end; ++sidx) issue_one();
+            FSTAMP(3, 0);
 
             int c_buf = 0;
-            int c_klen_nx = t.seg0.klen, c_scale_nx = t.seg0.scale_kind;   // compute cursor: the same one-ahead fetch of (klen, scale)
+            int c_klen_nx = TASK_F(seg0.klen), c_scale_nx = TASK_F(seg0.scale_kind);   // compute cursor: the same one-ahead fetch of (klen, scale)
             for (;;) {
                 const int klen = c_klen_nx, c_scale = c_scale_nx;
                 if (cseg + 1 < seg_end) { c_klen_nx = segs[cseg + 1].klen; c_scale_nx = segs[cseg + 1].scale_kind; }
@@ -1338,13 +1397,12 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     using T_ = std::true_type;
     using F_ = std::false_type;
     {
-        const Seg &s0 = t.seg0;
-        switch (s0.a_kmajor * 2 + s0.b_kmajor) {
+        switch (TASK_F(seg0.a_kmajor) * 2 + TASK_F(seg0.b_kmajor)) {
             case 0: if constexpr (KVE & 1) k_loop(F_{}, F_{}, F_{}); break;
             case 1: if constexpr (KVE & 2) k_loop(F_{}, T_{}, F_{}); break;
             case 2: if constexpr (KVE & 4) k_loop(T_{}, F_{}, F_{}); break;
             default:   // weight gradients (both operands k-major) are the only tiles that also produce a bias gradient
-                if (t.epi & EPI_ROWSUM_A) { if constexpr (KVE & 16) k_loop(T_{}, T_{}, T_{}); }
+                if (TASK_F(epi) & EPI_ROWSUM_A) { if constexpr (KVE & 16) k_loop(T_{}, T_{}, T_{}); }
                 else { if constexpr (KVE & 8) k_loop(T_{}, T_{}, F_{}); }
                 break;
         }
@@ -1379,8 +1437,8 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     const float *__restrict__ split_other = nullptr;
     if (OPT && (epi & EPI_SPLITK)) {
         int &split_ticket = *reinterpret_cast<int *>(&lds[EPI]);
-        const int half = t.pad[2] - 1;
-        float *mine = ptrs.ws + t.pad[0] + (size_t)half * (BM * BN);
+        const int half = TASK_A(pad, 2) - 1;
+        float *mine = ptrs.ws + TASK_A(pad, 0) + (size_t)half * (BM * BN);
         constexpr int ITER_S = (BM * BN / 4 + NT - 1) / NT;
 #pragma unroll
         for (int it = 0; it < ITER_S; ++it) {
@@ -1400,30 +1458,30 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        int *ticket = reinterpret_cast<int *>(ptrs.ws + t.pad[1]);
+        int *ticket = reinterpret_cast<int *>(ptrs.ws + TASK_A(pad, 1));
         if (tid == 0) split_ticket = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         if (split_ticket == 0) return;                          // (uniform) the partner finishes the tile
         if (tid == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next step
-        split_other = ptrs.ws + t.pad[0] + (size_t)(1 - half) * (BM * BN);
+        split_other = ptrs.ws + TASK_A(pad, 0) + (size_t)(1 - half) * (BM * BN);
     }
     // ... its partial tile is read in the store loop below with agent-scope loads (coherent: never served from a stale line of this
     // XCD's L2; compiler-managed, so nothing reads the registers before the data has landed)
-    const float alpha = scale_of(t.alpha_kind);
-    const float gamma = scale_of(t.gamma_kind);
-    const bool drop_on = (epi & (EPI_DROP_I | EPI_DROP_V)) && h_train != 0;
-    const uint32_t dseed = (epi & EPI_DROP_I) ? hh.seed_i : hh.seed_v;
-    const float dp = (epi & EPI_DROP_I) ? hh.p_drop_i : hh.p_drop_v;
-    const uint32_t doff = drop_on ? (uint32_t)t.pad2 : 0u;      // stream offset of a stacked shared layer (--add_fc; 0 otherwise)
-    float *__restrict__ cbase = const_cast<float *>(base_ptr(ptrs, t.c_base)) + (size_t)t.c_off;
+    const float alpha = scale_of(TASK_F(alpha_kind));
+    const float gamma = scale_of(TASK_F(gamma_kind));
+    const bool drop_on = (epi & (EPI_DROP_I | EPI_DROP_V)) && HYPER_TRAIN != 0;
+    const uint32_t dseed = (epi & EPI_DROP_I) ? HYPER_U(seed_i) : HYPER_U(seed_v);
+    const float dp = (epi & EPI_DROP_I) ? HYPER_F(p_drop_i) : HYPER_F(p_drop_v);
+    const uint32_t doff = drop_on ? (uint32_t)TASK_F(pad2) : 0u;      // stream offset of a stacked shared layer (--add_fc; 0 otherwise)
+    float *__restrict__ cbase = const_cast<float *>(base_ptr(ptrs, TASK_F(c_base))) + (size_t)TASK_F(c_off);
     const EpiOperands eo = PF_IT > 0 ? eo_early : epi_operands();
     const int nfan = eo.nfan;
-    const bool c_vec = ((t.c_off | t.c_ld) & 3) == 0;
+    const bool c_vec = ((TASK_F(c_off) | TASK_F(c_ld)) & 3) == 0;
     // Fused update (SgdSide::p_new): a gradient tile is also the optimiser step of its block of parameters.  torch.optim.SGD with
     // nesterov and weight decay (main.py:83, 583) in the arithmetic of sgd_kernel with the clip coefficient taken as 1:
     //   d = wd p + g;  m = mu m + d;  p_new = p - lr (d + mu m)
     // (a step whose gradient norm exceeds clip_gradient is corrected afterwards by sgd_fixup_kernel: the update is linear in g).
-    const bool upd = OPT && side.p_new != nullptr && t.c_base == BASE_G;      // workgroup-uniform
+    const bool upd = OPT && side.p_new != nullptr && TASK_F(c_base) == BASE_G;      // workgroup-uniform
     float sumsq = 0.f;   // EPI_SUMSQ: this thread's share of the tile's sum of squares
     // Every flag test below is workgroup-uniform: a tile without bias / mask / residual / fan-out issues no load for it.  The
     // bias and the per-step scalars were requested before the K loop, and in the kind-specialised kernels (EPI_EARLY) so were
@@ -1431,6 +1489,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     // front of the tile's own store): the first dependent global access of such a tile is its store.  The general kernels and
     // the experiments build request residual and mask at the head of the pass and the fan-out masks behind the tile's own store,
     // as before - see the request site above the K loop.
+    ESTAMP(alpha, gamma, TASK_F(c_ld));
     constexpr int ITER = (BM * BN / 4 + NT - 1) / NT;
     constexpr int UNR = ITER <= 4 ? ITER : 2;
 #pragma unroll UNR
@@ -1469,7 +1528,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
 #pragma unroll
             for (int e = 0; e < 4; ++e) { up[e] = up_e[UPD_PREFETCH ? it : 0][e]; um[e] = um_e[UPD_PREFETCH ? it : 0][e]; }
         } else if (upd && nrem > 0) {             // requested here: the latency overlaps the LDS reads below
-            const size_t pi = (size_t)t.c_off + (size_t)m * t.c_ld + n;
+            const size_t pi = (size_t)TASK_F(c_off) + (size_t)m * TASK_F(c_ld) + n;
             if (nrem >= 4 && c_vec) {
                 const float4 q4 = *reinterpret_cast<const float4 *>(ptrs.p + pi), r4 = *reinterpret_cast<const float4 *>(side.momentum + pi);
                 up[0] = q4.x; up[1] = q4.y; up[2] = q4.z; up[3] = q4.w; um[0] = r4.x; um[1] = r4.y; um[2] = r4.z; um[3] = r4.w;
@@ -1494,7 +1553,8 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
 #ifdef TA3N_GEMM_STAMPS
         if (it == 0) {      // [11]: the first pass's LDS sum is there - and, the compiler's own wait for them standing in front of it, so are its global operands
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            GSTAMP_W1(11, __builtin_amdgcn_s_memtime());
+            const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+            GSTAMP_W1(11, (now_ & 0xFFFFFFFFFFFFull) | (((now_ - ks_e) & 0xFFFFull) << 48));
         }
 #endif
         float v[4] = {v4.x, v4.y, v4.z, v4.w};
@@ -1503,14 +1563,14 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             float x = (v[e] + ebias[e]) * alpha + av[e];
             if (epi & EPI_RELU) x = fmaxf(x, 0.f);
             x = mv[e] > 0.f ? x : 0.f;
-            if (drop_on) x *= keep_mask(dseed, (uint32_t)(m * t.drop_ld + n + e) + doff, dp);
+            if (drop_on) x *= keep_mask(dseed, (uint32_t)(m * TASK_F(drop_ld) + n + e) + doff, dp);
             v[e] = x * gamma;
         }
         if (nrem <= 0) continue;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (e < nrem) sumsq = fmaf(v[e], v[e], sumsq);
-        float *cp = cbase + (size_t)m * t.c_ld + n;
+        float *cp = cbase + (size_t)m * TASK_F(c_ld) + n;
         if (epi & EPI_TWIN_ONLY) {
             // every consumer of this tile reads its bf16 twin: the fp32 copy is not written (a third of the store burst)
         } else if (nrem >= 4 && c_vec) {
@@ -1522,7 +1582,7 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
                 if (e < nrem) { if (pub) st_pub(cp + e, v[e]); else cp[e] = v[e]; }
         }
         if (upd) {
-            const size_t pi = (size_t)t.c_off + (size_t)m * t.c_ld + n;
+            const size_t pi = (size_t)TASK_F(c_off) + (size_t)m * TASK_F(c_ld) + n;
             float pn[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -1544,24 +1604,24 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
             }
         }
         if (epi & EPI_TWIN16) {          // bf16 twin of the stored values (TA3N_FLAG_BF16_STORE)
-            unsigned short *tp = reinterpret_cast<unsigned short *>(ptrs.ws + twin_off) + ((size_t)t.c_off + (size_t)m * t.c_ld + n);
+            unsigned short *tp = reinterpret_cast<unsigned short *>(ptrs.ws + twin_off) + ((size_t)TASK_F(c_off) + (size_t)m * TASK_F(c_ld) + n);
             const unsigned lo = pack_bf16(v[0], v[1]), hi = pack_bf16(v[2], v[3]);
             store_twin4(tp, lo, hi, nrem, c_vec, pub);
             if ((BF == 3 || BF == 4) && pair_delta)      // pair twins (split-arithmetic launches only): the lo plane of the same four values
                 store_twin4(tp + 2 * (size_t)pair_delta, pack_bf16_lo(v[0], v[1], lo), pack_bf16_lo(v[2], v[3], hi), nrem, c_vec, pub);
         }
         if (nfan > 0) {
-            const bool fan_vec = nrem >= 4 && (t.fan_ld & 3) == 0;
+            const bool fan_vec = nrem >= 4 && (TASK_F(fan_ld) & 3) == 0;
             if constexpr (!EPI_EARLY) fetch_fan(eo, fm, m, n, nrem);      // general and forward kernels, experiments build: all mask loads here, behind the tile's own store, as before
 #pragma unroll
             for (int f = 0; f < 3; ++f) {   // same value through several ReLU masks (TRN tuples of one scale)
                 if (f < nfan) {
-                    float *op = ptrs.ws + (size_t)t.fan_out_off[f] + (size_t)m * t.fan_ld + n;
+                    float *op = ptrs.ws + (size_t)TASK_A(fan_out_off, f) + (size_t)m * TASK_F(fan_ld) + n;
                     float ov[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ov[e] = (e < nrem && fm[f][e] > 0.f) ? v[e] : 0.f;
                     if (epi & EPI_TWIN_ONLY_FAN) {
-                    } else if (fan_vec && (t.fan_out_off[f] & 3) == 0) {
+                    } else if (fan_vec && (TASK_A(fan_out_off, f) & 3) == 0) {
                         if (pub) st_pub(op, f32x4{ov[0], ov[1], ov[2], ov[3]});
                         else *reinterpret_cast<float4 *>(op) = make_float4(ov[0], ov[1], ov[2], ov[3]);
                     } else {
@@ -1571,9 +1631,9 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
                     }
                     if (epi & EPI_TWIN16_FAN) {
                         unsigned short *tp = reinterpret_cast<unsigned short *>(ptrs.ws + twin_off) +
-                                             ((size_t)t.fan_out_off[f] + (size_t)m * t.fan_ld + n);
+                                             ((size_t)TASK_A(fan_out_off, f) + (size_t)m * TASK_F(fan_ld) + n);
                         const unsigned lo = pack_bf16(ov[0], ov[1]), hi = pack_bf16(ov[2], ov[3]);
-                        const bool fvec = ((t.fan_out_off[f] | t.fan_ld) & 3) == 0;
+                        const bool fvec = ((TASK_A(fan_out_off, f) | TASK_F(fan_ld)) & 3) == 0;
                         store_twin4(tp, lo, hi, nrem, fvec, pub);
                         if ((BF == 3 || BF == 4) && pair_delta)
                             store_twin4(tp + 2 * (size_t)pair_delta, pack_bf16_lo(ov[0], ov[1], lo), pack_bf16_lo(ov[2], ov[3], hi), nrem, fvec, pub);
@@ -1594,10 +1654,10 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
 #pragma unroll
             for (int i = 0; i < 2 * WK; ++i) b += lds[i * BM + tid];
             if (m0 + tid < m_valid) {
-                const_cast<float *>(base_ptr(ptrs, t.bias_base))[(size_t)t.bias_off + m0 + tid] = b;
+                const_cast<float *>(base_ptr(ptrs, TASK_F(bias_base)))[(size_t)TASK_F(bias_off) + m0 + tid] = b;
                 sumsq = fmaf(b, b, sumsq);
-                if (upd && t.bias_base == BASE_G) {      // the bias gradient's own parameter entries
-                    const size_t pi = (size_t)t.bias_off + m0 + tid;
+                if (upd && TASK_F(bias_base) == BASE_G) {      // the bias gradient's own parameter entries
+                    const size_t pi = (size_t)TASK_F(bias_off) + m0 + tid;
                     float p1 = ptrs.p[pi], mm = side.momentum[pi];
                     nesterov_sgd(p1, mm, b, side.lr, side.mu, side.wd);
                     side.p_new[pi] = p1; side.momentum[pi] = mm;
@@ -1608,7 +1668,8 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
     }
     GSTAMP(5);
 #if defined(TA3N_GEMM_STAMPS) && TA3N_GEMM_STAMPS == 1
-    GSTAMP_VAL(6, t.cost); GSTAMP_VAL(7, t.seg_count);
+    GSTAMP_VAL(6, (unsigned long long)TASK_F(cost) | ks_f[0] << 24 | ks_f[1] << 40);
+    GSTAMP_VAL(7, (unsigned long long)TASK_F(seg_count) | ks_f[2] << 16 | ks_f[3] << 32);
 #endif
     if (epi & EPI_SUMSQ) {   // wave-uniform: fixed-order block sum -> this tile's slot (fused grad-norm partial)
         __syncthreads();
@@ -1618,10 +1679,16 @@ __device__ __forceinline__ void gemm_tile(const Task &t, const Seg *__restrict__
         if (tid == 0) {
             float tot = 0.f;
             for (int i = 0; i < NW; ++i) tot += lds[i];
-            ptrs.ws[t.pad[3]] = tot;
+            ptrs.ws[TASK_A(pad, 3)] = tot;
         }
     }
 }
+
+#undef TASK_F
+#undef TASK_A
+#undef HYPER_F
+#undef HYPER_U
+#undef HYPER_TRAIN
 
 // One workgroup = one Task of the launch's list.  chain_off >= 0: a chained launch (several dependency levels; ta3n_types.h).
 template <int WM, int WN, int WK, int BF, int NS, int RM, int RN, int KV = 63>

@@ -6,7 +6,10 @@ and inside the K loop the time thread 0 spends WAITING for a stage (s_waitcnt + 
 stage's DMA, LDS reads and MFMAs - printed per launch and per tile length: where a launch's time goes; and around a Seg boundary: from the
 barrier to the stage's DMAs issued on chunks that start a Seg's stream against chunks inside a Seg, and the LDS reads + MFMAs of a Seg's last
 chunk against an interior one (-DTA3N_SEG_FAST=0 beside -DTA3N_GEMM_STAMPS builds the old boundary sequence).  TA3N_KIND_KERNELS=0 runs the
-general kernels, which request a tile's residual and mask inside the store loop; the default runs the kind-specialised ones."""
+general kernels, which request a tile's residual and mask inside the store loop; the default runs the kind-specialised ones.
+The front of a tile ("desc", entry -> descriptors / bias loaded) is split into its stretches - first Task word there, per-step scalars there, bias
+requested, first stage's DMAs issued: each as thread 0's time since entry, in the order the kernel reaches them - and the store pass into "Task fields
+of the store loop in registers" and the LDS sum behind it (-DTA3N_TASK_FAST=0 beside -DTA3N_GEMM_STAMPS builds the old descriptor reads)."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -45,6 +48,14 @@ for i, ph in enumerate(phases):
     torch.cuda.synchronize()
     n = min(ph["task_count"], 8192)
     st = stamps[: n * SL].cpu().numpy().reshape(n, SL).astype(np.int64)
+    # the front stamps share slots 6 / 7 with the cost and the Seg count, the store-pass stamp slot 11 with the old one (ta3n_gemm_kernel.h: FSTAMP)
+    front = np.stack([(st[:, 6] >> 24) & 0xFFFF, (st[:, 6] >> 40) & 0xFFFF, (st[:, 7] >> 16) & 0xFFFF, (st[:, 7] >> 32) & 0xFFFF], 1)
+    st[:, 6] &= (1 << 24) - 1
+    st[:, 7] &= (1 << 16) - 1
+    M48 = (1 << 48) - 1
+    sum_lds = (st[:, 11] >> 48) & 0xFFFF
+    st[:, 11] &= M48
+    st[:, 4] = np.where(st[:, 11] > 0, st[:, 4] & M48, st[:, 4])      # (only the difference [11] - [4] is printed)
     real = st[:, 7] > 0
     if not real.any():
         print(f"launch {i}: no stamps"); continue
@@ -59,6 +70,9 @@ for i, ph in enumerate(phases):
               f"{np.mean(ns):.1f} stages -> {np.mean(st[m, 8] / ns) * TICK * 1e3:5.0f} + {np.mean(st[m, 9] / ns) * TICK * 1e3:5.0f} ns per stage)  wait-waves {d(3, 2):5.2f}  to-lds {d(4, 3):5.2f}  "
               f"combine+store {d(5, 4):5.2f} (second wave, first pass: LDS sum and global operands there {d(11, 4):5.2f} after [4])"
               f"  | finish {np.mean(st[m, 5] - t0) * TICK:6.2f} us")
+        f = front[m].mean(0) * TICK
+        print(f"          front, us since entry: first Task word {f[0]:4.2f}  per-step scalars {f[1]:4.2f}  bias requested {f[2]:4.2f}  first stage's DMAs issued {f[3]:4.2f}"
+              f" | store pass: [4] -> Task fields in registers {d(11, 4) - np.mean(sum_lds[m]) * TICK:4.2f}, -> LDS sum and global operands there {np.mean(sum_lds[m]) * TICK:4.2f}")
         # Seg boundary stamps (slots 12 - 15: cycles in the low 40 bits, stretches counted above them): ns per stretch over the class
         def per(slot):
             cyc, cnt = (st[m, slot] & ((1 << 40) - 1)).sum(), (st[m, slot] >> 40).sum()
