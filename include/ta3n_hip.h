@@ -95,6 +95,14 @@ typedef enum {
  * without TA3N_FLAG_TRANS_ATTN (the reference fails there), on TA3N_AGG_AVGPOOL, and with TA3N_FLAG_F32_SPLIT, _MCD, _BN_SHARED,
  * shared_fc_layers > 1, chain, split_k or wgrads_late. */
 #define TA3N_FLAG_FRAME_ATTN     (1u << 11)
+/* --weighted_class_loss Y (main.py:156-165, 205): criterion = CrossEntropyLoss(weight = w), w[c] > 0 per class.  Every class cross-entropy
+ * of the plan (the step's, MCD's second classifier's, the validation metrics') becomes  sum_i w[y_i] ce_i / sum_i w[y_i]  over the valid
+ * source rows: the per-row coefficient is w[y_i] / sum_j w[y_j] instead of 1 / n.  The plan gets one more workspace region, "class_w"
+ * (64 floats, behind every other region; a plan without the flag is unchanged byte for byte): the caller writes the num_class weights
+ * there once, after ta3n_init_workspace (MCD: into both workspaces).  The kernels form sum_j w[y_j] themselves from region "labels" and
+ * ta3n_hyper.valid_source, in a fixed order, so batches gathered on the device and K-step calls need nothing from the host.  The sum is over
+ * THIS rank's rows: single rank.  ta3n_hyper.inv_n_cls is not used under the flag. */
+#define TA3N_FLAG_CLASS_WEIGHTS  (1u << 12)
 
 /* ta3n_config.aggregation */
 #define TA3N_AGG_TRN_M    0   /* 'trn-m': multi-scale TRN - the TA3N path (TRNmodule.py:27-86) */
@@ -185,7 +193,14 @@ typedef struct {
                               * its affine pair and its running statistics).  main.validate's call, main.py:707: model(val_data,
                               * val_data) scored on the target branch - the videos sit in the source rows here, so that is what
                               * TrainEngine.evaluate_batch sets.  0: each half through its own BatchNorm.  Ignored in train mode. */
-    int32_t reserved[1];
+    int32_t class_w_off;     /* ws offset of region "class_w" (TA3N_FLAG_CLASS_WEIGHTS), 0 without the flag.  Written BY THE LIBRARY from the
+                              * plan wherever it uploads or forwards these scalars: ta3n_set_hyper, the `next` of the update launches,
+                              * ta3n_train_steps*.  Whatever the caller leaves here is ignored. */
+    float dom_k[2];          /* weighted domain criterion, CrossEntropyLoss(weight = (w_s, w_t)) (main.py:166-167, 533): factor on the per-row
+                              * coefficient 1 / n of the domain cross-entropy of every level, [0] for source rows, [1] for target rows:
+                              *   k_s = w_s (n_s + n_t) / (w_s n_s + w_t n_t),  k_t = w_t (n_s + n_t) / (w_s n_s + w_t n_t)
+                              * with n_s, n_t the global valid video counts of the step (the same factor at the relation, video and frame
+                              * level).  A value of 0 IS READ AS 1: a zero-initialised ta3n_hyper is the unweighted criterion, bit for bit. */
 } ta3n_hyper;
 
 typedef struct ta3n_plan ta3n_plan;

@@ -29,6 +29,7 @@ from ta3n_amd.dataset import TSNDataSet  # noqa: E402
 from ta3n_amd.loss import JAN, attentive_entropy, dis_MCD, mmd_rbf  # noqa: E402
 from ta3n_amd.models import VideoModel  # noqa: E402
 from ta3n_amd import accel as _accel  # noqa: E402
+from ta3n_amd.engine import class_weights_from_list  # noqa: E402
 _accel.install()      # clip_grad_norm_ / SGD.step as passes over VideoModel's flat buffers (same arithmetic; TA3N_ACCEL=0: torch's own)
 from ta3n_amd.opts import parser  # noqa: E402
 from train_ddp import train_list_sizes, validate_options  # noqa: E402
@@ -105,8 +106,14 @@ def main():
 
     val_loader = torch.utils.data.DataLoader(dataset(args.val_list, num_val, val_segments), batch_size=args.batch_size[2],
                                              shuffle=False, num_workers=args.workers, pin_memory=True)
-    criterion = torch.nn.CrossEntropyLoss().cuda()                                      # :204-206 (class weights: rejected options)
-    criterion_domain = torch.nn.CrossEntropyLoss().cuda()
+    weight_source_class = torch.ones(num_class).cuda()                                  # :155-167
+    weight_domain_loss = torch.Tensor([1, 1]).cuda()
+    if args.weighted_class_loss == "Y":
+        weight_source_class = torch.Tensor(class_weights_from_list(args.train_source_list, num_class)).cuda()
+    if args.weighted_class_loss_DA == "Y":
+        weight_domain_loss = torch.Tensor([1 / num_source_train, 1 / num_target_train]).cuda()
+    criterion = torch.nn.CrossEntropyLoss(weight=weight_source_class).cuda()            # :204-206
+    criterion_domain = torch.nn.CrossEntropyLoss(weight=weight_domain_loss).cuda()
     if args.evaluate:                                                                   # :208-212
         prec1 = validate(val_loader, model, criterion, num_class, 0, test_file)
         test_short_file.write("%.3f\n" % prec1)
@@ -158,7 +165,18 @@ def _pad(data, n):
     return data
 
 
-def _fast_engine(model, optimizer, num_class):
+def _criterion_weights(criterion, n):
+    """The weights of a CrossEntropyLoss as the engine takes them: None when it has none or they are all equal (the unweighted mean)."""
+    w = getattr(criterion, "weight", None)
+    if w is None:
+        return None
+    w = tuple(float(v) for v in w.detach().cpu().reshape(-1).tolist())
+    if len(w) != n:
+        raise ValueError(f"criterion weight has {len(w)} entries, expected {n}")
+    return None if all(v == w[0] for v in w) else w
+
+
+def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=None):
     """The fused step (ta3n_amd.engine.TrainEngine: forward + the loss assembly of :439-562 + backward + clip + Nesterov SGD as 8
     launches of one library call) for the configurations it covers, instead of VideoModel.forward + the torch loss assembly + autograd
     + clip_grad_norm_ + SGD.step (the MODULE path: ~60 small torch kernels around the same HIP launches, 1.25 ms against 0.12 ms per step
@@ -207,13 +225,15 @@ def _fast_engine(model, optimizer, num_class):
     attn_frame = getattr(args, "use_attn_frame", "none")
     if attn_frame != "none" and (attn_frame != "TransAttn" or args.use_attn != "TransAttn" or dis or mcd or args.use_bn != "none" or add_fc != 1):
         return None
+    # --weighted_class_loss / --weighted_class_loss_DA: the engine takes the weights the two criteria carry (:160-167, 205-206)
+    class_w, domain_w = _criterion_weights(criterion, num_class), _criterion_weights(criterion_domain, 2)
     g = optimizer.param_groups[0]
     # everything the engine is BUILT from: a later train() call with other options must not find an engine made for these
     key = (args.batch_size[0], args.batch_size[1], args.num_segments, args.fc_dim, num_class, tuple(args.place_adv), args.add_loss_DA,
            args.use_attn, args.adv_DA, args.use_target, float(args.dropout_i), float(args.dropout_v),
            ("Adam", float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) if adam else ("SGD", float(g["momentum"])),
            float(g["weight_decay"]), None if args.clip_gradient is None else float(args.clip_gradient), args.use_bn,
-           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame)
+           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame, class_w, domain_w)
     eng = m.__dict__.get("_main_fast_engine", {}).get(key)
     if eng is None:
         eng = TrainEngine(args.batch_size[0], args.batch_size[1], args.num_segments, m.feature_dim, args.fc_dim, num_class,
@@ -222,9 +242,11 @@ def _fast_engine(model, optimizer, num_class):
                           **(dict(optimizer="Adam", betas=tuple(g["betas"]), eps=g["eps"]) if adam else dict(momentum=g["momentum"])),
                           clip=args.clip_gradient if args.clip_gradient is not None else 0.0, device=next(m.parameters()).device,
                           use_bn=args.use_bn, **(dict(dis_DA=args.dis_DA, place_dis=tuple(args.place_dis)) if dis else {}),
-                          **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc)
+                          **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc, class_weights=class_w, domain_weights=domain_w)
         if not eng.fused and not (dis or mcd or attn_frame != "none"):
             return None
+        if class_w is not None or domain_w is not None:      # said once: the weighted criteria train on the engine
+            print("[ta3n] " + eng.describe(), flush=True)
         m.__dict__.setdefault("_main_fast_engine", {})[key] = eng
     return eng
 
@@ -364,7 +386,7 @@ def _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, 
 def train(num_class, source_loader, target_loader, model, criterion, criterion_domain, optimizer, epoch, log, log_short, alpha, beta,
           gamma, mu):
     """:309-667 for the supported options: RevGrad adversarial losses on the enabled levels and attentive entropy."""
-    eng = _fast_engine(model, optimizer, num_class)
+    eng = _fast_engine(model, optimizer, num_class, criterion, criterion_domain)
     if eng is not None:
         done = _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, epoch, log, log_short, beta, gamma, alpha, mu)
         if done is not None:      # (None: optimiser state the engine cannot hold - Adam step counts that differ - found before anything ran)

@@ -29,6 +29,7 @@ FLAG_BF16_MFMA = 1 << 8
 FLAG_BF16_STORE = 1 << 9
 FLAG_F32_SPLIT = 1 << 10       # fp32-grade contractions as three bf16 MFMAs on operands split hi + lo in registers ("bf16x3")
 FLAG_FRAME_ATTN = 1 << 11      # use_attn_frame TransAttn: frame features scaled by 1 + (1 - H(frame-discriminator softmax)) in front of the TRN (regions F1a, attn_frame); unfused entry points
+FLAG_CLASS_WEIGHTS = 1 << 12   # --weighted_class_loss: every class CE weighted per class (region class_w, written by the caller); single rank
 AGG_TRN_M, AGG_AVGPOOL = 0, 1
 
 # every symbol include/ta3n_hip.h declares (tests check the export list)
@@ -66,7 +67,7 @@ class Hyper(C.Structure):
                 ("seed_i", C.c_uint32), ("seed_v", C.c_uint32), ("inv_n_cls", C.c_float), ("inv_n_rel", C.c_float),
                 ("inv_n_vid", C.c_float), ("inv_n_frm", C.c_float), ("inv_n_ent", C.c_float),
                 ("valid_source", C.c_int32), ("valid_target", C.c_int32), ("train", C.c_int32),
-                ("reverse", C.c_int32), ("mu", C.c_float), ("bn_eval_target", C.c_int32), ("reserved", C.c_int32 * 1)]
+                ("reverse", C.c_int32), ("mu", C.c_float), ("bn_eval_target", C.c_int32), ("class_w_off", C.c_int32), ("dom_k", C.c_float * 2)]
 
 
 class Feed(C.Structure):

@@ -64,6 +64,19 @@ int ensure_uploaded(ta3n_plan *p) {
     return TA3N_OK;
 }
 
+// A caller's ta3n_hyper with the words the PLAN owns filled in (class_w_off: the ws offset of region "class_w", 0 without
+// TA3N_FLAG_CLASS_WEIGHTS; whatever the caller left there is ignored).  Every path that uploads or forwards a Hyper goes through this.
+struct PlanHyper {
+    Hyper h;
+    bool has;
+    PlanHyper(const ta3n_plan *p, const ta3n_hyper *src) : has(src != nullptr) {
+        std::memset(&h, 0, sizeof(h));
+        if (src) std::memcpy(&h, src, sizeof(h));
+        h.class_w_off = (int32_t)p->class_w_off;
+    }
+    const Hyper *ptr() const { return has ? &h : nullptr; }
+};
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // buffers of one launch sequence; the parameter twins it reads are those of region `twin_region` (0: "p16", 1: "p16b")
@@ -333,9 +346,7 @@ int ta3n_set_hyper(ta3n_plan *p, float *ws, const ta3n_hyper *h, void *stream) {
     if (rc != TA3N_OK) return rc;
     // by kernel argument: the values are captured when the launch is enqueued, so the host may run any number of steps
     // ahead of the stream (a pinned staging ring would need an event per slot before reuse)
-    Hyper hv;
-    std::memcpy(&hv, h, sizeof(hv));
-    if (launch_set_hyper(ws + p->geom.o_hyper, hv, static_cast<hipStream_t>(stream)) != 0)
+    if (launch_set_hyper(ws + p->geom.o_hyper, PlanHyper(p, h).h, static_cast<hipStream_t>(stream)) != 0)
         return fail(TA3N_ERR_HIP, std::string("set_hyper launch failed: ") + hipGetErrorString(hipGetLastError()));
     return TA3N_OK;
 }
@@ -596,7 +607,7 @@ int ta3n_train_step_after_update(ta3n_plan *p, const float *x, float *params, fl
     if (!fused_norm && launch_grad_norm(g, grads, ws, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
     // (1) the update of the shared frame FC - the only parameters the next launch reads - and the new step's scalars
     if (launch_sgd_range(g, params, grads, momentum, ws, 0, p->first_floats, fused_norm != 0, lr, momentum_coef, weight_decay, clip,
-                         reinterpret_cast<const Hyper *>(next), s) != 0)
+                         PlanHyper(p, next).ptr(), s) != 0)
         return fail(TA3N_ERR_HIP, "sgd launch failed");
     // (2) the new step's first launch, with the rest of the update as side tasks; (3) the other launches of the step
     const SgdSide side = update_side(g, params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm);
@@ -661,12 +672,12 @@ static int enqueue_pipelined_step(ta3n_plan *p, const Ptrs &ptrs, float *params,
         if (target && (rc = feed_job(p, target, k, g.Bs, g.Bt, const_cast<float *>(ptrs.x), ws, nullptr, &jobs[1])) != TA3N_OK) return rc;
         if (!fused_norm && launch_grad_norm(g, grads, ws, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
         if (launch_sgd_open_feed(g, params, grads, momentum, ws, 0, p->first_floats, fused_norm != 0, lr, momentum_coef, weight_decay, clip,
-                                 reinterpret_cast<const Hyper *>(next), jobs, s) != 0)
+                                 PlanHyper(p, next).ptr(), jobs, s) != 0)
             return fail(TA3N_ERR_HIP, "sgd + batch-assembly launch failed");
     } else {
         if (!fused_norm && launch_grad_norm(g, grads, ws, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
         if (launch_sgd_range(g, params, grads, momentum, ws, 0, p->first_floats, fused_norm != 0, lr, momentum_coef, weight_decay, clip,
-                             reinterpret_cast<const Hyper *>(next), s) != 0)
+                             PlanHyper(p, next).ptr(), s) != 0)
             return fail(TA3N_ERR_HIP, "sgd launch failed");
     }
     const SgdSide side = update_side(g, params, momentum, lr, momentum_coef, weight_decay, clip, fused_norm);
@@ -800,7 +811,8 @@ int ta3n_sgd_shard(ta3n_plan *p, float *params, float *grads, float *momentum, f
     int64_t r[4];
     own_ranges(p, s, rank, r);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Hyper *nx = reinterpret_cast<const Hyper *>(next);
+    const PlanHyper next_h(p, next);
+    const Hyper *nx = next_h.ptr();
     // the norm is the sum of the ranks' shard partials in region norm_part (slots [0, world), the rest zero): fused_norm = false
     if (r[1] > r[0]) {
         if (launch_sgd_range(p->geom, params, grads, momentum, ws, r[0], r[1], false, lr, momentum_coef, weight_decay, clip, nx, st, true) != 0)
@@ -926,9 +938,7 @@ int ta3n_train_steps_fused_update(ta3n_plan *p, const float *x, float *params, f
     HIP_TRY(hipMemcpyAsync(params_alt, params, (size_t)p->param_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (twins) HIP_TRY(hipMemcpyAsync(T16[1], T16[0], (size_t)((p->param_floats + 1) / 2) * sizeof(float), hipMemcpyDeviceToDevice, s));
     // the first step's scalars; every later step receives its own from the launch that closes the step before it
-    Hyper h0;
-    std::memcpy(&h0, &hypers[0], sizeof(h0));
-    if (launch_set_hyper(ws + g.o_hyper, h0, s) != 0) return fail(TA3N_ERR_HIP, "set_hyper launch failed");
+    if (launch_set_hyper(ws + g.o_hyper, PlanHyper(p, &hypers[0]).h, s) != 0) return fail(TA3N_ERR_HIP, "set_hyper launch failed");
     int cur = 0;
     for (int k = 0; k < n_steps; ++k) {
         if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
@@ -943,7 +953,7 @@ int ta3n_train_steps_fused_update(ta3n_plan *p, const float *x, float *params, f
         cur ^= 1;
         // norm / clip check of step k on the buffer it wrote, carrying step k + 1's scalars
         if (launch_sgd_fixup(g, P[cur], grads, momentum, ws, T16[cur], hypers[k].lr, momentum_coef, clip,
-                             k + 1 < n_steps ? reinterpret_cast<const Hyper *>(&hypers[k + 1]) : nullptr, s) != 0)
+                             PlanHyper(p, k + 1 < n_steps ? &hypers[k + 1] : nullptr).ptr(), s) != 0)
             return fail(TA3N_ERR_HIP, "sgd fixup launch failed");
     }
     if (cur == 1) {      // an odd number of steps: the result goes back to the caller's buffer (and its twin region)
@@ -999,7 +1009,7 @@ int ta3n_sgd_step_next(ta3n_plan *p, float *params, float *grads, float *momentu
         if (launch_grad_norm(p->geom, grads, ws, static_cast<hipStream_t>(stream)) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
     }
     if (launch_sgd_range(p->geom, params, grads, momentum, ws, 0, p->live_floats, fused_norm != 0, lr, momentum_coef, weight_decay, clip,
-                         reinterpret_cast<const Hyper *>(next), static_cast<hipStream_t>(stream)) != 0)
+                         PlanHyper(p, next).ptr(), static_cast<hipStream_t>(stream)) != 0)
         return fail(TA3N_ERR_HIP, std::string("sgd launch failed: ") + hipGetErrorString(hipGetLastError()));
     return TA3N_OK;
 }
@@ -1068,7 +1078,7 @@ int enqueue_adam(ta3n_plan *p, float *params, float *grads, float *exp_avg, floa
     if (rc != TA3N_OK) return rc;
     if (!fused_norm && begin == 0 && launch_grad_norm(p->geom, grads, ws, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
     if (launch_adam_range(p->geom, params, grads, exp_avg, exp_avg_sq, ws, begin, end, fused_norm != 0, step_size, bc2_sqrt, beta1, beta2, eps,
-                          weight_decay, clip, reinterpret_cast<const Hyper *>(next), s) != 0)
+                          weight_decay, clip, PlanHyper(p, next).ptr(), s) != 0)
         return fail(TA3N_ERR_HIP, std::string("adam launch failed: ") + hipGetErrorString(hipGetLastError()));
     return TA3N_OK;
 }

@@ -108,12 +108,14 @@ struct StepScalars {
     int valid_source, valid_target;
     float inv_n_cls, inv_n_rel, inv_n_vid, inv_n_frm, inv_n_ent, gamma, beta1, p_drop_v;
     uint32_t seed_v;
+    float k_src, k_tgt;          // weighted domain criterion (ta3n_kernels.h: domain_coef); the class weights' offset is read where they are used
 };
 __device__ __forceinline__ StepScalars step_scalars(const Hyper *__restrict__ hy) {
     StepScalars h;
     h.valid_source = hy->valid_source; h.valid_target = hy->valid_target;
     h.inv_n_cls = hy->inv_n_cls; h.inv_n_rel = hy->inv_n_rel; h.inv_n_vid = hy->inv_n_vid; h.inv_n_frm = hy->inv_n_frm;
     h.inv_n_ent = hy->inv_n_ent; h.gamma = hy->gamma; h.beta1 = hy->beta[1]; h.p_drop_v = hy->p_drop_v; h.seed_v = hy->seed_v;
+    h.k_src = domain_factor(hy->dom_k[0]); h.k_tgt = domain_factor(hy->dom_k[1]);
     return h;
 }
 
@@ -454,8 +456,12 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
             const bool ent_on = (g.flags & TA3N_FLAG_ATTN_ENTROPY) && valid;
             const float ce = hs.gamma * hs.inv_n_ent;
             if (cls_on) {                                                              // main.py:446
-                gy = class_ce_grad(pr, lane == label, hs.inv_n_cls);
-                if (lane == label) l_cls = -lp * hs.inv_n_cls;
+                // (TA3N_FLAG_CLASS_WEIGHTS: the lead wave's own sum over the step's labels, here - behind a branch the unweighted kernel already
+                // has - and not at the top: the unweighted kernel keeps its front and its stage D.  The branch is wave-uniform: all 64 lanes are on.)
+                float k_cls = hs.inv_n_cls;
+                if (g.flags & TA3N_FLAG_CLASS_WEIGHTS) k_cls = class_coef(class_rule(g, wsr, hy->class_w_off, hs.valid_source, hs.inv_n_cls, lane), label);
+                gy = class_ce_grad(pr, lane == label, k_cls);
+                if (lane == label) l_cls = -lp * k_cls;
             }
             if (ent_on) {                                                              // loss.py:20-24
                 gy += ce * (1.f + s.H) * dH_dz(pr, lp, Hc);
@@ -463,7 +469,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
             }
             if (lane >= C) gy = 0.f;
             if ((g.flags & TA3N_FLAG_ADV_VIDEO) && valid) {                           // main.py:508-538, l = 1
-                const DomainCe c = domain_ce(s, is_src, hs.inv_n_vid);
+                const DomainCe c = domain_ce(s, is_src, domain_coef(hs.inv_n_vid, is_src, hs.k_src, hs.k_tgt));
                 g0 = c.g0; g1 = c.g1; if (lane == 0) l_vid = c.l;
             }
             if (ent_on) {
@@ -583,7 +589,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
             const Soft2 s = soft2(z0, z1);
             float g0 = 0.f, g1 = 0.f;
             if (adv_rel) {                                                             // main.py:508-538, l = 0
-                const DomainCe c = domain_ce(s, is_src, hs.inv_n_rel);
+                const DomainCe c = domain_ce(s, is_src, domain_coef(hs.inv_n_rel, is_src, hs.k_src, hs.k_tgt));
                 g0 = c.g0; g1 = c.g1; if (lane == 0) l_rel += c.l;
             }
             if (lane == 0) { ws[g.o_gPr + bj * 2] = g0; ws[g.o_gPr + bj * 2 + 1] = g1; }
@@ -687,7 +693,7 @@ __device__ __forceinline__ void frame_wg(const Geom g, const Ptrs ptrs, float *s
             float g0 = 0.f, g1 = 0.f;
             if (adv && valid) {                                                        // main.py:508-538, l = 2
                 const Soft2 s = soft2(d0[i], d1[i]);
-                const DomainCe c = domain_ce(s, b < g.Bs, hs.inv_n_frm);
+                const DomainCe c = domain_ce(s, b < g.Bs, domain_coef(hs.inv_n_frm, b < g.Bs, hs.k_src, hs.k_tgt));
                 g0 = c.g0; g1 = c.g1; l_frm += c.l;
             }
             if (lane == 0) {

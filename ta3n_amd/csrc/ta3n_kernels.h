@@ -11,6 +11,7 @@
 #endif
 #include <hip/hip_runtime.h>
 
+#include "../../include/ta3n_hip.h"
 #include "ta3n_types.h"
 
 namespace ta3n {
@@ -198,6 +199,30 @@ __device__ __forceinline__ LaneSoft lane_log_softmax(float y, bool on) {
 // gH = (ga wa + gb wb) [h > 0]: the way back through a 2-wide output layer and the ReLU in front of it.  The fmaf is written out (gb wb is rounded on its own): left to contraction, which product that is changes with the code around the sum.
 __device__ __forceinline__ float relu_back2(float h, float ga, float wa, float gb, float wb) { return h > 0.f ? fmaf(ga, wa, gb * wb) : 0.f; }
 __device__ __forceinline__ float class_ce_grad(float p, bool is_label, float inv_n_cls) { return (p - (is_label ? 1.f : 0.f)) * inv_n_cls; }   // main.py:446
+// Weighted criteria (main.py:160-167, 205-206: CrossEntropyLoss(weight = w), mean reduction = sum_i w[y_i] ce_i / sum_i w[y_i]).
+// Class CE (TA3N_FLAG_CLASS_WEIGHTS): the coefficient of a row, handed to class_ce_grad and the loss term in place of inv_n_cls, is
+// w[label] / sum_j w[label_j] over the valid source rows of the step.  Every wave that needs it forms the sum itself, from ws["labels"] and
+// ws["class_w"]: lane l adds rows l, l + 64, ... in order, then wave_allreduce_sum - the same bits in every workgroup of every launch of
+// the step, with no launch of its own and nothing from the host (device-gathered batches: the labels arrive in the step's opening launch).
+// Rows at and past valid_source (padding) never enter; a label outside [0, C) adds nothing.  All 64 lanes must be active at the call.
+struct ClassRule { const float *w; float inv; int C; };      // w == nullptr: unweighted, inv = inv_n_cls; otherwise inv = 1 / sum_j w[label_j]
+__device__ __forceinline__ ClassRule class_rule(const Geom &g, const float *__restrict__ ws, int class_w_off, int valid_source, float inv_n_cls, int lane) {
+    if (!(g.flags & TA3N_FLAG_CLASS_WEIGHTS) || class_w_off <= 0) return {nullptr, inv_n_cls, g.C};
+    const float *__restrict__ w = ws + class_w_off;
+    const int *__restrict__ labels = reinterpret_cast<const int *>(ws + g.o_labels);
+    const int n = valid_source < g.Bs ? valid_source : g.Bs;
+    float acc = 0.f;
+    for (int j = lane; j < n; j += 64) {
+        const int l = labels[j];
+        acc += (unsigned)l < (unsigned)g.C ? w[l] : 0.f;
+    }
+    const float sum = wave_allreduce_sum(acc);
+    return {w, sum > 0.f ? 1.f / sum : 0.f, g.C};
+}
+__device__ __forceinline__ float class_coef(const ClassRule &r, int label) { return r.w ? ((unsigned)label < (unsigned)r.C ? r.w[label] * r.inv : 0.f) : r.inv; }
+// Domain CE: 1 / n of the level times the step's factor for the row's domain (ta3n_hyper.dom_k; 0 is read as 1: unweighted, and x * 1.f = x bit for bit)
+__device__ __forceinline__ float domain_factor(float k) { return k != 0.f ? k : 1.f; }
+__device__ __forceinline__ float domain_coef(float inv_n, bool is_src, float k_src, float k_tgt) { return inv_n * (is_src ? k_src : k_tgt); }
 // One value / four values to the bf16 twin (TA3N_FLAG_BF16_STORE): the hi plane and, with pair twins (Geom::pair_delta floats further on), the lo plane
 __device__ __forceinline__ void twin1(unsigned short *__restrict__ tw, int64_t pair_delta, float v) {
     const unsigned h = pack_bf16(v, 0.f);

@@ -323,6 +323,12 @@ int finish_plan(ta3n_plan &p, Builder &b, std::string &err) {
     }
     for (auto &t : p.tasks)      // (after the twin re-addressing: the copies must be the final Segs)
         if (t.seg_count > 0) t.seg0 = p.segs[t.seg_begin];
+    // TA3N_FLAG_CLASS_WEIGHTS: the per-class weights of the class cross-entropy, written by the caller.  Behind everything else and only
+    // under the flag: no other plan changes by a byte.  Reached through Hyper::class_w_off (Geom's layout is fixed).
+    if (p.cfg.flags & TA3N_FLAG_CLASS_WEIGHTS) {
+        p.class_w_off = b.add_region("class_w", 64);
+        if (!workspace_fits(p, err)) return TA3N_ERR_INVALID;
+    }
     return TA3N_OK;
 }
 
@@ -1114,6 +1120,10 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     if (d.D <= 0 || d.F <= 0 || d.C <= 0) { err = "feature_dim, fc_dim and num_class must be positive"; return TA3N_ERR_INVALID; }
     if (d.NB <= 0 || d.NB % 64 != 0 || d.NB > 1024) { err = "num_bottleneck must be a multiple of 64 (<= 1024)"; return TA3N_ERR_INVALID; }
     if (d.C > 64) { err = "num_class > 64 not supported by the loss kernel"; return TA3N_ERR_INVALID; }
+    if ((c.flags & TA3N_FLAG_CLASS_WEIGHTS) && d.Bs <= 0) {
+        err = "TA3N_FLAG_CLASS_WEIGHTS (weighted class loss) without source rows: batch_source must be positive";
+        return TA3N_ERR_INVALID;
+    }
     if ((c.flags & TA3N_FLAG_ATTN_ENTROPY) &&
         !((c.flags & TA3N_FLAG_ADV_RELATION) && (c.flags & TA3N_FLAG_ADV_VIDEO))) {
         // main.py:559-562 indexes pred_domain_all[1]; that is the video entry only when

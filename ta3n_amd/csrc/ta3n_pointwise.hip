@@ -225,6 +225,10 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
     const int n_vid = B, n_rel = B * NR, n_frm = B * T;
     const int rid = blockIdx.x * blockDim.x + threadIdx.x;
     float l_cls = 0.f, l_rel = 0.f, l_vid = 0.f, l_frm = 0.f, l_ent = 0.f;
+    // (only the workgroups that hold video rows form the sum of the weights - block-uniform, every wave of them with all lanes on)
+    const ClassRule cr = (int)(blockIdx.x * blockDim.x) < n_vid ? class_rule(g, ws, hy->class_w_off, hy->valid_source, hy->inv_n_cls, threadIdx.x & 63)
+                                                                : ClassRule{nullptr, hy->inv_n_cls, C};
+    const float k_src = domain_factor(hy->dom_k[0]), k_tgt = domain_factor(hy->dom_k[1]);
     if (rid < n_vid) {
         const int b = rid;
         const bool is_src = b < g.Bs;
@@ -244,7 +248,8 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
         }
         const bool cls_on = is_src && valid;
         const int lab = cls_on ? labels[b] : -1;
-        if (cls_on) l_cls = -(y[lab] - m - ls) * hy->inv_n_cls;                      // main.py:446
+        const float k_cls = class_coef(cr, lab);
+        if (cls_on) l_cls = -(y[lab] - m - ls) * k_cls;                              // main.py:446
         const float z0 = ws[g.o_Pv + (size_t)b * 2], z1 = ws[g.o_Pv + (size_t)b * 2 + 1];
         const Soft2 s = soft2(z0, z1);
         const bool ent_on = (g.flags & TA3N_FLAG_ATTN_ENTROPY) && valid;
@@ -254,7 +259,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
             const float lp = y[i] - m - ls;
             const float p = expf(lp);
             float gi = 0.f;
-            if (cls_on) gi = class_ce_grad(p, i == lab, hy->inv_n_cls);
+            if (cls_on) gi = class_ce_grad(p, i == lab, k_cls);
             if (ent_on) gi += ce * (1.f + s.H) * dH_dz(p, lp, Hc);
             gy[i] = gi;
         }
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
         // ("add dummy tensors", models.py:707-708), so place_adv[0] = 'Y' adds the video-level CE a second time.
         const float vmult = ((g.flags & TA3N_FLAG_ADV_VIDEO) ? 1.f : 0.f) + ((NR == 0 && (g.flags & TA3N_FLAG_ADV_RELATION)) ? 1.f : 0.f);
         if (vmult > 0.f && valid) {                                                  // main.py:508-538, l = 1 (and l = 0 for avgpool)
-            const DomainCe c = domain_ce(s, is_src, hy->inv_n_vid);
+            const DomainCe c = domain_ce(s, is_src, domain_coef(hy->inv_n_vid, is_src, k_src, k_tgt));
             l_vid = c.l * vmult; g0 = c.g0 * vmult; g1 = c.g1 * vmult;
         }
         if (ent_on) {
@@ -283,7 +288,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
         float g0 = 0.f, g1 = 0.f;
         if (on) {
             const float inv_n = is_rel ? hy->inv_n_rel : hy->inv_n_frm;
-            const DomainCe c = domain_ce(soft2(z[0], z[1]), is_src, inv_n);
+            const DomainCe c = domain_ce(soft2(z[0], z[1]), is_src, domain_coef(inv_n, is_src, k_src, k_tgt));
             g0 = c.g0; g1 = c.g1; if (is_rel) l_rel = c.l; else l_frm = c.l;
         }
         gz[0] = g0; gz[1] = g1;
@@ -469,8 +474,10 @@ __global__ __launch_bounds__(256) void pool_cls_kernel(Geom g, Ptrs ptrs) {
         const bool on = video_valid(g.Bs, hy->valid_source, 0, b);
         const int label = on ? reinterpret_cast<const int32_t *>(ws + g.o_labels)[b] : -1;
         const float lp = lane_log_softmax(lane < C ? s_y[lane] : -INFINITY, lane < C).lp;
-        const float gy = (on && lane < C) ? class_ce_grad(expf(lp), lane == label, hy->inv_n_cls) : 0.f;
-        const float l = wave_allreduce_sum((on && lane == label) ? -lp * hy->inv_n_cls : 0.f);
+        const ClassRule cr = class_rule(g, ws, hy->class_w_off, hy->valid_source, hy->inv_n_cls, lane);
+        const float k_cls = on ? class_coef(cr, label) : 0.f;
+        const float gy = (on && lane < C) ? class_ce_grad(expf(lp), lane == label, k_cls) : 0.f;
+        const float l = wave_allreduce_sum((on && lane == label) ? -lp * k_cls : 0.f);
         if (lane < C) ws[g.o_gY + (size_t)b * C + lane] = gy;
         if (lane < 8) ws[g.o_loss_part + (size_t)b * 8 + lane] = lane < 2 ? l : 0.f;   // {loss, loss_c, 0 ...}: losses region layout
     }
@@ -622,6 +629,9 @@ __global__ __launch_bounds__(1024) void eval_metrics_kernel(Geom g, float *__res
     if (reset)
         for (int i = threadIdx.x; i < C * C; i += 1024) conf[i] = 0;
     __syncthreads();
+    // TA3N_FLAG_CLASS_WEIGHTS: main.validate's criterion(pred, label) is the weighted mean of THIS batch (main.py:725), averaged over batches by
+    // batch size: metrics[0] += n * sum_b w[y_b] ce_b / sum_b w[y_b]
+    const ClassRule cr = class_rule(g, ws, reinterpret_cast<const Hyper *>(ws + g.o_hyper)->class_w_off, n, 1.f, lane);
     float ce = 0.f, t1 = 0.f, t5 = 0.f;
     for (int b = wv; b < n; b += 16) {
         const float y = lane < C ? ws[g.o_Y + (size_t)b * C + lane] : -INFINITY;
@@ -635,7 +645,8 @@ __global__ __launch_bounds__(1024) void eval_metrics_kernel(Geom g, float *__res
         float amin = myahead_key;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) amin = fminf(amin, __shfl_xor(amin, off, 64));
-        ce += -(ylab - sm.m - sm.ls);
+        const float ce_b = -(ylab - sm.m - sm.ls);
+        ce += cr.w ? (((unsigned)lab < (unsigned)C ? cr.w[lab] : 0.f) * ce_b) : ce_b;
         t1 += ahead < 1.f ? 1.f : 0.f;
         t5 += ahead < 5.f ? 1.f : 0.f;
         if (lane == 0 && lab >= 0 && lab < C) atomicAdd(&conf[lab * C + (int)amin], 1);
@@ -644,7 +655,9 @@ __global__ __launch_bounds__(1024) void eval_metrics_kernel(Geom g, float *__res
     __syncthreads();
     if (threadIdx.x < 3) {
         float v = reset ? 0.f : ws[g.o_metrics + threadIdx.x];
-        for (int w = 0; w < 16; ++w) v += part[w][threadIdx.x];
+        float s = 0.f;
+        for (int w = 0; w < 16; ++w) { if (cr.w && threadIdx.x == 0) s += part[w][0]; else v += part[w][threadIdx.x]; }
+        if (cr.w && threadIdx.x == 0) v += (float)n * (s * cr.inv);
         ws[g.o_metrics + threadIdx.x] = v;
     }
     if (threadIdx.x == 3) ws[g.o_metrics + 3] = (reset ? 0.f : ws[g.o_metrics + 3]) + (float)n;
@@ -1110,14 +1123,15 @@ __global__ __launch_bounds__(256) void mcd_source_loss_kernel(Geom g, float *__r
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= g.B) return;
     const int C = g.C, ns = hy->valid_source;
-    const float inv = hy->inv_n_cls;
+    const ClassRule cr = class_rule(g, ws, hy->class_w_off, ns, hy->inv_n_cls, lane);
     const bool on = lane < C;
     float g2 = 0.f, term = 0.f;
     if (video_valid(g.Bs, ns, 0, b)) {
         const int label = reinterpret_cast<const int *>(ws + g.o_labels)[b];
         const RowSoft r = row_soft(on ? ws[g.o_Y2 + (size_t)b * C + lane] : 0.f, on);
-        g2 = class_ce_grad(expf(r.lp), lane == label, inv);
+        g2 = class_ce_grad(expf(r.lp), lane == label, class_coef(cr, label));
         term = -wave_allreduce_sum(lane == label ? r.lp : 0.f);
+        if (cr.w) term *= (unsigned)label < (unsigned)C ? cr.w[label] : 0.f;      // (the finish kernel scales the sum by 1 / sum_j w[label_j] in place of inv_n_cls)
     }
     if (on) {
         ws[g.o_gY2 + (size_t)b * C + lane] = g2;
@@ -1174,7 +1188,8 @@ __global__ __launch_bounds__(64) void mcd_finish_kernel(const float *__restrict_
         float acc = 0.f;
         for (int i = threadIdx.x; i < n; i += 64) acc += part[i];
         acc = wave_allreduce_sum(acc);
-        if (threadIdx.x == 0) out[0] = acc * hy->inv_n_cls;
+        const ClassRule cr = class_rule(g, ws, hy->class_w_off, n, hy->inv_n_cls, (int)threadIdx.x);
+        if (threadIdx.x == 0) out[0] = acc * cr.inv;
         return;
     }
     const int n = hy->valid_target;

@@ -137,7 +137,8 @@ struct Hyper {
     int32_t reverse;             // forward(..., reverse=True): GradReverse(mu) between dropout_v and the video heads (models.py:682-684)
     float mu;
     int32_t bn_eval_target;      // eval mode (train == 0): every row through the target domain's BatchNorm (main.validate, main.py:707)
-    int32_t reserved[1];
+    int32_t class_w_off;         // ws offset of the class weights (TA3N_FLAG_CLASS_WEIGHTS: region "class_w"), 0: none.  Filled by the library from the plan
+    float dom_k[2];              // [source, target] factor on the per-row coefficient of every domain CE (weighted criterion_domain); 0 reads as 1
 };
 
 // Columns per workgroup of the two BatchNorm launches (TA3N_FLAG_BN_SHARED): a thread moves the BN_COLS columns of one row as one 16-byte

@@ -133,6 +133,73 @@ def adam_refusal(world: int = 1, sharded_update: bool = False, process_group: bo
     return f"optimizer Adam together with {', '.join(what)} is not built (Adam: single rank, the update as one launch behind the step)" if what else ""
 
 
+def class_weights_from_list(list_file: str, num_class: int):
+    """The class weights of --weighted_class_loss Y, main.py:156-164: 1 / (share of each class among the lines of the source list, whose
+    third blank-separated field is the class id).  A class of the class file that the list does not hold would leave the reference with
+    fewer weights than classes (np.unique; CrossEntropyLoss then fails on the size): raised here, naming the class."""
+    counts = [0] * int(num_class)
+    with open(list_file) as f:
+        for line in f:
+            c = int(line.strip().split(" ")[2])
+            if not 0 <= c < num_class:
+                raise ValueError(f"{list_file}: class id {c} outside [0, {num_class})")
+            counts[c] += 1
+    total = sum(counts)
+    missing = [c for c, n in enumerate(counts) if n == 0]
+    if missing:
+        raise ValueError(f"--weighted_class_loss Y: class {missing[0]} of the class file has no video in {list_file} "
+                         f"(1 / class_freq is undefined; the reference fails on the weight's size)")
+    import numpy as np
+    freq = np.asarray([n / total for n in counts], dtype=np.float32)      # 1 / torch.Tensor(class_freq): the division in fp32
+    return [float(v) for v in (np.float32(1.0) / freq)]
+
+
+def domain_factors(domain_weights: Optional[Sequence[float]], n_source: int, n_target: int):
+    """(k_s, k_t) of ta3n_hyper.dom_k: CrossEntropyLoss(weight=(w_s, w_t)) over r n_s source and r n_t target rows is the unweighted mean
+    with every source row's coefficient times k_s = w_s (n_s + n_t) / (w_s n_s + w_t n_t) and every target row's times k_t (the same at the
+    relation, video and frame level: r cancels).  No weights: (0, 0), which the kernels read as (1, 1)."""
+    if domain_weights is None:
+        return 0.0, 0.0
+    ws_, wt_ = float(domain_weights[0]), float(domain_weights[1])
+    den = ws_ * n_source + wt_ * n_target
+    if den <= 0.0:
+        return 0.0, 0.0
+    return ws_ * (n_source + n_target) / den, wt_ * (n_source + n_target) / den
+
+
+def weights_refusal(class_weights=None, domain_weights=None, num_class: int = 0, world: int = 1, process_group: bool = False,
+                    ddp_selftest: bool = False) -> str:
+    """The message of weights_refusal_kind (''  when nothing is refused)."""
+    return weights_refusal_kind(class_weights, domain_weights, num_class=num_class, world=world, process_group=process_group,
+                                ddp_selftest=ddp_selftest)[1]
+
+
+def weights_refusal_kind(class_weights=None, domain_weights=None, num_class: int = 0, world: int = 1, process_group: bool = False,
+                         ddp_selftest: bool = False):
+    """(exception type, message): (None, '') when the weighted criteria (class_weights: --weighted_class_loss, domain_weights: --weighted_class_loss_DA) are built as asked,
+    otherwise the message that refuses them.  The class weights' normaliser sum_j w[y_j] is taken by the kernels over the rank's own rows:
+    single rank.  The domain factors are formed from the global counts: any world.  ValueError: a value that no configuration
+    accepts; NotImplementedError: a combination that is not built."""
+    if class_weights is not None:
+        w = [float(v) for v in class_weights]
+        if len(w) != num_class:
+            return ValueError, f"class_weights has {len(w)} entries for {num_class} classes"
+        if any(not (v > 0.0 and math.isfinite(v)) for v in w):
+            return ValueError, "class_weights must be positive and finite (1 / class_freq, main.py:164)"
+        what = [t for t, on in ((f"world size {world} (a process group)", world > 1 or process_group),
+                                ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest)) if on]
+        if what:
+            return NotImplementedError, (f"class_weights together with {', '.join(what)} is not built (the weighted mean divides by the sum of the weights of the "
+                    f"rank's own labels: single rank)")
+    if domain_weights is not None:
+        d = [float(v) for v in domain_weights]
+        if len(d) != 2:
+            return ValueError, f"domain_weights has {len(d)} entries, takes (w_source, w_target)"
+        if any(not (v > 0.0 and math.isfinite(v)) for v in d):
+            return ValueError, "domain_weights must be positive and finite (1 / num_source_train, 1 / num_target_train; main.py:167)"
+    return None, ""
+
+
 class TrainEngine:
     """Device-resident state of one rank: flat parameters / gradients / momentum,
     workspace, static input buffers.  Source rows come first in every batch
@@ -148,7 +215,18 @@ class TrainEngine:
                  dis_DA: str = "none", place_dis: Sequence[str] = ("N", "Y", "N"), alpha: float = 0.0, use_bn: str = "none",
                  ens_DA: str = "none", mu: float = 0.0, split_k: Optional[int] = None, sharded_update: Optional[bool] = None,
                  peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False,
-                 add_fc: int = 1, optimizer: str = "SGD", betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8):
+                 add_fc: int = 1, optimizer: str = "SGD", betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8,
+                 class_weights: Optional[Sequence[float]] = None, domain_weights: Optional[Sequence[float]] = None):
+        # --weighted_class_loss / --weighted_class_loss_DA (reference main.py:156-167, 205-206): the two criteria as CrossEntropyLoss(weight=...).
+        # class_weights: TA3N_FLAG_CLASS_WEIGHTS and the C weights in workspace region "class_w" - every class cross-entropy of the step, MCD's
+        # second classifier and the validation metrics divide by the sum of the weights of the batch's labels, formed inside the kernels.
+        # domain_weights (w_s, w_t): two per-step factors in ta3n_hyper.dom_k, from the step's global valid counts (set_hyper).
+        kind, refused = weights_refusal_kind(class_weights, domain_weights, num_class=num_class, process_group=process_group is not None,
+                                             ddp_selftest=os.environ.get("TA3N_DDP_SELFTEST") == "1")
+        if kind is not None:
+            raise kind(refused)
+        self.class_weights = None if class_weights is None else tuple(float(v) for v in class_weights)
+        self.domain_weights = None if domain_weights is None else (float(domain_weights[0]), float(domain_weights[1]))
         # --optimizer Adam (reference main.py:84-86): clip + torch.optim.Adam as ONE launch over the flat live prefix behind the step's
         # gradients (include/ta3n_hip.h: ta3n_adam_range) - the same for every model variant.  self.M is exp_avg, self.V exp_avg_sq,
         # self.adam_step_count the number of updates applied.  The schedules that overlap or shard the SGD update are not built for it.
@@ -178,6 +256,8 @@ class TrainEngine:
         self.add_fc = int(add_fc)
         if flags is None:        # default: the full TA3N configuration for trn-m, the source-only one (BASELINE configs[0]) for avgpool
             flags = ALL_FLAGS if aggregation == "trn-m" else 0
+        if self.class_weights is not None:
+            flags |= _lib.FLAG_CLASS_WEIGHTS
         # use_attn_frame TransAttn (TA3N_FLAG_FRAME_ATTN in `flags`, flags_from_options(use_attn_frame=...); models.py:368-377, 612-614): the
         # frame features enter the TRN scaled by 1 + (1 - H(frame-discriminator softmax)).  The frame discriminator's logits come before the
         # tuple products and its backward behind the TRN input gradient: the unfused launch lists with two more pointwise launches.
@@ -288,6 +368,8 @@ class TrainEngine:
             self.rank = torch.distributed.get_rank(process_group)
         if self.optimizer == "Adam" and self.world > 1:
             raise NotImplementedError(adam_refusal(world=self.world))
+        if self.class_weights is not None and self.world > 1:
+            raise NotImplementedError(weights_refusal(self.class_weights, None, num_class=num_class, world=self.world))
         # The DA options under more than one rank follow what the reference's nn.DataParallel does with them (main.py:79): the discrepancy
         # loss is taken on the gathered global batch (discrepancy()); MCD's discrepancy is a mean over the global target batch
         # (mcd_second_forward()); BatchNorm statistics are PER REPLICA - each replica normalises its own slice of the batch with its own
@@ -319,6 +401,12 @@ class TrainEngine:
                 # form of rounds 4-5, kept for A/B): per-row terms [3 B] + the four scalars {loss_c2, loss_s, d total, d loss_e} at the end
                 self._mcd_buf = torch.zeros(3 * self.B + 4, dtype=torch.float32, device=self.device)
         self._mcd_native = self.ens_DA == "MCD" and os.environ.get("TA3N_NATIVE_MCD", "1") != "0"
+        if self.class_weights is not None:      # region "class_w": once, into every workspace whose launches take a class cross-entropy
+            w = torch.tensor(self.class_weights, dtype=torch.float32, device=self.device)
+            off, _ = p.region("class_w")
+            for ws in (self.ws, self.ws2):
+                if ws is not None:
+                    ws[off:off + self.C].copy_(w)
         # fused: forward + loss + backward as ONE C-ABI call (ta3n_train_step, 7 launches) when the plan has it
         self.fused = bool(fused) and p.has_fused_step
         # ... and where it has not (trn-m: fc_dim > 2048 - the heads kernel keeps ceil(F / 64) <= 32 frame channels per lane) the step runs
@@ -419,7 +507,9 @@ class TrainEngine:
         arith = "bf16" if self.bf16 else "f32x3" if self._flags & _lib.FLAG_F32_SPLIT else "fp32"
         step = "fused step" if self.fused else "unfused launch lists" + (f" ({self.fused_fallback})" if self.fused_fallback else "")
         return (f"TrainEngine {self.Bs}+{self.Bt} videos x {self.T} segments, feature_dim {self.D}, fc_dim {self.F}, {self.C} classes, "
-                f"{self.aggregation}, {arith}{' on twins' if self.bf16_store else ''}, {self.optimizer}, world {self.world}: {step}")
+                f"{self.aggregation}, {arith}{' on twins' if self.bf16_store else ''}, {self.optimizer}, world {self.world}"
+                f"{', class weights' if self.class_weights is not None else ''}"
+                f"{', domain weights ({:.3g}, {:.3g})'.format(*self.domain_weights) if self.domain_weights is not None else ''}: {step}")
 
     # ---- plumbing ----
     def _stream(self) -> C.c_void_p:
@@ -556,6 +646,7 @@ class TrainEngine:
             setattr(h, k, v)
         h.valid_source, h.valid_target, h.train = int(ns), int(nt), int(bool(train))
         h.bn_eval_target = int(bn_eval_target)
+        h.dom_k[0], h.dom_k[1] = domain_factors(getattr(self, "domain_weights", None), int(gs), int(gt))      # (0, 0) = unweighted
         self._global_source, self._global_target = int(gs), int(gt)
         if not upload:      # the caller delivers self._hyper another way (ta3n_sgd_step_next)
             return
@@ -649,10 +740,13 @@ class TrainEngine:
             lab = self._labels[:ns].long()
             lp = torch.log_softmax(y2[:ns], 1)
             inv = float(self._hyper.inv_n_cls)
+            if self.class_weights is not None:      # per-row coefficient w[y_i] / sum_j w[y_j] in place of 1 / n
+                wl = torch.tensor(self.class_weights, dtype=torch.float32, device=self.device)[lab]
+                inv = (wl / wl.sum())[:, None]
             g = lp.exp()
             g[torch.arange(ns, device=self.device), lab] -= 1.0
             g2[:ns] = g * inv
-            self.loss_c2 = -(lp[torch.arange(ns, device=self.device), lab]).sum() * inv
+            self.loss_c2 = -(lp[torch.arange(ns, device=self.device), lab] * (inv[:, 0] if self.class_weights is not None else inv)).sum()
         else:
             self.loss_c2 = y2.new_zeros(())
 

@@ -73,8 +73,11 @@ def validate_options(args, module_path: bool = False) -> None:
         need(args.use_bn in ("none", "AdaBN", "AutoDIAL"), f"--use_bn {args.use_bn}")
     need(args.add_loss_DA in ("none", "attentive_entropy"), f"--add_loss_DA {args.add_loss_DA} (built: attentive_entropy)")
     need(args.use_target in ("none", "uSv"), f"--use_target {args.use_target} (target labels in the classification loss are not built)")
-    need(args.weighted_class_loss == "N", "--weighted_class_loss Y")
-    need(args.weighted_class_loss_DA == "N", "--weighted_class_loss_DA Y")
+    # --weighted_class_loss / --weighted_class_loss_DA (main.py:156-167, 205-206): main.py builds the two weighted criteria and trains them on
+    # the engine (TrainEngine class_weights / domain_weights; the class weights' sum is per rank: single rank)
+    if not module_path:
+        need(args.weighted_class_loss == "N", "--weighted_class_loss Y (built on main.py)")
+        need(args.weighted_class_loss_DA == "N", "--weighted_class_loss_DA Y (built on main.py)")
     need(args.pred_normalize == "N", "--pred_normalize Y")
     need(not args.pretrain_source, "--pretrain_source")
     need(args.lr_adaptive in ("dann", "none"), f"--lr_adaptive {args.lr_adaptive} (built: dann, none with --lr_steps/--lr_decay)")
