@@ -103,6 +103,23 @@ typedef enum {
  * ta3n_hyper.valid_source, in a fixed order, so batches gathered on the device and K-step calls need nothing from the host.  The sum is over
  * THIS rank's rows: single rank.  ta3n_hyper.inv_n_cls is not used under the flag. */
 #define TA3N_FLAG_CLASS_WEIGHTS  (1u << 12)
+/* --use_target Sv (main.py:439-446): the class cross-entropy runs over the valid rows of BOTH halves,
+ * criterion(cat(out_source, out_target), cat(label_source, label_target)).  The label of target video j is region "labels"[Bs + j] (the
+ * region has Bs + Bt entries in every plan); the caller writes it there, or the batch assembly does (under the flag the target feed's
+ * labels go there: ta3n_feed.labels of the target feed is then required; ta3n_gather_segments_into takes labels_out as before).  Padding rows
+ * never enter.  Unweighted, the per-row coefficient is ta3n_hyper.inv_n_cls, which the caller sets to 1 / (n_s + n_t) from the global valid
+ * counts; with TA3N_FLAG_CLASS_WEIGHTS the sum of the weights runs over the valid rows of both halves, the target range added behind the
+ * source range in a fixed order.  No new launch, no new region: a plan with the flag differs from the one without it in `flags` alone.
+ * Single rank.  ta3n_plan_create refuses it by name with TA3N_FLAG_MCD (the reference itself fails there, main.py:448), with
+ * batch_target == 0, and on the source-only TA3N_AGG_AVGPOOL plan (no adversarial / module-path flag: there are no target rows to label). */
+#define TA3N_FLAG_TARGET_LABELS  (1u << 13)
+/* --add_loss_DA target_entropy (main.py:542-545, loss.py:8-12): loss += gamma * mean over the valid target rows of H(softmax(y_b)).  Per
+ * valid target row the entropy slot of region "losses" gets H * inv_n_ent and the class logits gamma * inv_n_ent * dH/dz; source rows and
+ * the domain logits get nothing (no (1 + H_d) factor).  The caller sets ta3n_hyper.inv_n_ent = 1 / n_t (global valid target count); a step
+ * without a valid target row is the caller's to refuse (the reference's mean over no rows is NaN).  Needs neither TA3N_FLAG_TRANS_ATTN nor
+ * an ADV flag.  ta3n_plan_create refuses it by name together with TA3N_FLAG_ATTN_ENTROPY (one entropy slot, one --add_loss_DA value), with
+ * TA3N_FLAG_MCD (MCD rebinds out_target to the second pass's logits: not built) and on TA3N_AGG_AVGPOOL. */
+#define TA3N_FLAG_TARGET_ENTROPY (1u << 14)
 
 /* ta3n_config.aggregation */
 #define TA3N_AGG_TRN_M    0   /* 'trn-m': multi-scale TRN - the TA3N path (TRNmodule.py:27-86) */

@@ -26,7 +26,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from ta3n_amd.dataset import TSNDataSet  # noqa: E402
-from ta3n_amd.loss import JAN, attentive_entropy, dis_MCD, mmd_rbf  # noqa: E402
+from ta3n_amd.loss import JAN, attentive_entropy, cross_entropy_soft, dis_MCD, mmd_rbf  # noqa: E402
 from ta3n_amd.models import VideoModel  # noqa: E402
 from ta3n_amd import accel as _accel  # noqa: E402
 from ta3n_amd.engine import class_weights_from_list  # noqa: E402
@@ -211,6 +211,10 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
     mcd = args.ens_DA == "MCD"      # (likewise ens_DA MCD: both passes' launch lists + ta3n_mcd_source_loss / ta3n_mcd_second_loss, 0.44 ms per step)
     if mcd and (args.use_target == "none" or args.use_bn != "none"):
         return None
+    # --use_target Sv / --add_loss_DA target_entropy (TA3N_FLAG_TARGET_LABELS / _TARGET_ENTROPY): on the engine, single rank, not with MCD
+    sv, tent = args.use_target == "Sv", args.add_loss_DA == "target_entropy" and args.use_target != "none"
+    if (sv or tent) and mcd:
+        return None
     if dis and (args.use_target == "none" or args.use_bn != "none" or not hasattr(args, "place_dis") or len(args.place_dis) < 2 or
                 (args.dis_DA == "DAN" and (len(args.place_dis) > 2 and args.place_dis[2] == "Y"))):
         return None
@@ -245,7 +249,7 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
                           **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc, class_weights=class_w, domain_weights=domain_w)
         if not eng.fused and not (dis or mcd or attn_frame != "none"):
             return None
-        if class_w is not None or domain_w is not None:      # said once: the weighted criteria train on the engine
+        if class_w is not None or domain_w is not None or sv or tent:      # said once: the weighted criteria / target labels / target entropy train on the engine
             print("[ta3n] " + eng.describe(), flush=True)
         m.__dict__.setdefault("_main_fast_engine", {})[key] = eng
     return eng
@@ -294,7 +298,13 @@ def _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, 
             labels = torch.zeros(args.batch_size[0], dtype=torch.long)
             labels[:batch_source_ori] = source_label
             data_time.update(time.time() - end)
-            eng.set_batch(source_data.to(dev, non_blocking=True), target_data.to(dev, non_blocking=True), labels.to(dev, non_blocking=True))
+            labels_t = None
+            if eng.target_labels:                                           # use_target Sv: the target videos' labels behind the source's (:442-444)
+                labels_t = torch.zeros(args.batch_size[1], dtype=torch.long)
+                labels_t[:batch_target_ori] = target_label
+                labels_t = labels_t.to(dev, non_blocking=True)
+            eng.set_batch(source_data.to(dev, non_blocking=True), target_data.to(dev, non_blocking=True), labels.to(dev, non_blocking=True),
+                          target_label=labels_t)
             lr = optimizer.param_groups[0]["lr"]
             # the dropout seeds come from the global torch RNG exactly as VideoModel.forward draws them (one draw of two per train forward):
             # the same masks as the module path, and the same RNG state for the samplers of the next epoch
@@ -319,9 +329,13 @@ def _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, 
             if args.adv_DA != "none" and args.use_target != "none":
                 last = [r for r, on in zip((args.num_segments - 1, 1, args.num_segments), args.place_adv) if on == "Y"]   # (:537 weights by the LAST enabled level's rows)
                 losses_a.update(l["loss_adv_rel"] + l["loss_adv_vid"] + l["loss_adv_frm"], (batch_source_ori + batch_target_ori) * (last[-1] if last else 1))
-            if args.add_loss_DA == "attentive_entropy" and args.use_attn != "none" and args.use_target != "none":
+            if (args.add_loss_DA == "attentive_entropy" and args.use_attn != "none" and args.use_target != "none") or eng.target_entropy:   # (:544, :561)
                 losses_e.update(l["loss_e"], batch_target_ori)
-            prec1, prec5 = accuracy(out, source_label.to(dev), topk=(1, min(5, num_class)))
+            label = source_label.to(dev)
+            if eng.target_labels:      # :565-567: pred = out, the concatenation of :442-444 (the meters keep the weight n_s, :570-571)
+                out = torch.cat((out, eng.outputs()["out"][args.batch_size[0]:args.batch_size[0] + batch_target_ori]))
+                label = torch.cat((label, target_label.to(dev)))
+            prec1, prec5 = accuracy(out, label, topk=(1, min(5, num_class)))
             if dis:      # the term the loss kernel does not know (:452-505): logged, and part of the total like in the module path
                 ld = float(eng.loss_d)
                 losses_d.update(ld, batch_source_ori)
@@ -420,7 +434,9 @@ def train(num_class, source_loader, target_loader, model, criterion, criterion_d
             attn_source, out_source, out_source_2, pred_domain_source, feat_source, batch_source_ori)       # :421-422
         attn_target, out_target, out_target_2, pred_domain_target, feat_target = removeDummy(
             attn_target, out_target, out_target_2, pred_domain_target, feat_target, batch_target_ori)
-        out, label = out_source, label_source                                           # :439-451 (use_target uSv / none: source labels only)
+        out, label = out_source, label_source                                           # :439-451
+        if args.use_target == "Sv":                                                     # :442-444: the supervised-target upper bound
+            out, label = torch.cat((out, out_target)), torch.cat((label, target_label))
         loss_classification = criterion(out, label)
         if args.ens_DA == "MCD" and args.use_target != "none":                          # :446-447
             loss_classification = loss_classification + criterion(out_source_2, label)
@@ -472,6 +488,10 @@ def train(num_class, source_loader, target_loader, model, criterion, criterion_d
                     loss_adversarial = loss_adversarial + criterion_domain(pred_domain, domain_label)
             losses_a.update(loss_adversarial.item(), pred_domain.size(0))
             loss = loss + loss_adversarial
+        if args.add_loss_DA == "target_entropy" and args.use_target != "none":          # :542-545
+            loss_entropy = cross_entropy_soft(out_target)
+            losses_e.update(loss_entropy.item(), out_target.size(0))
+            loss = loss + gamma * loss_entropy
         if args.ens_DA == "MCD" and args.use_target != "none":                          # :548-556: the whole model once more, reversed
             _, _, _, _, _, attn_target, out_target, out_target_2, pred_domain_target, feat_target = model(
                 source_data, target_data, beta_new, mu, is_train=True, reverse=True)

@@ -30,6 +30,8 @@ FLAG_BF16_STORE = 1 << 9
 FLAG_F32_SPLIT = 1 << 10       # fp32-grade contractions as three bf16 MFMAs on operands split hi + lo in registers ("bf16x3")
 FLAG_FRAME_ATTN = 1 << 11      # use_attn_frame TransAttn: frame features scaled by 1 + (1 - H(frame-discriminator softmax)) in front of the TRN (regions F1a, attn_frame); unfused entry points
 FLAG_CLASS_WEIGHTS = 1 << 12   # --weighted_class_loss: every class CE weighted per class (region class_w, written by the caller); single rank
+FLAG_TARGET_LABELS = 1 << 13   # --use_target Sv: the class CE over the valid rows of both halves, target labels in region "labels"[Bs:]; single rank
+FLAG_TARGET_ENTROPY = 1 << 14  # --add_loss_DA target_entropy: gamma * mean entropy of the valid target rows' class softmax; exclusive with FLAG_ATTN_ENTROPY
 AGG_TRN_M, AGG_AVGPOOL = 0, 1
 
 # every symbol include/ta3n_hip.h declares (tests check the export list)

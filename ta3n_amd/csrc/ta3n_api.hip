@@ -617,13 +617,19 @@ int ta3n_train_step_after_update(ta3n_plan *p, const float *x, float *params, fl
     return run_group(p, 4, ptrs, nullptr, nullptr, s, nullptr, 1, 1 << 30);
 }
 
+// Where the target feed's labels go: ws["labels"][Bs:] under TA3N_FLAG_TARGET_LABELS (--use_target Sv), nowhere without it
+static int32_t *target_labels_out(const ta3n_plan *p, float *ws) {
+    const Geom &g = p->geom;
+    return (g.flags & TA3N_FLAG_TARGET_LABELS) ? reinterpret_cast<int32_t *>(ws + g.o_labels) + g.Bs : nullptr;
+}
+
 // One batch assembly of a multi-step call: rows [first_video, first_video + ids_per_step) of the input from a packed store.
 static int feed_step(ta3n_plan *p, const ta3n_feed *f, int step, int first_video, int cap, float *x, float *ws, int32_t *labels_out,
                      hipStream_t s) {
     const Geom &g = p->geom;
     if (!f->store || !f->first_row || !f->num_frames || !f->video_ids) return fail(TA3N_ERR_INVALID, "ta3n_feed: null table");
     if (f->ids_per_step < 0 || f->ids_per_step > cap) return fail(TA3N_ERR_INVALID, "ta3n_feed: ids_per_step exceeds the batch half");
-    if (labels_out && !f->labels) return fail(TA3N_ERR_INVALID, "ta3n_feed: the source feed needs labels");
+    if (labels_out && !f->labels) return fail(TA3N_ERR_INVALID, "ta3n_feed: the feed needs labels (the source feed; the target feed under TA3N_FLAG_TARGET_LABELS)");
     const int32_t *ids = f->video_ids + (size_t)step * f->ids_per_step;
     const size_t row0 = (size_t)first_video * g.T;
     float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
@@ -644,7 +650,7 @@ static int feed_job(ta3n_plan *p, const ta3n_feed *f, int step, int first_video,
     const Geom &g = p->geom;
     if (!f->store || !f->first_row || !f->num_frames || !f->video_ids) return fail(TA3N_ERR_INVALID, "ta3n_feed: null table");
     if (f->ids_per_step < 0 || f->ids_per_step > cap) return fail(TA3N_ERR_INVALID, "ta3n_feed: ids_per_step exceeds the batch half");
-    if (labels_out && !f->labels) return fail(TA3N_ERR_INVALID, "ta3n_feed: the source feed needs labels");
+    if (labels_out && !f->labels) return fail(TA3N_ERR_INVALID, "ta3n_feed: the feed needs labels (the source feed; the target feed under TA3N_FLAG_TARGET_LABELS)");
     const size_t row0 = (size_t)first_video * g.T;
     float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
     if (f->bf16 && !twin && !x) return fail(TA3N_ERR_INVALID, "ta3n_feed: a plan without bf16 twins needs the fp32 input rows");
@@ -669,7 +675,7 @@ static int enqueue_pipelined_step(ta3n_plan *p, const Ptrs &ptrs, float *params,
         FeedJob jobs[2];
         std::memset(jobs, 0, sizeof(jobs));
         if (source && (rc = feed_job(p, source, k, 0, g.Bs, const_cast<float *>(ptrs.x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), &jobs[0])) != TA3N_OK) return rc;
-        if (target && (rc = feed_job(p, target, k, g.Bs, g.Bt, const_cast<float *>(ptrs.x), ws, nullptr, &jobs[1])) != TA3N_OK) return rc;
+        if (target && (rc = feed_job(p, target, k, g.Bs, g.Bt, const_cast<float *>(ptrs.x), ws, target_labels_out(p, ws), &jobs[1])) != TA3N_OK) return rc;
         if (!fused_norm && launch_grad_norm(g, grads, ws, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
         if (launch_sgd_open_feed(g, params, grads, momentum, ws, 0, p->first_floats, fused_norm != 0, lr, momentum_coef, weight_decay, clip,
                                  PlanHyper(p, next).ptr(), jobs, s) != 0)
@@ -876,7 +882,7 @@ int ta3n_train_steps_sharded(ta3n_plan *p, ta3n_comm *c, const float *x, float *
     float lr = lr_pending;
     for (int k = 0; k < n_steps; ++k) {
         if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
-        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, nullptr, s)) != TA3N_OK) return rc;
+        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, target_labels_out(p, ws), s)) != TA3N_OK) return rc;
         // -- update of the step before (its gradients are reduce-scattered): norm of the own shards, one float per rank gathered,
         //    clip + Nesterov SGD on the own shards (1 / world of the optimiser pass), carrying this step's scalars
         if ((rc = ta3n_shard_sumsq(p, grads, ws, rank, world, stream)) != TA3N_OK) return rc;
@@ -942,7 +948,7 @@ int ta3n_train_steps_fused_update(ta3n_plan *p, const float *x, float *params, f
     int cur = 0;
     for (int k = 0; k < n_steps; ++k) {
         if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
-        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, nullptr, s)) != TA3N_OK) return rc;
+        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, target_labels_out(p, ws), s)) != TA3N_OK) return rc;
         // forward, heads, backward on P[cur]; every gradient tile writes its block of P[1 - cur] (and its twins)
         Ptrs ptrs = make_ptrs(p, x, P[cur], grads, ws, cur);
         SgdSide side;
@@ -1132,7 +1138,7 @@ int ta3n_train_steps_adam(ta3n_plan *p, const float *x, float *params, float *gr
     for (int k = 0; k < n_steps; ++k) {
         // the batch of step k (its input rows were last read by the final launch of step k - 1, already enqueued)
         if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
-        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, nullptr, s)) != TA3N_OK) return rc;
+        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, target_labels_out(p, ws), s)) != TA3N_OK) return rc;
         // the update of the step before as update number step_pending + k, carrying this step's scalars; then the step's own launches
         if ((rc = enqueue_adam(p, params, grads, exp_avg, exp_avg_sq, ws, 0, p->live_floats, fused_norm, lr, beta1, beta2, eps, weight_decay,
                                clip, step_pending + k, &hypers[k], s)) != TA3N_OK) return rc;

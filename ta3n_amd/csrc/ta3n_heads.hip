@@ -289,7 +289,8 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
     const float bcdv0 = P[g.p_bcdv], bcdv1 = P[g.p_bcdv + 1];
     // (a SCALAR load: as a vector load at the end of the burst above, its consumer `lane == label` - which the compiler hoists up here to
     // keep the result as a lane mask - waited for the whole 256 KB weight burst with s_waitcnt vmcnt(0) before stage A could start)
-    const int label = (have && b < g.Bs) ? labels[__builtin_amdgcn_readfirstlane(b)] : -1;
+    // (TA3N_FLAG_TARGET_LABELS: the target videos' waves load theirs, ws["labels"][Bs + j], the same way - one more scalar test)
+    const int label = (have && (b < g.Bs || (g.flags & TA3N_FLAG_TARGET_LABELS))) ? labels[__builtin_amdgcn_readfirstlane(b)] : -1;
     if (NW == 4) load_small_b();
     if (NW == 8) __builtin_amdgcn_sched_barrier(0);      // nothing below is issued in front of the loads above
 
@@ -451,7 +452,7 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
         if (have && lead) {
             const bool is_src = b < g.Bs;
             const bool valid = video_valid(g.Bs, hs.valid_source, hs.valid_target, b);
-            const bool cls_on = is_src && valid;
+            const bool cls_on = class_ce_on(g.flags, g.Bs, valid, b);
             const Soft2 s = soft2(d0, d1);
             const bool ent_on = (g.flags & TA3N_FLAG_ATTN_ENTROPY) && valid;
             const float ce = hs.gamma * hs.inv_n_ent;
@@ -459,13 +460,18 @@ __device__ __forceinline__ void video_wg(const Geom g, const Ptrs ptrs, float *s
                 // (TA3N_FLAG_CLASS_WEIGHTS: the lead wave's own sum over the step's labels, here - behind a branch the unweighted kernel already
                 // has - and not at the top: the unweighted kernel keeps its front and its stage D.  The branch is wave-uniform: all 64 lanes are on.)
                 float k_cls = hs.inv_n_cls;
-                if (g.flags & TA3N_FLAG_CLASS_WEIGHTS) k_cls = class_coef(class_rule(g, wsr, hy->class_w_off, hs.valid_source, hs.inv_n_cls, lane), label);
+                if (g.flags & TA3N_FLAG_CLASS_WEIGHTS) k_cls = class_coef(class_rule(g, wsr, hy->class_w_off, hs.valid_source, hs.valid_target, hs.inv_n_cls, lane), label);
                 gy = class_ce_grad(pr, lane == label, k_cls);
                 if (lane == label) l_cls = -lp * k_cls;
             }
             if (ent_on) {                                                              // loss.py:20-24
                 gy += ce * (1.f + s.H) * dH_dz(pr, lp, Hc);
                 if (lane == 0) l_ent = (1.f + s.H) * Hc * hs.inv_n_ent;
+            }
+            // (TA3N_FLAG_TARGET_ENTROPY, exclusive with _ATTN_ENTROPY: plain entropy of the valid target rows, main.py:542-545 - wave-uniform)
+            if (target_ent_on(g.flags, g.Bs, valid, b)) {
+                gy += target_ent_grad(ce, pr, lp, Hc);
+                if (lane == 0) l_ent = target_ent_loss(Hc, hs.inv_n_ent);
             }
             if (lane >= C) gy = 0.f;
             if ((g.flags & TA3N_FLAG_ADV_VIDEO) && valid) {                           // main.py:508-538, l = 1

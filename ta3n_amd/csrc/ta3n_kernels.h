@@ -173,6 +173,8 @@ __device__ __forceinline__ void nesterov_sgd(float &p, float &m, float g_scaled,
 // kernel, the unfused lists (pool_fwd / loss / pool_bwd, frame_attn_*, pool_cls), the MCD glue and the validation metrics call these, and every new variant does.
 // Is video b of the batch [Bs source | Bt target] a real row, not the padding of a ragged batch (source-only steps pass valid_target = 0)
 __device__ __forceinline__ bool video_valid(int Bs, int valid_source, int valid_target, int b) { return b < Bs ? (b < valid_source) : (b - Bs < valid_target); }
+// Is the class cross-entropy of video b on: a valid source row, or - TA3N_FLAG_TARGET_LABELS - any valid row (main.py:442-446)
+__device__ __forceinline__ bool class_ce_on(uint32_t flags, int Bs, bool valid, int b) { return valid && (b < Bs || (flags & TA3N_FLAG_TARGET_LABELS)); }
 // Domain cross-entropy of a 2-logit row (source: label 0, target: 1), mean over 1 / inv_n rows (main.py:508-538): loss term and logit gradient
 struct DomainCe { float l, g0, g1; };
 __device__ __forceinline__ DomainCe domain_ce(const Soft2 &s, bool is_src, float inv_n) {
@@ -180,6 +182,12 @@ __device__ __forceinline__ DomainCe domain_ce(const Soft2 &s, bool is_src, float
     return {-(d ? s.lp1 : s.lp0) * inv_n, (s.p0 - (d == 0 ? 1.f : 0.f)) * inv_n, (s.p1 - (d == 1 ? 1.f : 0.f)) * inv_n};
 }
 __device__ __forceinline__ float dH_dz(float p, float lp, float H) { return -p * (lp + H); }   // of the entropy H of softmax(z) (loss.py:20-24)
+// Plain target entropy (TA3N_FLAG_TARGET_ENTROPY, --add_loss_DA target_entropy; main.py:542-545, loss.py:8-12): gamma * mean over the valid target
+// rows of H(softmax y).  Per valid target row: the loss term, and the logit gradient with ce = gamma * inv_n_ent.  No (1 + H_d) factor, nothing
+// to the domain logits, nothing on source rows.
+__device__ __forceinline__ bool target_ent_on(uint32_t flags, int Bs, bool valid, int b) { return (flags & TA3N_FLAG_TARGET_ENTROPY) && valid && b >= Bs; }
+__device__ __forceinline__ float target_ent_loss(float Hc, float inv_n_ent) { return Hc * inv_n_ent; }
+__device__ __forceinline__ float target_ent_grad(float ce, float p, float lp, float Hc) { return ce * dH_dz(p, lp, Hc); }
 // Transferable attention (models.py:351-357): w = 1 - H(softmax z) and the features scaled by 1 + w.  The weights are not detached: with
 // dot = dL/dw, dot dw/dz_i = dot p_i (log p_i + H) joins the logit gradients; the gradient behind the scale is 1 + (1 - H) times the one in front.
 __device__ __forceinline__ float attn_weight(const Soft2 &s) { return 1.f - s.H; }
@@ -205,8 +213,11 @@ __device__ __forceinline__ float class_ce_grad(float p, bool is_label, float inv
 // ws["class_w"]: lane l adds rows l, l + 64, ... in order, then wave_allreduce_sum - the same bits in every workgroup of every launch of
 // the step, with no launch of its own and nothing from the host (device-gathered batches: the labels arrive in the step's opening launch).
 // Rows at and past valid_source (padding) never enter; a label outside [0, C) adds nothing.  All 64 lanes must be active at the call.
+// TA3N_FLAG_TARGET_LABELS (--use_target Sv, main.py:442-446: criterion(cat(out_source, out_target), cat(label_source, label_target))): the valid
+// target rows carry labels too (ws["labels"][Bs + j]) and enter the class CE and the sum of the weights; callers whose rows are all source
+// rows (validation, the source-only pool_cls) pass valid_target = 0.
 struct ClassRule { const float *w; float inv; int C; };      // w == nullptr: unweighted, inv = inv_n_cls; otherwise inv = 1 / sum_j w[label_j]
-__device__ __forceinline__ ClassRule class_rule(const Geom &g, const float *__restrict__ ws, int class_w_off, int valid_source, float inv_n_cls, int lane) {
+__device__ __forceinline__ ClassRule class_rule(const Geom &g, const float *__restrict__ ws, int class_w_off, int valid_source, int valid_target, float inv_n_cls, int lane) {
     if (!(g.flags & TA3N_FLAG_CLASS_WEIGHTS) || class_w_off <= 0) return {nullptr, inv_n_cls, g.C};
     const float *__restrict__ w = ws + class_w_off;
     const int *__restrict__ labels = reinterpret_cast<const int *>(ws + g.o_labels);
@@ -215,6 +226,13 @@ __device__ __forceinline__ ClassRule class_rule(const Geom &g, const float *__re
     for (int j = lane; j < n; j += 64) {
         const int l = labels[j];
         acc += (unsigned)l < (unsigned)g.C ? w[l] : 0.f;
+    }
+    if (g.flags & TA3N_FLAG_TARGET_LABELS) {      // the second range, [Bs, Bs + valid_target), behind the first in every lane: one order at every call site
+        const int nt = valid_target < g.B - g.Bs ? valid_target : g.B - g.Bs;
+        for (int j = lane; j < nt; j += 64) {
+            const int l = labels[g.Bs + j];
+            acc += (unsigned)l < (unsigned)g.C ? w[l] : 0.f;
+        }
     }
     const float sum = wave_allreduce_sum(acc);
     return {w, sum > 0.f ? 1.f / sum : 0.f, g.C};

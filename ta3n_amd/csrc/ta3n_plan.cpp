@@ -349,6 +349,11 @@ int build_plan_avgpool(ta3n_plan &p, std::string &err) {
     const int B = d.B, BT = d.BT, D = d.D, F = d.F, C = d.C;
     const uint32_t da_flags = TA3N_FLAG_ADV_RELATION | TA3N_FLAG_ADV_VIDEO | TA3N_FLAG_ADV_FRAME | TA3N_FLAG_ATTN_ENTROPY | TA3N_FLAG_TRANS_ATTN;
     if (c.flags & da_flags) { err = "avgpool is built for the source-only configuration: no adversarial / attention flags (SURVEY 8f rank 4)"; return TA3N_ERR_INVALID; }
+    if (c.flags & TA3N_FLAG_TARGET_ENTROPY) { err = "avgpool: TA3N_FLAG_TARGET_ENTROPY (add_loss_DA target_entropy) is not built"; return TA3N_ERR_INVALID; }
+    if (c.flags & TA3N_FLAG_TARGET_LABELS) {
+        err = "TA3N_FLAG_TARGET_LABELS (use_target Sv) on the source-only avgpool plan: built on the general avgpool plan (an adversarial flag) and on trn-m";
+        return TA3N_ERR_INVALID;
+    }
     if (const char *e = avgpool_dims_refusal(d)) { err = e; return TA3N_ERR_INVALID; }
     Builder b(p);
     // live parameters first (the all-reduce / optimiser operand), then the rest of the reference's state_dict for this configuration
@@ -481,6 +486,7 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
         err = "avgpool: attention / attentive entropy are not built (the reference's script switches them off with use_attn none)";
         return TA3N_ERR_INVALID;
     }
+    if (c.flags & TA3N_FLAG_TARGET_ENTROPY) { err = "avgpool: TA3N_FLAG_TARGET_ENTROPY (add_loss_DA target_entropy) is not built"; return TA3N_ERR_INVALID; }
     if (const char *e = avgpool_dims_refusal(d)) { err = e; return TA3N_ERR_INVALID; }
     if (const char *e = bn_shared_refusal(c, d)) { err = e; return TA3N_ERR_INVALID; }
     const bool live_frm = (c.flags & TA3N_FLAG_ADV_FRAME) != 0;
@@ -1122,6 +1128,23 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     if (d.C > 64) { err = "num_class > 64 not supported by the loss kernel"; return TA3N_ERR_INVALID; }
     if ((c.flags & TA3N_FLAG_CLASS_WEIGHTS) && d.Bs <= 0) {
         err = "TA3N_FLAG_CLASS_WEIGHTS (weighted class loss) without source rows: batch_source must be positive";
+        return TA3N_ERR_INVALID;
+    }
+    // TA3N_FLAG_TARGET_LABELS (--use_target Sv) / TA3N_FLAG_TARGET_ENTROPY (--add_loss_DA target_entropy): what is not built, by name
+    if ((c.flags & TA3N_FLAG_TARGET_LABELS) && (c.flags & TA3N_FLAG_MCD)) {
+        err = "TA3N_FLAG_TARGET_LABELS (use_target Sv) with TA3N_FLAG_MCD: the reference itself fails there (main.py:448: out_source_2 has n_s rows against n_s + n_t labels)";
+        return TA3N_ERR_INVALID;
+    }
+    if ((c.flags & TA3N_FLAG_TARGET_ENTROPY) && (c.flags & TA3N_FLAG_MCD)) {
+        err = "TA3N_FLAG_TARGET_ENTROPY (add_loss_DA target_entropy) with TA3N_FLAG_MCD is not built (MCD rebinds out_target to the second pass's logits)";
+        return TA3N_ERR_INVALID;
+    }
+    if ((c.flags & TA3N_FLAG_TARGET_LABELS) && d.Bt <= 0) {
+        err = "TA3N_FLAG_TARGET_LABELS (use_target Sv) without target rows: batch_target must be positive";
+        return TA3N_ERR_INVALID;
+    }
+    if ((c.flags & TA3N_FLAG_TARGET_ENTROPY) && (c.flags & TA3N_FLAG_ATTN_ENTROPY)) {
+        err = "TA3N_FLAG_TARGET_ENTROPY and TA3N_FLAG_ATTN_ENTROPY are two values of one option (add_loss_DA target_entropy / attentive_entropy): set one";
         return TA3N_ERR_INVALID;
     }
     if ((c.flags & TA3N_FLAG_ATTN_ENTROPY) &&

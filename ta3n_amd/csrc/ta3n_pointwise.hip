@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
     const int rid = blockIdx.x * blockDim.x + threadIdx.x;
     float l_cls = 0.f, l_rel = 0.f, l_vid = 0.f, l_frm = 0.f, l_ent = 0.f;
     // (only the workgroups that hold video rows form the sum of the weights - block-uniform, every wave of them with all lanes on)
-    const ClassRule cr = (int)(blockIdx.x * blockDim.x) < n_vid ? class_rule(g, ws, hy->class_w_off, hy->valid_source, hy->inv_n_cls, threadIdx.x & 63)
+    const ClassRule cr = (int)(blockIdx.x * blockDim.x) < n_vid ? class_rule(g, ws, hy->class_w_off, hy->valid_source, hy->valid_target, hy->inv_n_cls, threadIdx.x & 63)
                                                                 : ClassRule{nullptr, hy->inv_n_cls, C};
     const float k_src = domain_factor(hy->dom_k[0]), k_tgt = domain_factor(hy->dom_k[1]);
     if (rid < n_vid) {
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
             const float lp = y[i] - m - ls;
             Hc -= expf(lp) * lp;
         }
-        const bool cls_on = is_src && valid;
+        const bool cls_on = class_ce_on(g.flags, g.Bs, valid, b);                     // (TA3N_FLAG_TARGET_LABELS: the valid target rows too, their labels at labels[Bs + j])
         const int lab = cls_on ? labels[b] : -1;
         const float k_cls = class_coef(cr, lab);
         if (cls_on) l_cls = -(y[lab] - m - ls) * k_cls;                              // main.py:446
@@ -255,12 +255,15 @@ __global__ __launch_bounds__(256) void loss_kernel(Geom g, Ptrs ptrs) {
         const bool ent_on = (g.flags & TA3N_FLAG_ATTN_ENTROPY) && valid;
         const float ce = hy->gamma * hy->inv_n_ent;
         if (ent_on) l_ent = (1.f + s.H) * Hc * hy->inv_n_ent;                         // loss.py:20-24
+        const bool tent_on = target_ent_on(g.flags, g.Bs, valid, b);                  // main.py:542-545 (exclusive with ent_on)
+        if (tent_on) l_ent = target_ent_loss(Hc, hy->inv_n_ent);
         for (int i = 0; i < C; ++i) {
             const float lp = y[i] - m - ls;
             const float p = expf(lp);
             float gi = 0.f;
             if (cls_on) gi = class_ce_grad(p, i == lab, k_cls);
             if (ent_on) gi += ce * (1.f + s.H) * dH_dz(p, lp, Hc);
+            if (tent_on) gi += target_ent_grad(ce, p, lp, Hc);
             gy[i] = gi;
         }
         float g0 = 0.f, g1 = 0.f;
@@ -474,7 +477,7 @@ __global__ __launch_bounds__(256) void pool_cls_kernel(Geom g, Ptrs ptrs) {
         const bool on = video_valid(g.Bs, hy->valid_source, 0, b);
         const int label = on ? reinterpret_cast<const int32_t *>(ws + g.o_labels)[b] : -1;
         const float lp = lane_log_softmax(lane < C ? s_y[lane] : -INFINITY, lane < C).lp;
-        const ClassRule cr = class_rule(g, ws, hy->class_w_off, hy->valid_source, hy->inv_n_cls, lane);
+        const ClassRule cr = class_rule(g, ws, hy->class_w_off, hy->valid_source, 0, hy->inv_n_cls, lane);
         const float k_cls = on ? class_coef(cr, label) : 0.f;
         const float gy = (on && lane < C) ? class_ce_grad(expf(lp), lane == label, k_cls) : 0.f;
         const float l = wave_allreduce_sum((on && lane == label) ? -lp * k_cls : 0.f);
@@ -631,7 +634,7 @@ __global__ __launch_bounds__(1024) void eval_metrics_kernel(Geom g, float *__res
     __syncthreads();
     // TA3N_FLAG_CLASS_WEIGHTS: main.validate's criterion(pred, label) is the weighted mean of THIS batch (main.py:725), averaged over batches by
     // batch size: metrics[0] += n * sum_b w[y_b] ce_b / sum_b w[y_b]
-    const ClassRule cr = class_rule(g, ws, reinterpret_cast<const Hyper *>(ws + g.o_hyper)->class_w_off, n, 1.f, lane);
+    const ClassRule cr = class_rule(g, ws, reinterpret_cast<const Hyper *>(ws + g.o_hyper)->class_w_off, n, 0, 1.f, lane);
     float ce = 0.f, t1 = 0.f, t5 = 0.f;
     for (int b = wv; b < n; b += 16) {
         const float y = lane < C ? ws[g.o_Y + (size_t)b * C + lane] : -INFINITY;
@@ -692,7 +695,7 @@ struct FeedHalf {
     const int64_t *first_row;
     const int32_t *num_frames, *labels, *video_ids;
     float *out;                  // fp32 input rows of this half (nullptr: a bf16 store feeding a plan that reads twins only)
-    int32_t *labels_out;         // nullptr: target half
+    int32_t *labels_out;         // nullptr: the target half without TA3N_FLAG_TARGET_LABELS
     float *twin;                 // bf16 twin rows of this half (nullptr: the plan keeps none)
     int32_t rows, bf16;          // ids_per_step * T; the store holds bf16
 };
@@ -1123,7 +1126,7 @@ __global__ __launch_bounds__(256) void mcd_source_loss_kernel(Geom g, float *__r
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= g.B) return;
     const int C = g.C, ns = hy->valid_source;
-    const ClassRule cr = class_rule(g, ws, hy->class_w_off, ns, hy->inv_n_cls, lane);
+    const ClassRule cr = class_rule(g, ws, hy->class_w_off, ns, 0, hy->inv_n_cls, lane);
     const bool on = lane < C;
     float g2 = 0.f, term = 0.f;
     if (video_valid(g.Bs, ns, 0, b)) {
@@ -1188,7 +1191,7 @@ __global__ __launch_bounds__(64) void mcd_finish_kernel(const float *__restrict_
         float acc = 0.f;
         for (int i = threadIdx.x; i < n; i += 64) acc += part[i];
         acc = wave_allreduce_sum(acc);
-        const ClassRule cr = class_rule(g, ws, hy->class_w_off, n, hy->inv_n_cls, (int)threadIdx.x);
+        const ClassRule cr = class_rule(g, ws, hy->class_w_off, n, 0, hy->inv_n_cls, (int)threadIdx.x);
         if (threadIdx.x == 0) out[0] = acc * cr.inv;
         return;
     }

@@ -43,6 +43,10 @@ def flags_from_options(place_adv: Sequence[str] = ("Y", "Y", "Y"), add_loss_DA: 
         raise ValueError(frame_attn_refusal(use_attn_frame))
     if use_attn_frame == "TransAttn":      # (with which other options it is built: frame_attn_refusal)
         f |= _lib.FLAG_FRAME_ATTN
+    if use_target == "Sv":                 # main.py:439-446: the class CE over source + target rows (everything else as under uSv)
+        f |= _lib.FLAG_TARGET_LABELS
+    if add_loss_DA == "target_entropy" and use_target != "none":      # main.py:542-545
+        f |= _lib.FLAG_TARGET_ENTROPY
     return f
 
 
@@ -131,6 +135,23 @@ def adam_refusal(world: int = 1, sharded_update: bool = False, process_group: bo
                             ("capture() (a hipGraph would freeze the step count of the bias corrections)", capture),
                             ("the two-stream multi-job call (ta3n_train_steps_multi)", two_stream)) if on]
     return f"optimizer Adam together with {', '.join(what)} is not built (Adam: single rank, the update as one launch behind the step)" if what else ""
+
+
+def target_refusal(use_target: str = "none", add_loss_DA: str = "none", world: int = 1, process_group: bool = False,
+                   ddp_selftest: bool = False, sharded_update: bool = False, peer_exchange: bool = False, ens_DA: str = "none") -> str:
+    """'' when --use_target Sv / --add_loss_DA target_entropy are built together with the named schedule, otherwise the message that refuses
+    them.  Both are means over this rank's rows with labels this rank holds (TA3N_FLAG_TARGET_LABELS / TA3N_FLAG_TARGET_ENTROPY): single rank."""
+    opts = [o for o, on in (("--use_target Sv", use_target == "Sv"),
+                            ("--add_loss_DA target_entropy", add_loss_DA == "target_entropy" and use_target != "none")) if on]
+    if not opts:
+        return ""
+    what = [w for w, on in ((f"world size {world} (a process group)", world > 1 or process_group),
+                            ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest),
+                            ("the sharded update (sharded_update / TA3N_DDP_SHARDED)", sharded_update),
+                            ("the peer gradient exchange (peer_exchange / TA3N_DDP_PEER)", peer_exchange),
+                            ("--ens_DA MCD (under Sv the reference itself fails at main.py:448; target entropy on MCD's rebound out_target is not built)",
+                             ens_DA == "MCD")) if on]
+    return f"{' / '.join(opts)} together with {', '.join(what)} is not built (target labels and target entropy: single rank)" if what else ""
 
 
 def class_weights_from_list(list_file: str, num_class: int):
@@ -225,6 +246,18 @@ class TrainEngine:
                                              ddp_selftest=os.environ.get("TA3N_DDP_SELFTEST") == "1")
         if kind is not None:
             raise kind(refused)
+        # --use_target Sv (TA3N_FLAG_TARGET_LABELS in `flags`: the class CE over both halves, set_batch(..., target_label=...)) and
+        # --add_loss_DA target_entropy (TA3N_FLAG_TARGET_ENTROPY: gamma * mean entropy of the valid target rows); flags_from_options sets them
+        self.target_labels = bool((flags or 0) & _lib.FLAG_TARGET_LABELS)
+        self.target_entropy = bool((flags or 0) & _lib.FLAG_TARGET_ENTROPY)
+        if self.target_labels or self.target_entropy:
+            refused = target_refusal("Sv" if self.target_labels else "uSv", "target_entropy" if self.target_entropy else "none",
+                                     process_group=process_group is not None, ddp_selftest=os.environ.get("TA3N_DDP_SELFTEST") == "1",
+                                     sharded_update=bool(sharded_update) or (sharded_update is None and os.environ.get("TA3N_DDP_SHARDED", "0") == "1"),
+                                     peer_exchange=bool(peer_exchange) or (peer_exchange is None and os.environ.get("TA3N_DDP_PEER", "0") == "1"),
+                                     ens_DA=ens_DA)
+            if refused:
+                raise NotImplementedError(refused)
         self.class_weights = None if class_weights is None else tuple(float(v) for v in class_weights)
         self.domain_weights = None if domain_weights is None else (float(domain_weights[0]), float(domain_weights[1]))
         # --optimizer Adam (reference main.py:84-86): clip + torch.optim.Adam as ONE launch over the flat live prefix behind the step's
@@ -370,6 +403,9 @@ class TrainEngine:
             raise NotImplementedError(adam_refusal(world=self.world))
         if self.class_weights is not None and self.world > 1:
             raise NotImplementedError(weights_refusal(self.class_weights, None, num_class=num_class, world=self.world))
+        if (self.target_labels or self.target_entropy) and self.world > 1:
+            raise NotImplementedError(target_refusal("Sv" if self.target_labels else "uSv", "target_entropy" if self.target_entropy else "none",
+                                                     world=self.world))
         # The DA options under more than one rank follow what the reference's nn.DataParallel does with them (main.py:79): the discrepancy
         # loss is taken on the gathered global batch (discrepancy()); MCD's discrepancy is a mean over the global target batch
         # (mcd_second_forward()); BatchNorm statistics are PER REPLICA - each replica normalises its own slice of the batch with its own
@@ -509,6 +545,8 @@ class TrainEngine:
         return (f"TrainEngine {self.Bs}+{self.Bt} videos x {self.T} segments, feature_dim {self.D}, fc_dim {self.F}, {self.C} classes, "
                 f"{self.aggregation}, {arith}{' on twins' if self.bf16_store else ''}, {self.optimizer}, world {self.world}"
                 f"{', class weights' if self.class_weights is not None else ''}"
+                f"{', target labels (use_target Sv)' if self.target_labels else ''}"
+                f"{', target entropy' if self.target_entropy else ''}"
                 f"{', domain weights ({:.3g}, {:.3g})'.format(*self.domain_weights) if self.domain_weights is not None else ''}: {step}")
 
     # ---- plumbing ----
@@ -613,11 +651,19 @@ class TrainEngine:
         self.adam_range(0, self.plan.live_floats, float(self._hyper.lr) if lr is None else lr, fused_norm=fused_norm)
         self.adam_step_count += 1
 
-    def set_batch(self, source: torch.Tensor, target: torch.Tensor, source_label: torch.Tensor) -> None:
-        """[Bs,T,D], [Bt,T,D] float features and int labels into the static device buffers."""
+    def set_batch(self, source: torch.Tensor, target: torch.Tensor, source_label: torch.Tensor,
+                  target_label: Optional[torch.Tensor] = None) -> None:
+        """[Bs,T,D], [Bt,T,D] float features and int labels into the static device buffers.  target_label [Bt]: the target videos' labels,
+        required under TA3N_FLAG_TARGET_LABELS (--use_target Sv) and refused without it."""
+        if self.target_labels and target_label is None:
+            raise ValueError("set_batch: use_target Sv (TA3N_FLAG_TARGET_LABELS) needs target_label")
+        if target_label is not None and not self.target_labels:
+            raise ValueError("set_batch: target_label without use_target Sv (TA3N_FLAG_TARGET_LABELS is off: the target labels would be ignored)")
         self.X[: self.Bs * self.T].copy_(source.reshape(-1, self.D), non_blocking=True)
         self.X[self.Bs * self.T:].copy_(target.reshape(-1, self.D), non_blocking=True)
         self._labels[: self.Bs].copy_(source_label.to(torch.int32), non_blocking=True)
+        if target_label is not None:
+            self._labels[self.Bs:].copy_(target_label.to(torch.int32), non_blocking=True)
         self.refresh_bf16(x=True)
 
     def set_hyper(self, beta: Sequence[float], gamma: float, lr: float, train: bool = True,
@@ -642,7 +688,10 @@ class TrainEngine:
         h.seed_i, h.seed_v = dropout_seeds(self.step_count if seed is None else seed, self.rank)
         if raw_seeds is not None:      # the two dropout stream seeds as given (a caller that draws them itself, like VideoModel.forward does)
             h.seed_i, h.seed_v = int(raw_seeds[0]) & 0xFFFFFFFF, int(raw_seeds[1]) & 0xFFFFFFFF
-        for k, v in parallel.loss_normalisers(gs, gt, self.T).items():
+        tflags = getattr(self, "_flags", 0) & (_lib.FLAG_TARGET_LABELS | _lib.FLAG_TARGET_ENTROPY)
+        if (tflags & _lib.FLAG_TARGET_ENTROPY) and train and int(gt) == 0:
+            raise ValueError("--add_loss_DA target_entropy: a step without a valid target video (the reference's mean over no rows is NaN)")
+        for k, v in parallel.loss_normalisers(gs, gt, self.T, tflags).items():
             setattr(h, k, v)
         h.valid_source, h.valid_target, h.train = int(ns), int(nt), int(bool(train))
         h.bn_eval_target = int(bn_eval_target)
@@ -1102,6 +1151,12 @@ class TrainEngine:
         a["seed_v"] = ((st2 + np.uint32(2)) * np.uint32(0x85EBCA77)) ^ np.uint32((r * 0x27D4EB2F) & 0xFFFFFFFF)
         return hy
 
+    def _feed_labels_out(self, first: int):
+        """Where the labels of the batch half that starts at video `first` go: the source half's always, the target half's under use_target Sv."""
+        if first == 0:
+            return self._labels[: self.Bs]
+        return self._labels[self.Bs:] if self.target_labels else None
+
     def _feeds(self, feeds, k0: int):
         """ta3n_feed structs (and the id tables that must outlive the enqueued gathers) of a multi-step call."""
         fd, keep = [None, None], []
@@ -1165,7 +1220,7 @@ class TrainEngine:
                 if feeds is not None:
                     for (store, ids), first in zip(feeds, (0, self.Bs)):
                         if store is not None:
-                            store.gather_into(self, ids[k], first, labels_out=self._labels[: self.Bs] if first == 0 else None)
+                            store.gather_into(self, ids[k], first, labels_out=self._feed_labels_out(first))
                 (self.train_step_pipelined if self.fused else self.train_step)(beta, gamma, lr)
             return
         if _split and n >= 4 and not self._sharded and not _LEGACY_HOST_PREP:
@@ -1226,7 +1281,7 @@ class TrainEngine:
             if feeds is not None:
                 for (store, ids), first in zip(feeds, (0, self.Bs)):
                     if store is not None:
-                        store.gather_into(self, ids[0], first, labels_out=self._labels[: self.Bs] if first == 0 else None)
+                        store.gather_into(self, ids[0], first, labels_out=self._feed_labels_out(first))
             self.train_step_pipelined(*schedule[0])
             k0 = 1
             if n == 1:

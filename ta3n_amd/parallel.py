@@ -52,12 +52,20 @@ def padded_shard_size(n: int, world: int) -> int:
     return -(-n // world)
 
 
-def loss_normalisers(global_source: int, global_target: int, num_segments: int) -> Dict[str, float]:
+def loss_normalisers(global_source: int, global_target: int, num_segments: int, flags: int = 0) -> Dict[str, float]:
     """1/N of every loss mean over the GLOBAL batch (main.py:446 CE over labelled source
-    videos; main.py:533 adversarial CE over (src+tgt) x {T-1, 1, T} rows; loss.py:24)."""
+    videos; main.py:533 adversarial CE over (src+tgt) x {T-1, 1, T} rows; loss.py:24).
+    flags (the plan's TA3N_FLAG_* word; 0: the values above): under TA3N_FLAG_TARGET_LABELS the class CE is a mean over the valid
+    rows of both halves (main.py:442-446), under TA3N_FLAG_TARGET_ENTROPY the entropy term one over the valid target rows (:542-545)."""
     tot = max(global_source + global_target, 1)
-    return dict(inv_n_cls=1.0 / max(global_source, 1), inv_n_rel=1.0 / (tot * (num_segments - 1)),
-                inv_n_vid=1.0 / tot, inv_n_frm=1.0 / (tot * num_segments), inv_n_ent=1.0 / tot)
+    n = dict(inv_n_cls=1.0 / max(global_source, 1), inv_n_rel=1.0 / (tot * (num_segments - 1)),
+             inv_n_vid=1.0 / tot, inv_n_frm=1.0 / (tot * num_segments), inv_n_ent=1.0 / tot)
+    from . import _lib
+    if flags & _lib.FLAG_TARGET_LABELS:
+        n["inv_n_cls"] = 1.0 / tot
+    if flags & _lib.FLAG_TARGET_ENTROPY:
+        n["inv_n_ent"] = 1.0 / max(global_target, 1)
+    return n
 
 
 def global_counts(valid_source: int, valid_target: int, group=None, device=None) -> Tuple[int, int]:

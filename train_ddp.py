@@ -71,8 +71,21 @@ def validate_options(args, module_path: bool = False) -> None:
         need(args.use_bn in ("none", "AdaBN", "AutoDIAL"), f"--use_bn {args.use_bn}")
     else:
         need(args.use_bn in ("none", "AdaBN", "AutoDIAL"), f"--use_bn {args.use_bn}")
-    need(args.add_loss_DA in ("none", "attentive_entropy"), f"--add_loss_DA {args.add_loss_DA} (built: attentive_entropy)")
-    need(args.use_target in ("none", "uSv"), f"--use_target {args.use_target} (target labels in the classification loss are not built)")
+    # --use_target Sv (main.py:439-446: the class CE over source + target rows) and --add_loss_DA target_entropy (:542-545): main.py trains
+    # them, on the engine (TA3N_FLAG_TARGET_LABELS / TA3N_FLAG_TARGET_ENTROPY: single rank) or on its module path
+    if module_path:
+        need(args.add_loss_DA in ("none", "attentive_entropy", "target_entropy"), f"--add_loss_DA {args.add_loss_DA} (built: attentive_entropy, target_entropy)")
+        need(args.use_target in ("none", "uSv", "Sv"), f"--use_target {args.use_target} (built: none, uSv, Sv)")
+        if args.ens_DA == "MCD":
+            need(args.use_target != "Sv", "--use_target Sv with --ens_DA MCD (the reference itself fails there, main.py:448: out_source_2 has "
+                 "n_s rows against n_s + n_t labels)")
+            need(not (args.add_loss_DA == "target_entropy" and args.use_target != "none"),
+                 "--add_loss_DA target_entropy with --ens_DA MCD is not built (MCD rebinds out_target to the second pass's logits)")
+    else:
+        need(args.add_loss_DA in ("none", "attentive_entropy"), f"--add_loss_DA {args.add_loss_DA} (built: attentive_entropy)" +
+             (" (built on main.py)" if args.add_loss_DA == "target_entropy" else ""))
+        need(args.use_target in ("none", "uSv"), f"--use_target {args.use_target}" +
+             (" (built on main.py)" if args.use_target == "Sv" else " (built: none, uSv)"))
     # --weighted_class_loss / --weighted_class_loss_DA (main.py:156-167, 205-206): main.py builds the two weighted criteria and trains them on
     # the engine (TrainEngine class_weights / domain_weights; the class weights' sum is per rank: single rank)
     if not module_path:
