@@ -11,7 +11,8 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional, Sequence
+from collections import namedtuple
+from typing import Dict, Mapping, Optional, Sequence
 
 import os
 import torch
@@ -70,7 +71,6 @@ def dropout_seeds(step: int, rank: int = 0):
 
 
 _HYPER_DTYPE = None
-_LEGACY_HOST_PREP = os.environ.get("TA3N_HOST_PREP", "") == "legacy"      # A/B aid (tools/r5_session16.sh): schedule arrays entry by entry, no split
 
 
 def _hyper_dtype():
@@ -80,6 +80,16 @@ def _hyper_dtype():
     if _HYPER_DTYPE is None:
         _HYPER_DTYPE = np.dtype(_lib.Hyper)
     return np, _HYPER_DTYPE
+
+
+def _clip_value(clip: Optional[float]) -> float:
+    """TrainEngine.clip as the float the library takes (None: 0, no clipping)."""
+    return float(clip) if clip is not None else 0.0
+
+
+def _update_scalars(eng, lr: float):
+    """(lr, mu, wd, clip) of the update that closes a step taken at learning rate lr: what a postponing schedule keeps in eng._pending."""
+    return float(lr), float(eng.momentum), float(eng.weight_decay), _clip_value(eng.clip)
 
 
 def add_fc_refusal(add_fc: int, use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", chain: bool = False, split_k: int = 0,
@@ -121,19 +131,24 @@ def frame_attn_refusal(use_attn_frame: str, use_attn: str = "TransAttn", frame_a
     return f"--use_attn_frame TransAttn together with {', '.join(other)} is not built" if other else ""
 
 
+def _rank_schedules(world: int, process_group: bool, ddp_selftest: bool, sharded_update: bool = False, peer_exchange: bool = False):
+    """The names of the multi-rank schedules that are on, as every refusal of a single-rank option lists them."""
+    return [w for w, on in ((f"world size {world} (a process group)", world > 1 or process_group),
+                            ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest),
+                            ("the sharded update (sharded_update / TA3N_DDP_SHARDED)", sharded_update),
+                            ("the peer gradient exchange (peer_exchange / TA3N_DDP_PEER)", peer_exchange)) if on]
+
+
 def adam_refusal(world: int = 1, sharded_update: bool = False, process_group: bool = False, ddp_selftest: bool = False,
                  peer_exchange: bool = False, fused_update: bool = False, side_update: bool = False, capture: bool = False,
                  two_stream: bool = False) -> str:
     """'' when optimizer="Adam" is built together with the named schedule, otherwise the message that refuses it.  Adam is one launch over
     the flat prefix behind the step's gradients on one rank; every schedule below is a way of splitting or moving the SGD update."""
-    what = [w for w, on in ((f"world size {world} (a process group)", world > 1 or process_group),
-                            ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest),
-                            ("the sharded update (sharded_update / TA3N_DDP_SHARDED)", sharded_update),
-                            ("the peer gradient exchange (peer_exchange / TA3N_DDP_PEER)", peer_exchange),
-                            ("fused_update=True (the Nesterov update inside the gradient tiles, TA3N_FUSED_UPDATE)", fused_update),
-                            ("the side-stream / side-workgroup update (TA3N_SIDE_UPDATE)", side_update),
-                            ("capture() (a hipGraph would freeze the step count of the bias corrections)", capture),
-                            ("the two-stream multi-job call (ta3n_train_steps_multi)", two_stream)) if on]
+    what = _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange) + [
+        w for w, on in (("fused_update=True (the Nesterov update inside the gradient tiles, TA3N_FUSED_UPDATE)", fused_update),
+                        ("the side-stream / side-workgroup update (TA3N_SIDE_UPDATE)", side_update),
+                        ("capture() (a hipGraph would freeze the step count of the bias corrections)", capture),
+                        ("the two-stream multi-job call (ta3n_train_steps_multi)", two_stream)) if on]
     return f"optimizer Adam together with {', '.join(what)} is not built (Adam: single rank, the update as one launch behind the step)" if what else ""
 
 
@@ -145,12 +160,9 @@ def target_refusal(use_target: str = "none", add_loss_DA: str = "none", world: i
                             ("--add_loss_DA target_entropy", add_loss_DA == "target_entropy" and use_target != "none")) if on]
     if not opts:
         return ""
-    what = [w for w, on in ((f"world size {world} (a process group)", world > 1 or process_group),
-                            ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest),
-                            ("the sharded update (sharded_update / TA3N_DDP_SHARDED)", sharded_update),
-                            ("the peer gradient exchange (peer_exchange / TA3N_DDP_PEER)", peer_exchange),
-                            ("--ens_DA MCD (under Sv the reference itself fails at main.py:448; target entropy on MCD's rebound out_target is not built)",
-                             ens_DA == "MCD")) if on]
+    what = _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
+    if ens_DA == "MCD":
+        what.append("--ens_DA MCD (under Sv the reference itself fails at main.py:448; target entropy on MCD's rebound out_target is not built)")
     return f"{' / '.join(opts)} together with {', '.join(what)} is not built (target labels and target entropy: single rank)" if what else ""
 
 
@@ -207,8 +219,7 @@ def weights_refusal_kind(class_weights=None, domain_weights=None, num_class: int
             return ValueError, f"class_weights has {len(w)} entries for {num_class} classes"
         if any(not (v > 0.0 and math.isfinite(v)) for v in w):
             return ValueError, "class_weights must be positive and finite (1 / class_freq, main.py:164)"
-        what = [t for t, on in ((f"world size {world} (a process group)", world > 1 or process_group),
-                                ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest)) if on]
+        what = _rank_schedules(world, process_group, ddp_selftest)
         if what:
             return NotImplementedError, (f"class_weights together with {', '.join(what)} is not built (the weighted mean divides by the sum of the weights of the "
                     f"rank's own labels: single rank)")
@@ -219,6 +230,47 @@ def weights_refusal_kind(class_weights=None, domain_weights=None, num_class: int
         if any(not (v > 0.0 and math.isfinite(v)) for v in d):
             return ValueError, "domain_weights must be positive and finite (1 / num_source_train, 1 / num_target_train; main.py:167)"
     return None, ""
+
+
+# What TrainEngine's arguments and the TA3N_* environment settle about an engine, once, at construction (_resolve_switches says what each is)
+_Switches = namedtuple("_Switches", "ddp_selftest sharded_update peer_exchange peer_exchange_arg grad_bf16 ddp_buckets ddp_native split_k "
+                                    "chain_given chain_arg chain_env phase_tiles_env cost_model side_update native_mcd native_discrepancy "
+                                    "fused_update sharded_two_streams")
+
+
+def _resolve_switches(sharded_update: Optional[bool] = None, peer_exchange: Optional[bool] = None, grad_transport: Optional[str] = None,
+                      ddp_buckets: Optional[int] = None, split_k: Optional[int] = None, chain: Optional[bool] = None,
+                      env: Optional[Mapping[str, str]] = None) -> _Switches:
+    """Every switch TrainEngine takes as an argument and / or from the environment (default: os.environ), read in this one place: an
+    argument that is not None wins over its variable.  Pure: no device, no plan.
+    Two places see a switch in another form than the engine runs with, and keep doing so (changing either changes which calls are refused):
+      - adam_refusal sees peer_exchange_arg, not peer_exchange: TA3N_DDP_PEER=1 in the environment does not refuse a single-rank Adam
+        engine (on one rank without the self-test no exchange is set up at all), peer_exchange=True does.  target_refusal sees peer_exchange.
+      - add_fc_refusal and frame_attn_refusal see chain_arg, not the TA3N_CHAIN default: that default is itself off for add_fc > 1 and
+        for frame attention (TrainEngine._create_plan), so only a chain that was asked for by argument is refused there."""
+    env = os.environ if env is None else env
+
+    def either(arg, name):
+        return env.get(name, "0") == "1" if arg is None else bool(arg)
+    return _Switches(
+        ddp_selftest=env.get("TA3N_DDP_SELFTEST") == "1",
+        sharded_update=either(sharded_update, "TA3N_DDP_SHARDED"),
+        peer_exchange=either(peer_exchange, "TA3N_DDP_PEER"),
+        peer_exchange_arg=bool(peer_exchange),                         # as passed (None: off)
+        grad_bf16=either(None if grad_transport is None else grad_transport == "bf16", "TA3N_DDP_BF16"),
+        ddp_buckets=int(env.get("TA3N_DDP_BUCKETS", "1")) if ddp_buckets is None else int(ddp_buckets),
+        ddp_native=env.get("TA3N_DDP_NATIVE", "1") == "1",
+        split_k=int(env.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k),
+        chain_given=chain is not None,
+        chain_arg=bool(chain),                                         # as passed (None: off)
+        chain_env=env.get("TA3N_CHAIN", "0") == "1",                   # the default where chain was not passed, taken only where chained launches are built
+        phase_tiles_env=env.get("TA3N_PHASE_TILES") or "",
+        cost_model=int(env.get("TA3N_COST_MODEL", "0")),
+        side_update=env.get("TA3N_SIDE_UPDATE", "1") == "1",
+        native_mcd=env.get("TA3N_NATIVE_MCD", "1") != "0",
+        native_discrepancy=env.get("TA3N_NATIVE_DISCREPANCY", "1") != "0",
+        fused_update=env.get("TA3N_FUSED_UPDATE", "0") == "1",         # the default of train_steps(fused_update=None)
+        sharded_two_streams=env.get("TA3N_DDP_SHARDED_STREAMS", "1") == "2")
 
 
 class TrainEngine:
@@ -238,26 +290,75 @@ class TrainEngine:
                  peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False,
                  add_fc: int = 1, optimizer: str = "SGD", betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8,
                  class_weights: Optional[Sequence[float]] = None, domain_weights: Optional[Sequence[float]] = None):
+        sw = self._switches = _resolve_switches(sharded_update, peer_exchange, grad_transport, ddp_buckets, split_k, chain)
+        flags, fused, world_checks = self._check_options(
+            sw, flags=flags, fused=fused, num_class=num_class, process_group=process_group, optimizer=optimizer, betas=betas, eps=eps,
+            class_weights=class_weights, domain_weights=domain_weights, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, place_dis=place_dis,
+            alpha=alpha, ens_DA=ens_DA, mu=mu, aggregation=aggregation, wgrads_late=wgrads_late, phase_tiles=phase_tiles,
+            f32_split=f32_split, bf16=bf16, bf16_store=bf16_store)
+        if not torch.cuda.is_available():
+            raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.Bs, self.Bt, self.T, self.D, self.C = batch_source, batch_target, num_segments, feature_dim, num_class
+        self.B = batch_source + batch_target
+        self.F = min(fc_dim, feature_dim)
+        self.dropout_i, self.dropout_v = dropout_i, dropout_v
+        self.momentum, self.weight_decay, self.clip = momentum, weight_decay, clip
+        self._global_source, self._global_target = int(batch_source), int(batch_target)      # job-wide valid counts of the current step (set_hyper)
+        self._create_plan(sw, flags, fused, fc_dim=fc_dim, tile_config=tile_config, phase_tiles=phase_tiles, xcd_aware=xcd_aware,
+                          wgrads_late=wgrads_late)
+        self.pg = process_group
+        self.world, self.rank = 1, 0
+        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
+            self.world = torch.distributed.get_world_size(process_group)
+            self.rank = torch.distributed.get_rank(process_group)
+        if self.world > 1:      # the single-rank options, asked again, with the arguments of the first time, now that the world size is known
+            for refusal, kw in world_checks:
+                refused = refusal(world=self.world, **kw)
+                if refused:
+                    raise NotImplementedError(refused)
+        # The DA options under more than one rank follow what the reference's nn.DataParallel does with them (main.py:79): the discrepancy
+        # loss is taken on the gathered global batch (discrepancy()); MCD's discrepancy is a mean over the global target batch
+        # (mcd_second_forward()); BatchNorm statistics are PER REPLICA - each replica normalises its own slice of the batch with its own
+        # batch statistics (torch's DataParallel replicates the module; nothing synchronises the statistics) - and the running
+        # buffers that persist are replica 0's (sync_buffers()).
+        self._allocate_buffers(sw, fused)
+        self._setup_exchange(sw, parallel.shared_native_comm if share_comm else parallel.NativeComm)
+        self._setup_batchnorm()
+        self.step_count = 0
+        self.skip_collective = False
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._hyper = _lib.Hyper()
+
+    def _check_options(self, sw: "_Switches", *, flags, fused, num_class, process_group, optimizer, betas, eps, class_weights, domain_weights,
+                       add_fc, use_bn, dis_DA, place_dis, alpha, ens_DA, mu, aggregation, wgrads_late, phase_tiles, f32_split, bf16, bf16_store):
+        """Refuses what is not built and composes the plan's flags from the options; touches no device and no plan.  Returns (flags,
+        fused, world_checks): world_checks are the (refusal, arguments) of the single-rank options, which the constructor asks again
+        with the world size once it knows it (Adam's first: the order in which they win over each other)."""
+        world_checks = []
+
+        def refuse(refusal, first: bool = False, **kw):
+            refused = refusal(**kw)
+            if refused:
+                raise NotImplementedError(refused)
+            world_checks.insert(0 if first else len(world_checks), (refusal, kw))
         # --weighted_class_loss / --weighted_class_loss_DA (reference main.py:156-167, 205-206): the two criteria as CrossEntropyLoss(weight=...).
         # class_weights: TA3N_FLAG_CLASS_WEIGHTS and the C weights in workspace region "class_w" - every class cross-entropy of the step, MCD's
         # second classifier and the validation metrics divide by the sum of the weights of the batch's labels, formed inside the kernels.
         # domain_weights (w_s, w_t): two per-step factors in ta3n_hyper.dom_k, from the step's global valid counts (set_hyper).
-        kind, refused = weights_refusal_kind(class_weights, domain_weights, num_class=num_class, process_group=process_group is not None,
-                                             ddp_selftest=os.environ.get("TA3N_DDP_SELFTEST") == "1")
+        kw = dict(class_weights=class_weights, domain_weights=domain_weights, num_class=num_class, process_group=process_group is not None,
+                  ddp_selftest=sw.ddp_selftest)
+        kind, refused = weights_refusal_kind(**kw)
         if kind is not None:
             raise kind(refused)
+        world_checks.append((weights_refusal, kw))
         # --use_target Sv (TA3N_FLAG_TARGET_LABELS in `flags`: the class CE over both halves, set_batch(..., target_label=...)) and
         # --add_loss_DA target_entropy (TA3N_FLAG_TARGET_ENTROPY: gamma * mean entropy of the valid target rows); flags_from_options sets them
         self.target_labels = bool((flags or 0) & _lib.FLAG_TARGET_LABELS)
         self.target_entropy = bool((flags or 0) & _lib.FLAG_TARGET_ENTROPY)
-        if self.target_labels or self.target_entropy:
-            refused = target_refusal("Sv" if self.target_labels else "uSv", "target_entropy" if self.target_entropy else "none",
-                                     process_group=process_group is not None, ddp_selftest=os.environ.get("TA3N_DDP_SELFTEST") == "1",
-                                     sharded_update=bool(sharded_update) or (sharded_update is None and os.environ.get("TA3N_DDP_SHARDED", "0") == "1"),
-                                     peer_exchange=bool(peer_exchange) or (peer_exchange is None and os.environ.get("TA3N_DDP_PEER", "0") == "1"),
-                                     ens_DA=ens_DA)
-            if refused:
-                raise NotImplementedError(refused)
+        refuse(target_refusal, use_target="Sv" if self.target_labels else "uSv", add_loss_DA="target_entropy" if self.target_entropy else "none",
+               process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
+               peer_exchange=sw.peer_exchange, ens_DA=ens_DA)
         self.class_weights = None if class_weights is None else tuple(float(v) for v in class_weights)
         self.domain_weights = None if domain_weights is None else (float(domain_weights[0]), float(domain_weights[1]))
         # --optimizer Adam (reference main.py:84-86): clip + torch.optim.Adam as ONE launch over the flat live prefix behind the step's
@@ -268,22 +369,16 @@ class TrainEngine:
         self.optimizer = optimizer
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         if optimizer == "Adam":
-            refused = adam_refusal(sharded_update=bool(sharded_update) or (sharded_update is None and os.environ.get("TA3N_DDP_SHARDED", "0") == "1"),
-                                   process_group=process_group is not None, ddp_selftest=os.environ.get("TA3N_DDP_SELFTEST") == "1",
-                                   peer_exchange=bool(peer_exchange))
-            if refused:
-                raise NotImplementedError(refused)
+            refuse(adam_refusal, first=True, sharded_update=sw.sharded_update, process_group=process_group is not None,
+                   ddp_selftest=sw.ddp_selftest, peer_exchange=sw.peer_exchange_arg)
             if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0) or self.eps < 0.0:
                 raise ValueError(f"Adam: betas {self.betas} must be in [0, 1) and eps {self.eps} >= 0 (torch.optim.Adam's own checks)")
-        if not torch.cuda.is_available():
-            raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
         # --add_fc 2 / 3 (models.py:145-153, 581-603): one or two more Linear(F, F) -> ReLU -> dropout_i layers on the shared frame FC
         # (ta3n_config.shared_fc_layers: one more GEMM launch per layer in the forward and in the backward).  Built for use_bn none without
         # the discrepancy / MCD terms, on the measured default launch shapes (the tuned tile lists are indexed by the one-layer order).
-        add_fc_refused = add_fc_refusal(add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA, chain=bool(chain),
-                                        split_k=int(os.environ.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k),
-                                        wgrads_late=bool(wgrads_late), phase_tiles=bool(phase_tiles and any(phase_tiles)) or
-                                        bool(os.environ.get("TA3N_PHASE_TILES")))
+        add_fc_refused = add_fc_refusal(add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA, chain=sw.chain_arg, split_k=sw.split_k,
+                                        wgrads_late=bool(wgrads_late),
+                                        phase_tiles=bool(phase_tiles and any(phase_tiles)) or bool(sw.phase_tiles_env))
         if add_fc_refused:
             raise NotImplementedError(add_fc_refused) if add_fc >= 1 else ValueError(add_fc_refused)
         self.add_fc = int(add_fc)
@@ -298,9 +393,7 @@ class TrainEngine:
         if self.frame_attn:
             refused = frame_attn_refusal("TransAttn", use_attn="TransAttn" if flags & _lib.FLAG_TRANS_ATTN else "none",
                                          frame_aggregation=aggregation, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA,
-                                         f32_split=bool(f32_split), chain=bool(chain),
-                                         split_k=int(os.environ.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k),
-                                         wgrads_late=bool(wgrads_late))
+                                         f32_split=bool(f32_split), chain=sw.chain_arg, split_k=sw.split_k, wgrads_late=bool(wgrads_late))
             if refused:
                 raise NotImplementedError(refused)
             fused = False
@@ -312,8 +405,6 @@ class TrainEngine:
         if dis_DA not in ("none", "DAN", "JAN"):
             raise NotImplementedError(f"dis_DA {dis_DA!r} (built: DAN, JAN)")
         self.dis_DA, self.place_dis, self.alpha = dis_DA, tuple(place_dis), float(alpha)
-        self.loss_d = None                       # device scalar: the discrepancy loss of the last step (main.py's loss_d)
-        self._disc_scratch = None                # (native path: kernel matrices, stacked rows, the loss scalar in its last float)
         if dis_DA != "none":
             if dis_DA == "DAN" and len(self.place_dis) > 2 and self.place_dis[2] == "Y":
                 raise ValueError("place_dis[2]: the reference itself fails on the 3-D frame features (loss.py:49)")
@@ -338,79 +429,54 @@ class TrainEngine:
         if ens_DA not in ("none", "MCD"):
             raise NotImplementedError(f"ens_DA {ens_DA!r} (built: MCD)")
         self.ens_DA, self.mu = ens_DA, float(mu)
-        self.loss_s = None                       # device scalar: the MCD discrepancy loss of the last step (main.py's loss_s)
-        self.loss_c2 = None                      # ... and the second classifier's cross-entropy on the source rows
-        self._global_source, self._global_target = int(batch_source), int(batch_target)      # job-wide valid counts of the current step (set_hyper)
-        self._job_last_hyper = None      # ta3n_hyper of the last step a _steps_job enqueued (becomes self._hyper in _steps_done)
-        self.loss_e_shift = None                 # MCD + attentive entropy: (d total, d loss_e) that moving the target rows' entropy term to the
-                                                 # second pass's logits adds to what the loss kernel logged (main.py:549 vs :559-562)
         if ens_DA == "MCD":
             if use_bn != "none":
                 raise NotImplementedError("ens_DA MCD with use_bn (the second forward moves the BatchNorm buffers again: the module path)")
             flags |= _lib.FLAG_MCD
             fused = False
-        if f32_split:            # fp32-grade contractions as three bf16 MFMAs on operands split hi + lo (ta3n_hip.h) ...
-            if bf16:
-                raise ValueError("f32_split and bf16 are different arithmetics: set one")
+        if f32_split and bf16:
+            raise ValueError("f32_split and bf16 are different arithmetics: set one")
+        if f32_split:                # fp32-grade contractions as three bf16 MFMAs on operands split hi + lo (ta3n_hip.h)
             flags |= _lib.FLAG_F32_SPLIT
-            if bf16_store:       # ... read from "pair twins": producers store the hi and the lo plane, nothing is split in the K loops
-                flags |= _lib.FLAG_BF16_STORE
-        else:
-            if bf16 or bf16_store:   # BASELINE configs[1]: contraction operands rounded to bf16, fp32 accumulation and fp32 state
-                flags |= _lib.FLAG_BF16_MFMA
-            if bf16_store:           # ... and the forward launches of the fused step read bf16 twins instead of rounding on the fly
-                flags |= _lib.FLAG_BF16_STORE
+        elif bf16 or bf16_store:     # BASELINE configs[1]: contraction operands rounded to bf16, fp32 accumulation and fp32 state
+            flags |= _lib.FLAG_BF16_MFMA
+        if bf16_store:      # f32_split: read from "pair twins" - producers store the hi and the lo plane, nothing is split in the K loops;
+            # bf16: the forward launches of the fused step read bf16 twins instead of rounding on the fly
+            flags |= _lib.FLAG_BF16_STORE
         self.bf16 = bool(flags & _lib.FLAG_BF16_MFMA)
         self.bf16_store = bool(flags & _lib.FLAG_BF16_STORE)
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         if aggregation not in ("trn-m", "avgpool"):
             raise NotImplementedError(f"frame_aggregation {aggregation!r} (built: 'trn-m', and 'avgpool' in the source-only configuration)")
         self.aggregation = aggregation
         if aggregation == "avgpool":     # TemPooling: no relation features, no attention (use_attn none in the reference's script); with
             # use_target none (BASELINE configs[0]) the caller passes no adversarial flag either (flags_from_options)
             flags &= ~(_lib.FLAG_ATTN_ENTROPY | _lib.FLAG_TRANS_ATTN)
-        if phase_tiles is None and tile_config == 0 and aggregation == "trn-m" and add_fc == 1 and not self.frame_attn:      # measured choices for the benchmarked shapes (indexed by the plain launch order)
+        return flags, fused, world_checks
+
+    def _create_plan(self, sw: "_Switches", flags: int, fused: bool, *, fc_dim, tile_config, phase_tiles, xcd_aware, wgrads_late) -> None:
+        """self.plan (and self.chain, self._flags) for the checked options: the launch-shape choices, then the plan builder."""
+        plain = self.aggregation == "trn-m" and self.add_fc == 1 and not self.frame_attn
+        if phase_tiles is None and tile_config == 0 and plain:      # measured choices for the benchmarked shapes (indexed by the plain launch order)
             from .tuning import tuned_phase_tiles
-            phase_tiles = tuned_phase_tiles(batch_source + batch_target, num_segments, feature_dim, min(fc_dim, feature_dim),
-                                            self.bf16, self.bf16_store, split=bool(flags & _lib.FLAG_F32_SPLIT))
-        if os.environ.get("TA3N_PHASE_TILES") and tile_config == 0:      # measurement aid: "i:code,i:code" replaces entries of the list (A/B of one launch's tile under bench.py's protocol)
+            phase_tiles = tuned_phase_tiles(self.B, self.T, self.D, self.F, self.bf16, self.bf16_store, split=bool(flags & _lib.FLAG_F32_SPLIT))
+        if sw.phase_tiles_env and tile_config == 0:      # measurement aid: "i:code,i:code" replaces entries of the list (A/B of one launch's tile under bench.py's protocol)
             phase_tiles = list(phase_tiles or []) + [0] * (16 - len(phase_tiles or []))
-            for item in os.environ["TA3N_PHASE_TILES"].split(","):
+            for item in sw.phase_tiles_env.split(","):
                 i, code = item.split(":")
                 phase_tiles[int(i)] = int(code)
-        if chain is None:        # chained launches (ta3n_config.chain): the fused trn-m step in 5 launches instead of 8
-            chain = os.environ.get("TA3N_CHAIN", "0") == "1" and aggregation == "trn-m" and fused and add_fc == 1 and not self.frame_attn
+        # chained launches (ta3n_config.chain): the fused trn-m step in 5 launches instead of 8; as an argument it is taken as given, as
+        # TA3N_CHAIN=1 only where it is built
+        chain = sw.chain_arg if sw.chain_given else (sw.chain_env and plain and bool(fused))
         self._flags = int(flags)
-        self.plan = _lib.Plan(batch_source, batch_target, num_segments, feature_dim, fc_dim, num_class, flags,
+        self.plan = _lib.Plan(self.Bs, self.Bt, self.T, self.D, fc_dim, self.C, flags,
                               tile_config=tile_config, phase_tiles=list(phase_tiles or []), xcd_aware=xcd_aware,
-                              aggregation=_lib.AGG_AVGPOOL if aggregation == "avgpool" else _lib.AGG_TRN_M,
-                              wgrads_late=int(wgrads_late), chain=int(chain),
-                              cost_model=int(os.environ.get("TA3N_COST_MODEL", "0")),
-                              split_k=int(os.environ.get("TA3N_SPLIT_K", "0")) if split_k is None else int(split_k),
+                              aggregation=_lib.AGG_AVGPOOL if self.aggregation == "avgpool" else _lib.AGG_TRN_M,
+                              wgrads_late=int(wgrads_late), chain=int(chain), cost_model=sw.cost_model, split_k=sw.split_k,
                               shared_fc_layers=self.add_fc)
         self.chain = bool(chain)
-        self.Bs, self.Bt, self.T, self.D, self.C = batch_source, batch_target, num_segments, feature_dim, num_class
-        self.B = batch_source + batch_target
-        self.F = min(fc_dim, feature_dim)
-        self.dropout_i, self.dropout_v = dropout_i, dropout_v
-        self.momentum, self.weight_decay, self.clip = momentum, weight_decay, clip
-        self.pg = process_group
-        self.world, self.rank = 1, 0
-        if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self.world = torch.distributed.get_world_size(process_group)
-            self.rank = torch.distributed.get_rank(process_group)
-        if self.optimizer == "Adam" and self.world > 1:
-            raise NotImplementedError(adam_refusal(world=self.world))
-        if self.class_weights is not None and self.world > 1:
-            raise NotImplementedError(weights_refusal(self.class_weights, None, num_class=num_class, world=self.world))
-        if (self.target_labels or self.target_entropy) and self.world > 1:
-            raise NotImplementedError(target_refusal("Sv" if self.target_labels else "uSv", "target_entropy" if self.target_entropy else "none",
-                                                     world=self.world))
-        # The DA options under more than one rank follow what the reference's nn.DataParallel does with them (main.py:79): the discrepancy
-        # loss is taken on the gathered global batch (discrepancy()); MCD's discrepancy is a mean over the global target batch
-        # (mcd_second_forward()); BatchNorm statistics are PER REPLICA - each replica normalises its own slice of the batch with its own
-        # batch statistics (torch's DataParallel replicates the module; nothing synchronises the statistics) - and the running
-        # buffers that persist are replica 0's (sync_buffers()).
+
+    def _allocate_buffers(self, sw: "_Switches", fused: bool) -> None:
+        """Parameters, gradients, optimiser state, the workspace(s) and the static input buffer; which step the plan gives this engine."""
         p = self.plan
         with torch.cuda.device(self.device):
             self.P = torch.zeros(p.param_floats, dtype=torch.float32, device=self.device)
@@ -422,8 +488,13 @@ class TrainEngine:
             self.X = torch.zeros(self.B * self.T, self.D, dtype=torch.float32, device=self.device)
             self._L = _lib.lib()
             _lib.check(self._L.ta3n_init_workspace(p.handle, self.ws.data_ptr(), self._stream()), "ta3n_init_workspace")
-        off, n = p.region("labels")
-        self._labels = self.ws[off:off + n].view(torch.int32)
+        self._labels = self.region("labels").view(torch.int32)
+        self.loss_d = None                       # device scalar: the discrepancy loss of the last step (main.py's loss_d)
+        self._disc_scratch = None                # (native path: kernel matrices, stacked rows, the loss scalar in its last float)
+        self.loss_s = None                       # device scalar: the MCD discrepancy loss of the last step (main.py's loss_s)
+        self.loss_c2 = None                      # ... and the second classifier's cross-entropy on the source rows
+        self.loss_e_shift = None                 # MCD + attentive entropy: (d total, d loss_e) that moving the target rows' entropy term to the
+                                                 # second pass's logits adds to what the loss kernel logged (main.py:549 vs :559-562)
         self._mcd_buf: Optional[torch.Tensor] = None
         self.mcd_raw_seeds = None                # ens_DA MCD: the second pass's two dropout stream seeds as given (None: derived from the first pass's)
         self.ws2: Optional[torch.Tensor] = None      # ens_DA MCD: workspace and gradient buffer of the reversed second pass
@@ -436,7 +507,7 @@ class TrainEngine:
                 # the loss assembly of the two passes from the library (ta3n_mcd_source_loss / ta3n_mcd_second_loss; TA3N_NATIVE_MCD=0: the torch
                 # form of rounds 4-5, kept for A/B): per-row terms [3 B] + the four scalars {loss_c2, loss_s, d total, d loss_e} at the end
                 self._mcd_buf = torch.zeros(3 * self.B + 4, dtype=torch.float32, device=self.device)
-        self._mcd_native = self.ens_DA == "MCD" and os.environ.get("TA3N_NATIVE_MCD", "1") != "0"
+        self._mcd_native = self.ens_DA == "MCD" and sw.native_mcd
         if self.class_weights is not None:      # region "class_w": once, into every workspace whose launches take a class cross-entropy
             w = torch.tensor(self.class_weights, dtype=torch.float32, device=self.device)
             off, _ = p.region("class_w")
@@ -449,7 +520,7 @@ class TrainEngine:
         # as the unfused launch lists: the same results from about twice the launches.  Said once, not silently (describe()).
         self.fused_fallback: Optional[str] = None
         if fused and not p.has_fused_step:
-            self.fused_fallback = (f"no fused step for num_class {num_class}, fc_dim {self.F} (needs num_class <= 64 and fc_dim <= 2048): "
+            self.fused_fallback = (f"no fused step for num_class {self.C}, fc_dim {self.F} (needs num_class <= 64 and fc_dim <= 2048): "
                                    "forward / loss / backward run as the unfused launch lists")
             if self.rank == 0:
                 print(f"[ta3n] {self.fused_fallback}", flush=True)
@@ -457,19 +528,25 @@ class TrainEngine:
         # the shared frame FC updates on a side stream beside the next step's first launch (include/ta3n_hip.h: ta3n_sgd_range)
         self._pending = None
         self._side: Optional[torch.cuda.Stream] = None
-        # TA3N_DDP_SELFTEST=1: take the N > 1 code path (split launches + RCCL buckets) in a 1-rank process group
-        self._ddp_selftest = os.environ.get("TA3N_DDP_SELFTEST") == "1"
+        self._job_last_hyper = None      # ta3n_hyper of the last step a _steps_job enqueued (becomes self._hyper in _steps_done)
         # TA3N_SIDE_UPDATE=0: keep the pipelined update a launch of its own (ta3n_sgd_step_next)
-        self._side_update = (os.environ.get("TA3N_SIDE_UPDATE", "1") == "1" and
-                             self._L.ta3n_has_pipelined_step(self.plan.handle) == 1)
-        if self.optimizer == "Adam":      # the side workgroups of the step's first launch (EPI_SGD tasks) apply Nesterov SGD: not taken under Adam
-            self._side_update = False
+        # (the side workgroups of the step's first launch - EPI_SGD tasks - apply Nesterov SGD: not taken under Adam)
+        self._side_update = sw.side_update and self.optimizer != "Adam" and self._L.ta3n_has_pipelined_step(p.handle) == 1
         self.adam_step_count = 0          # Adam: updates applied so far (the `step` of torch.optim.Adam's state)
         self.force_unfused_norm = False   # Adam: take the clip norm from the gradient-norm pass even where the fused step left its partials
+        self._n_first = next(off for name, off, _, _ in p.params if not name.startswith("fc_feature_shared_source"))
+        self._P2: Optional[torch.Tensor] = None      # second parameter buffer of the fused-update steps (train_steps)
+
+    def _setup_exchange(self, sw: "_Switches", native_comm) -> None:
+        """The gradient exchange of N > 1 ranks (or of the 1-rank self-test): the communicator (native_comm makes it), the bf16 transport
+        scratch, the peer path, the layout of the sharded update."""
+        p = self.plan
+        # TA3N_DDP_SELFTEST=1: take the N > 1 code path (split launches + RCCL buckets) in a 1-rank process group
+        self._ddp_selftest = sw.ddp_selftest
+        ddp = self.world > 1 or self._ddp_selftest
         # 1 (default): one all-reduce after the last launch; 2: everything but the shared frame FC's gradient is reduced while
         # the last launch runs (worth it only when that launch is longer than an extra collective's fixed cost)
-        self._ddp_buckets = int(os.environ.get("TA3N_DDP_BUCKETS", "1")) if ddp_buckets is None else int(ddp_buckets)
-        self._n_first = next(off for name, off, _, _ in p.params if not name.startswith("fc_feature_shared_source"))
+        self._ddp_buckets = sw.ddp_buckets
         # N > 1 (or the 1-rank self-test): RCCL straight from the C ABI on the step's streams (TA3N_DDP_NATIVE=0: through
         # torch.distributed instead).
         self.comm = None
@@ -477,11 +554,11 @@ class TrainEngine:
         self._g16 = None
         self._comm_stream: Optional[torch.cuda.Stream] = None
         rccl_group = self.world == 1 or torch.distributed.get_backend(self.pg) == "nccl"     # gloo (CPU / shared-GPU tests): torch path
-        if (self.world > 1 or self._ddp_selftest) and rccl_group and os.environ.get("TA3N_DDP_NATIVE", "1") == "1":
+        if ddp and rccl_group and sw.ddp_native:
             # Either EVERY rank uses the library's communicator or none does (parallel.NativeComm agrees on that over the torch group
             # before and after ncclCommInitRank): ranks that disagreed would enqueue different collectives and hang.
             try:
-                self.comm = (parallel.shared_native_comm if share_comm else parallel.NativeComm)(self.pg if self.world > 1 else None, self.device)
+                self.comm = native_comm(self.pg if self.world > 1 else None, self.device)
             except Exception as ex:      # noqa: BLE001 - raised on every rank together: still RCCL, through torch.distributed
                 self.comm = None
                 self.comm_fallback = f"{type(ex).__name__}: {ex}"
@@ -491,17 +568,14 @@ class TrainEngine:
             # Gradient transport: fp32 unless asked otherwise (grad_transport="bf16" / TA3N_DDP_BF16=1: every rank's gradients are
             # rounded to bf16 and SUMMED in bf16 - half the xGMI bytes, but the N-rank result then differs from the 1-rank /
             # fp32-transport one by up to ~N * 2^-9 relative per element, and the clip norm is taken on the rounded sum)
-            want16 = (grad_transport == "bf16") if grad_transport is not None else os.environ.get("TA3N_DDP_BF16", "0") == "1"
-            if self.comm is not None and want16:
+            if self.comm is not None and sw.grad_bf16:
                 self._g16 = torch.zeros(p.live_floats, dtype=torch.bfloat16, device=self.device)
         # TA3N_DDP_PEER=1: the exchange as a two-shot all-reduce over peer-mapped buffers (csrc/ta3n_peer.hip) instead of ncclAllReduce;
         # opt-in (only its protocol could be exercised on the one-GPU boxes this was built on); any backend of the process group
         self.peer = None
-        want_peer = (os.environ.get("TA3N_DDP_PEER", "0") == "1") if peer_exchange is None else bool(peer_exchange)
-        if (self.world > 1 or self._ddp_selftest) and want_peer:
-            want16 = (grad_transport == "bf16") if grad_transport is not None else os.environ.get("TA3N_DDP_BF16", "0") == "1"
+        if ddp and sw.peer_exchange:
             try:
-                self.peer = parallel.PeerComm(self.pg if self.world > 1 else None, self.device, p.live_floats, bf16=want16)
+                self.peer = parallel.PeerComm(self.pg if self.world > 1 else None, self.device, p.live_floats, bf16=sw.grad_bf16)
                 if self.comm is not None:      # ta3n_all_reduce_sum / ta3n_train_steps of the communicator go through the peer path
                     _lib.check(self._L.ta3n_comm_attach_peer(self.comm.handle, self.peer.handle), "ta3n_comm_attach_peer")
             except Exception as ex:      # noqa: BLE001 - raised on every rank together (PeerComm): keep the default exchange
@@ -510,7 +584,21 @@ class TrainEngine:
                     print(f"[ta3n] peer all-reduce unavailable ({type(ex).__name__}: {ex}); using the default exchange", flush=True)
         if self.comm is not None and self.peer is None and getattr(self.comm, "shared", False):
             self._L.ta3n_comm_attach_peer(self.comm.handle, None)      # (a shared communicator may still carry the previous engine's transport)
-        # use_bn: running [source, target][mean, var][F] (nn.BatchNorm1d: zeros / ones, momentum 0.1, unbiased variance) + batch counter
+        # Sharded update (TA3N_DDP_SHARDED=1 / sharded_update=True; N > 1 or the 1-rank self-test, fused step): the gradient exchange as
+        # reduce-scatter + all-gather around an optimiser pass that touches only this rank's 1 / world of the parameters
+        # (include/ta3n_hip.h: ta3n_sharded_update).  Every rank must make the same choice.
+        self._sharded = bool(sw.sharded_update and ddp and self.fused and self.peer is None and
+                             self._L.ta3n_has_pipelined_step(p.handle) == 1)
+        self._shard_own = self._shard_layout = None
+        if self._sharded:
+            own, lay = (C.c_int64 * 4)(), (C.c_int64 * 4)()
+            _lib.check(self._L.ta3n_shard_ranges(p.handle, self.rank, self.world, own, lay), "ta3n_shard_ranges")
+            self._shard_own, self._shard_layout = list(own), list(lay)
+            if self._g16 is not None:      # bf16 gradient transport: the scratch covers the padded end of region B
+                self._g16 = torch.zeros(max(p.live_floats, self._shard_layout[3]), dtype=torch.bfloat16, device=self.device)
+
+    def _setup_batchnorm(self) -> None:
+        """use_bn: running [source, target][mean, var][F] (nn.BatchNorm1d: zeros / ones, momentum 0.1, unbiased variance) + batch counter."""
         self.bn_running: Optional[torch.Tensor] = None
         self.bn_batches = 0
         if self.use_bn != "none":
@@ -519,24 +607,6 @@ class TrainEngine:
             self.bn_running = self.region("bn_run").view(2, 2, self.F)
             self.bn_running[:, 0] = 0.0
             self.bn_running[:, 1] = 1.0
-        # Sharded update (TA3N_DDP_SHARDED=1 / sharded_update=True; N > 1 or the 1-rank self-test, fused step): the gradient exchange as
-        # reduce-scatter + all-gather around an optimiser pass that touches only this rank's 1 / world of the parameters
-        # (include/ta3n_hip.h: ta3n_sharded_update).  Every rank must make the same choice.
-        want_sh = (os.environ.get("TA3N_DDP_SHARDED", "0") == "1") if sharded_update is None else bool(sharded_update)
-        self._sharded = bool(want_sh and (self.world > 1 or self._ddp_selftest) and self.fused and self.peer is None and
-                             self._L.ta3n_has_pipelined_step(self.plan.handle) == 1)
-        self._shard_own = self._shard_layout = None
-        if self._sharded:
-            own, lay = (C.c_int64 * 4)(), (C.c_int64 * 4)()
-            _lib.check(self._L.ta3n_shard_ranges(p.handle, self.rank, self.world, own, lay), "ta3n_shard_ranges")
-            self._shard_own, self._shard_layout = list(own), list(lay)
-            if self._g16 is not None:      # bf16 gradient transport: the scratch covers the padded end of region B
-                self._g16 = torch.zeros(max(p.live_floats, self._shard_layout[3]), dtype=torch.bfloat16, device=self.device)
-        self._P2: Optional[torch.Tensor] = None      # second parameter buffer of the fused-update steps (train_steps)
-        self.step_count = 0
-        self.skip_collective = False
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self._hyper = _lib.Hyper()
 
     def describe(self) -> str:
         """One line: the configuration this engine runs, the launch lists of its step included."""
@@ -558,15 +628,12 @@ class TrainEngine:
         t = self.ws[off:off + n]
         return t.view(shape) if shape is not None else t
 
+    def _views(self, src: torch.Tensor, live_only: bool = False) -> Dict[str, torch.Tensor]:
+        """{name: view of the parameter's floats in the flat buffer src, in its shape} (live_only: a buffer that covers the live prefix)."""
+        return {name: src[off:off + math.prod(shape)].view(shape) for name, off, shape, live in self.plan.params if live or not live_only}
+
     def param_views(self, src: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        src = self.P if src is None else src
-        out = {}
-        for name, off, shape, live in self.plan.params:
-            n = 1
-            for s in shape:
-                n *= s
-            out[name] = src[off:off + n].view(shape)
-        return out
+        return self._views(self.P if src is None else src)
 
     def load_state(self, state: Dict[str, torch.Tensor]) -> None:
         """Copy reference-named tensors (state_dict keys, models.py:141-294) into the flat buffer."""
@@ -608,42 +675,37 @@ class TrainEngine:
     def momentum_views(self) -> Dict[str, torch.Tensor]:
         """Momentum buffers of the live parameters (views into the flat buffer; zero = "no update yet", which is what
         torch.optim.SGD's lazily created buffer amounts to: buf = g on first use = mu * 0 + g)."""
-        out = {}
-        for name, off, shape, live in self.plan.params:
-            if live:
-                n = 1
-                for s in shape:
-                    n *= s
-                out[name] = self.M[off:off + n].view(shape)
-        return out
+        return self._views(self.M, live_only=True)
 
     def adam_views(self) -> Dict[str, tuple]:
         """optimizer="Adam": {name: (exp_avg view, exp_avg_sq view)} over the live parameters (zero = no update yet; the step count,
         one for all of them, is self.adam_step_count)."""
         if self.optimizer != "Adam":
             raise _lib.Ta3nError("adam_views: this engine was built with optimizer='SGD' (momentum_views)")
-        m = self.momentum_views()
-        out = {}
-        for name, off, shape, live in self.plan.params:
-            if live:
-                out[name] = (m[name], self.V[off:off + m[name].numel()].view(shape))
-        return out
+        m, v = self._views(self.M, live_only=True), self._views(self.V, live_only=True)
+        return {name: (m[name], v[name]) for name in m}
 
-    def _adam_fused_norm(self) -> int:
-        """1 where the SGD path takes ta3n_sgd_step_fused: the fused step's per-tile partials are the norm of the final gradients."""
-        return int(self.fused and self.world == 1 and not self._ddp_selftest and not self.force_unfused_norm)
+    def _fused_norm(self) -> int:
+        """1 where the update takes the clip norm from the fused step's per-tile partials (SGD: ta3n_sgd_step_fused), 0 where a
+        gradient-norm pass forms it: the partials are the norm of the FINAL gradients only on one rank without the self-test's exchange.
+        Adam can be told to take the pass anyway (force_unfused_norm)."""
+        return int(self.fused and self.world == 1 and not self._ddp_selftest and
+                   not (self.optimizer == "Adam" and self.force_unfused_norm))
 
     def _adam_args(self, lr: float, wd: float, clip: float):
         return (float(lr), self.betas[0], self.betas[1], self.eps, float(wd), float(clip), self.adam_step_count + 1)
 
-    def adam_range(self, lo: int, hi: int, lr: float, fused_norm: Optional[int] = None, step: Optional[int] = None) -> None:
-        """ta3n_adam_range over floats [lo, hi) of the live prefix as update number `step` (default: the next one).  Does not count the
-        update: the caller that has covered the whole prefix adds 1 to self.adam_step_count."""
-        args = list(self._adam_args(lr, self.weight_decay, float(self.clip) if self.clip is not None else 0.0))
+    def adam_range(self, lo: int, hi: int, lr: float, fused_norm: Optional[int] = None, step: Optional[int] = None,
+                   weight_decay: Optional[float] = None, clip: Optional[float] = None) -> None:
+        """ta3n_adam_range over floats [lo, hi) of the live prefix as update number `step` (default: the next one), with the engine's
+        weight decay and clip unless given (a postponed update carries its own).  Does not count the update: the caller that has covered
+        the whole prefix adds 1 to self.adam_step_count."""
+        args = list(self._adam_args(lr, self.weight_decay if weight_decay is None else weight_decay,
+                                    _clip_value(self.clip) if clip is None else clip))
         if step is not None:
             args[-1] = int(step)
         _lib.check(self._L.ta3n_adam_range(self.plan.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
-                                           self.ws.data_ptr(), int(lo), int(hi), self._adam_fused_norm() if fused_norm is None else int(fused_norm),
+                                           self.ws.data_ptr(), int(lo), int(hi), self._fused_norm() if fused_norm is None else int(fused_norm),
                                            *args, self._stream()), "ta3n_adam_range")
 
     def adam_step(self, lr: Optional[float] = None, fused_norm: Optional[int] = None) -> None:
@@ -683,7 +745,7 @@ class TrainEngine:
         h.beta[0], h.beta[1], h.beta[2] = float(beta[0]), float(beta[1]), float(beta[2])
         h.gamma, h.lr = float(gamma), float(lr)
         h.momentum, h.weight_decay = float(self.momentum), float(self.weight_decay)
-        h.clip = float(self.clip) if self.clip is not None else 0.0
+        h.clip = _clip_value(self.clip)
         h.p_drop_i, h.p_drop_v = float(self.dropout_i), float(self.dropout_v)
         h.seed_i, h.seed_v = dropout_seeds(self.step_count if seed is None else seed, self.rank)
         if raw_seeds is not None:      # the two dropout stream seeds as given (a caller that draws them itself, like VideoModel.forward does)
@@ -725,7 +787,7 @@ class TrainEngine:
         if self.dis_DA == "none":
             return
         ns, nt = int(self._hyper.valid_source), int(self._hyper.valid_target)
-        if self.world == 1 and os.environ.get("TA3N_NATIVE_DISCREPANCY", "1") != "0":
+        if self.world == 1 and self._switches.native_discrepancy:
             # one rank: the whole term from the library (ta3n_discrepancy) - the torch glue around the same kernels (cat / slices / autograd /
             # a dozen small allocations) cost 0.4 - 1.1 ms of host time per step against 0.2 ms for everything else the step launches
             (oy, _), (ov, nv), (ogy, _), (ogv, _) = (self.plan.region(k) for k in ("Y", "V", "gY", "gV_ext"))
@@ -932,8 +994,7 @@ class TrainEngine:
         if self._sharded:
             self.fused_step()
             self._shard_reduce_scatter()
-            h = self._hyper
-            self._sharded_update(float(h.lr), float(h.momentum), float(h.weight_decay), float(h.clip), None)
+            self._apply_update()
             return
         if self.fused and (self.world > 1 or self._ddp_selftest) and self._ddp_buckets == 2:
             self._fused_step_overlapped_allreduce()
@@ -953,40 +1014,61 @@ class TrainEngine:
                 self.mcd_second_backward()
         self.all_reduce_grads()
         if self.optimizer == "Adam":
-            # the norm partials of the fused step only where sgd_step_fused is taken below; by value: lr, weight decay and clip of set_hyper
-            h = self._hyper
-            _lib.check(self._L.ta3n_adam_range(self.plan.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(),
-                                               self.ws.data_ptr(), 0, self.plan.live_floats, self._adam_fused_norm(),
-                                               *self._adam_args(h.lr, h.weight_decay, h.clip), self._stream()), "ta3n_adam_range")
-            self.adam_step_count += 1
-        elif self.fused and self.world == 1 and not self._ddp_selftest:
+            self._apply_update()
+        elif self._fused_norm():
             self.sgd_step_fused()       # local gradients are final: their norm partials are already in ws
         else:
             self.sgd_step()
+
+    # ---- the update of the step before, where it opens or closes a step ----
+    def _apply_update(self, scalars=None, nxt: Optional["_lib.Hyper"] = None, fused_norm: Optional[int] = None) -> None:
+        """The whole-prefix update (lr, mu, wd, clip) = scalars (default: by value, those of the step set_hyper last described) on the
+        gradients in self.G, as this engine's optimiser and exchange take it: the sharded update, Adam (counted in adam_step_count) or
+        Nesterov SGD.  nxt: the next step's ta3n_hyper, which the same launch then leaves in the workspace (ta3n_sgd_step_next /
+        ta3n_adam_step_next).  The schedules that fuse the update with a step (the side-stream split of _apply_pending,
+        ta3n_train_step_after_update, the multi-step calls) do not come through here."""
+        hy = self._hyper
+        lr, mu, wd, clip = scalars or (float(hy.lr), float(hy.momentum), float(hy.weight_decay), float(hy.clip))
+        if self._sharded:
+            self._sharded_update(lr, mu, wd, clip, nxt)
+            return
+        fused_norm = self._fused_norm() if fused_norm is None else fused_norm
+        L, h = self._L, self.plan.handle
+        if self.optimizer == "Adam":
+            if nxt is None:
+                self.adam_range(0, self.plan.live_floats, lr, fused_norm=fused_norm, weight_decay=wd, clip=clip)
+            else:
+                _lib.check(L.ta3n_adam_step_next(h, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), self.ws.data_ptr(),
+                                                 fused_norm, *self._adam_args(lr, wd, clip), C.byref(nxt), self._stream()), "ta3n_adam_step_next")
+            self.adam_step_count += 1
+        elif nxt is None:
+            _lib.check(L.ta3n_sgd_range(h, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.ws.data_ptr(), 0, self.plan.live_floats,
+                                        fused_norm, lr, mu, wd, clip, self._stream()), "ta3n_sgd_range")
+        else:
+            _lib.check(L.ta3n_sgd_step_next(h, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.ws.data_ptr(), fused_norm,
+                                            lr, mu, wd, clip, C.byref(nxt), self._stream()), "ta3n_sgd_step_next")
 
     # ---- deferred, overlapped update ----
     def _apply_pending(self, overlap: bool):
         """Enqueue the pending update.  overlap: returns the event the next step must join after its first launch."""
         if self._pending is None:
             return None
-        lr, mu, wd, clip = self._pending
-        self._pending = None
-        L, h = self._L, self.plan.handle
-        if self.optimizer == "Adam":      # one launch on the step's stream (the side-stream split is an SGD schedule): nothing to join
-            _lib.check(L.ta3n_adam_range(h, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.V.data_ptr(), self.ws.data_ptr(),
-                                         0, self.plan.live_floats, self._adam_fused_norm(), *self._adam_args(lr, wd, clip), self._stream()),
-                       "ta3n_adam_range")
-            self.adam_step_count += 1
+        scalars, self._pending = self._pending, None
+        fused_norm = self._fused_norm()
+        if self._ddp_selftest and self.optimizer != "Adam":
+            # A known difference from the other schedules, kept as it is (DESIGN.md 3): under TA3N_DDP_SELFTEST=1 this site alone - the
+            # update that opens a train_step_deferred call, and what flush() applies - still clips on the fused step's partials, i.e. on
+            # the gradients as they were before the self-test's exchange.
+            fused_norm = int(self.fused and self.world == 1)
+        if self.optimizer == "Adam" or not overlap:      # Adam: one launch on the step's stream (the side-stream split is an SGD schedule): nothing to join
+            self._apply_update(scalars, fused_norm=fused_norm)
             return None
-        fused_norm = int(self.fused and self.world == 1)
+        L, h = self._L, self.plan.handle
         main = torch.cuda.current_stream(self.device)
 
         def rng(lo, hi, stream):
             _lib.check(L.ta3n_sgd_range(h, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), self.ws.data_ptr(), lo, hi,
-                                        fused_norm, lr, mu, wd, clip, C.c_void_p(stream.cuda_stream)), "ta3n_sgd_range")
-        if not overlap:
-            rng(0, self.plan.live_floats, main)
-            return None
+                                        fused_norm, *scalars, C.c_void_p(stream.cuda_stream)), "ta3n_sgd_range")
         if self._side is None:
             self._side = torch.cuda.Stream(self.device)
         rng(0, self._n_first, main)                 # (+ the gradient-norm pass when the norm is not fused)
@@ -1000,11 +1082,6 @@ class TrainEngine:
 
     def flush(self) -> None:
         """Apply a deferred update (train_step(defer_update=True)) so that the parameters are current."""
-        if self._sharded and self._pending is not None:
-            lr, mu, wd, clip = self._pending
-            self._pending = None
-            self._sharded_update(lr, mu, wd, clip, None)
-            return
         self._apply_pending(overlap=False)
 
     # ---- sharded update (reduce-scatter / own-shard optimiser / all-gather) ----
@@ -1053,7 +1130,7 @@ class TrainEngine:
                                                 self.ws.data_ptr(), self._stream(), ev), "ta3n_train_step_join")
         self._bn_track()
         self.all_reduce_grads()
-        self._pending = (float(lr), float(self.momentum), float(self.weight_decay), float(self.clip) if self.clip is not None else 0.0)
+        self._pending = _update_scalars(self, lr)
         self.step_count += 1
 
     def train_step_pipelined(self, beta: Sequence[float], gamma: float, lr: float, **hyper_kw) -> None:
@@ -1064,47 +1141,30 @@ class TrainEngine:
             raise _lib.Ta3nError("pipelined updates need the fused step")
         first = self._pending is None
         self.set_hyper(beta, gamma, lr, train=True, upload=first, **hyper_kw)
-        if self._sharded:
-            if not first:
-                lr_p, mu, wd, clip = self._pending
-                self._pending = None
-                self._sharded_update(lr_p, mu, wd, clip, self._hyper)
-            self.fused_step()
-            self._shard_reduce_scatter()
-            self._pending = (float(lr), float(self.momentum), float(self.weight_decay), float(self.clip) if self.clip is not None else 0.0)
-            self.step_count += 1
-            return
-        two_buckets = (self.world > 1 or self._ddp_selftest) and self._ddp_buckets == 2
+        two_buckets = not self._sharded and (self.world > 1 or self._ddp_selftest) and self._ddp_buckets == 2
         stepped = False
         if not first:
-            lr_p, mu, wd, clip = self._pending
-            self._pending = None
-            fused_norm = int(self.world == 1 and not self._ddp_selftest)
-            if self.optimizer == "Adam":      # one launch: the update of the step before + this step's scalars (ta3n_adam_step_next)
-                _lib.check(self._L.ta3n_adam_step_next(self.plan.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(),
-                                                       self.V.data_ptr(), self.ws.data_ptr(), self._adam_fused_norm(),
-                                                       *self._adam_args(lr_p, wd, clip), C.byref(self._hyper), self._stream()),
-                           "ta3n_adam_step_next")
-                self.adam_step_count += 1
-            elif self._side_update and not two_buckets:
+            scalars, self._pending = self._pending, None
+            if self._side_update and not two_buckets and not self._sharded:
                 # the update of everything but the shared frame FC rides in the new step's first launch
                 _lib.check(self._L.ta3n_train_step_after_update(self.plan.handle, self.X.data_ptr(), self.P.data_ptr(),
-                                                                self.G.data_ptr(), self.M.data_ptr(), self.ws.data_ptr(), fused_norm,
-                                                                lr_p, mu, wd, clip, C.byref(self._hyper), self._stream()),
+                                                                self.G.data_ptr(), self.M.data_ptr(), self.ws.data_ptr(), self._fused_norm(),
+                                                                *scalars, C.byref(self._hyper), self._stream()),
                            "ta3n_train_step_after_update")
                 self._bn_track()
                 stepped = True
-            else:
-                _lib.check(self._L.ta3n_sgd_step_next(self.plan.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(),
-                                                      self.ws.data_ptr(), fused_norm, lr_p, mu, wd, clip, C.byref(self._hyper),
-                                                      self._stream()), "ta3n_sgd_step_next")
-        if two_buckets:
+            else:      # one launch: the update of the step before + this step's scalars
+                self._apply_update(scalars, self._hyper)
+        if self._sharded:
+            self.fused_step()
+            self._shard_reduce_scatter()
+        elif two_buckets:
             self._fused_step_overlapped_allreduce()
         else:
             if not stepped:
                 self.fused_step()
             self.all_reduce_grads()
-        self._pending = (float(lr), float(self.momentum), float(self.weight_decay), float(self.clip) if self.clip is not None else 0.0)
+        self._pending = _update_scalars(self, lr)
         self.step_count += 1
 
     def hyper_for(self, beta: Sequence[float], gamma: float, lr: float, step: Optional[int] = None, **hyper_kw) -> "_lib.Hyper":
@@ -1132,11 +1192,6 @@ class TrainEngine:
         if m == 1:
             C.memmove(hy, C.byref(h0), size)
             return hy
-        if _LEGACY_HOST_PREP:              # A/B aid: the per-entry loop of rounds 3-4
-            for k in range(m):
-                h = h0 if k == 0 else self.hyper_for(*entries[k], step=step0 + k)
-                C.memmove(C.byref(hy, k * size), C.byref(h), size)
-            return hy
         np, dt = _hyper_dtype()
         np.frombuffer(hy, dtype=np.uint8).reshape(m, size)[:] = np.frombuffer(h0, dtype=np.uint8)      # every entry = entry 0 ...
         a = np.frombuffer(hy, dtype=dt)
@@ -1156,6 +1211,14 @@ class TrainEngine:
         if first == 0:
             return self._labels[: self.Bs]
         return self._labels[self.Bs:] if self.target_labels else None
+
+    def _gather_step(self, feeds, k: int) -> None:
+        """Step k's batch halves assembled on the device from the feeds (for a step that goes out on its own, not inside a multi-step call)."""
+        if feeds is None:
+            return
+        for (store, ids), first in zip(feeds, (0, self.Bs)):
+            if store is not None:
+                store.gather_into(self, ids[k], first, labels_out=self._feed_labels_out(first))
 
     def _feeds(self, feeds, k0: int):
         """ta3n_feed structs (and the id tables that must outlive the enqueued gathers) of a multi-step call."""
@@ -1193,7 +1256,7 @@ class TrainEngine:
             self._feed_keep_prev, self._feed_keep = getattr(self, "_feed_keep", None), []
         ddp = self.world > 1 or self._ddp_selftest
         if fused_update is None:
-            fused_update = os.environ.get("TA3N_FUSED_UPDATE", "0") == "1"
+            fused_update = self._switches.fused_update
         if fused_update and self.optimizer == "Adam":
             raise NotImplementedError(adam_refusal(fused_update=True))
         if fused_update and not ddp and self.fused and self.bn_running is None and self._L.ta3n_has_fused_update(self.plan.handle) == 1:
@@ -1205,7 +1268,7 @@ class TrainEngine:
             fd, keep = self._feeds(feeds, 0)
             _lib.check(self._L.ta3n_train_steps_fused_update(
                 self.plan.handle, self.X.data_ptr(), self.P.data_ptr(), self._P2.data_ptr(), self.G.data_ptr(), self.M.data_ptr(),
-                self.ws.data_ptr(), float(self.momentum), float(self.weight_decay), float(self.clip) if self.clip is not None else 0.0,
+                self.ws.data_ptr(), float(self.momentum), float(self.weight_decay), _clip_value(self.clip),
                 hy, n, C.byref(fd[0]) if fd[0] is not None else None, C.byref(fd[1]) if fd[1] is not None else None, self._stream()),
                 "ta3n_train_steps_fused_update")
             if keep:
@@ -1217,13 +1280,10 @@ class TrainEngine:
             # no single library call for this configuration (torch.distributed fallback, two buckets, TA3N_SIDE_UPDATE=0, unfused):
             # the same steps one by one, the batch of each assembled on the device before it
             for k, (beta, gamma, lr) in enumerate(schedule):
-                if feeds is not None:
-                    for (store, ids), first in zip(feeds, (0, self.Bs)):
-                        if store is not None:
-                            store.gather_into(self, ids[k], first, labels_out=self._feed_labels_out(first))
+                self._gather_step(feeds, k)
                 (self.train_step_pipelined if self.fused else self.train_step)(beta, gamma, lr)
             return
-        if _split and n >= 4 and not self._sharded and not _LEGACY_HOST_PREP:
+        if _split and n >= 4 and not self._sharded:
             # The first step goes out on its own and the rest of the schedule is prepared while the GPU runs it (a long schedule in two
             # further pieces: 16 steps, then the rest): the host work in front of a call's first launch (the ta3n_hyper array: ~7 us +
             # ~0.5 us per step) then costs the GPU one step's preparation, whatever the length of the schedule.  Same launches in the
@@ -1240,24 +1300,21 @@ class TrainEngine:
             return
         if self.optimizer == "Adam":      # the same pending-update contract: update number adam_step_count + 1 + k opens step k
             _lib.check(self._L.ta3n_train_steps_adam(job.plan, job.x, job.params, job.grads, job.momentum, self.V.data_ptr(), job.ws,
-                                                     self._adam_fused_norm(), *self._adam_args(job.lr_pending, job.weight_decay, job.clip),
+                                                     self._fused_norm(), *self._adam_args(job.lr_pending, job.weight_decay, job.clip),
                                                      job.hypers, n_run, job.source, job.target, job.stream), "ta3n_train_steps_adam")
             self.adam_step_count += n_run
-            self._steps_done(schedule, keep, n_run)
-            return
-        if self._sharded:      # the same steps with the sharded update; region B's collectives on a second stream
+        elif self._sharded:      # the same steps with the sharded update; region B's collectives on a second stream
             if self._comm_stream is None:
                 self._comm_stream = torch.cuda.Stream(self.device)
-            two = os.environ.get("TA3N_DDP_SHARDED_STREAMS", "1") == "2"
             _lib.check(self._L.ta3n_train_steps_sharded(job.plan, job.comm, job.x, job.params, job.grads, job.momentum, job.ws, job.lr_pending,
                                                         job.momentum_coef, job.weight_decay, job.clip, job.hypers, n_run, job.source, job.target,
                                                         job.scratch_bf16, job.stream,
-                                                        C.c_void_p(self._comm_stream.cuda_stream) if two else None), "ta3n_train_steps_sharded")
-            self._steps_done(schedule, keep, n_run)
-            return
-        _lib.check(self._L.ta3n_train_steps(job.plan, job.x, job.params, job.grads, job.momentum, job.ws, job.fused_norm, job.lr_pending,
-                                            job.momentum_coef, job.weight_decay, job.clip, job.hypers, n_run, job.source, job.target,
-                                            job.comm, job.scratch_bf16, job.stream), "ta3n_train_steps")
+                                                        C.c_void_p(self._comm_stream.cuda_stream) if self._switches.sharded_two_streams else None),
+                       "ta3n_train_steps_sharded")
+        else:
+            _lib.check(self._L.ta3n_train_steps(job.plan, job.x, job.params, job.grads, job.momentum, job.ws, job.fused_norm, job.lr_pending,
+                                                job.momentum_coef, job.weight_decay, job.clip, job.hypers, n_run, job.source, job.target,
+                                                job.comm, job.scratch_bf16, job.stream), "ta3n_train_steps")
         self._steps_done(schedule, keep, n_run)
 
     def can_batch_steps(self) -> bool:
@@ -1278,22 +1335,18 @@ class TrainEngine:
         n, k0 = len(schedule), 0
         ddp = self.world > 1 or self._ddp_selftest
         if self._pending is None:
-            if feeds is not None:
-                for (store, ids), first in zip(feeds, (0, self.Bs)):
-                    if store is not None:
-                        store.gather_into(self, ids[0], first, labels_out=self._feed_labels_out(first))
+            self._gather_step(feeds, 0)
             self.train_step_pipelined(*schedule[0])
             k0 = 1
             if n == 1:
                 return None, [], 0
         hy = self.hyper_array(schedule[k0:], self.step_count)
         self._job_last_hyper = _lib.Hyper.from_buffer_copy(hy[n - k0 - 1])      # (for _steps_done: the scalars of the last step enqueued)
-        lr_p, mu, wd, clip = self._pending
         fd, keep = self._feeds(feeds, k0)
         job = _lib.StepsJob()
         job.plan, job.x, job.params, job.grads = self.plan.handle, self.X.data_ptr(), self.P.data_ptr(), self.G.data_ptr()
-        job.momentum, job.ws, job.fused_norm = self.M.data_ptr(), self.ws.data_ptr(), 0 if ddp else 1
-        job.lr_pending, job.momentum_coef, job.weight_decay, job.clip = lr_p, mu, wd, clip
+        job.momentum, job.ws, job.fused_norm = self.M.data_ptr(), self.ws.data_ptr(), self._fused_norm()
+        job.lr_pending, job.momentum_coef, job.weight_decay, job.clip = self._pending
         job.hypers = C.cast(hy, C.POINTER(_lib.Hyper))
         job.source = C.pointer(fd[0]) if fd[0] is not None else None
         job.target = C.pointer(fd[1]) if fd[1] is not None else None
@@ -1308,7 +1361,7 @@ class TrainEngine:
                 self._feed_keep = []
             self._feed_keep.append(keep)
         last = schedule[-1]
-        self._pending = (float(last[2]), float(self.momentum), float(self.weight_decay), float(self.clip) if self.clip is not None else 0.0)
+        self._pending = _update_scalars(self, last[2])
         self._hyper = self._job_last_hyper if self._job_last_hyper is not None else self.hyper_for(*last, step=self.step_count + n_run - 1)
         self._job_last_hyper = None
         self.step_count += n_run
@@ -1375,7 +1428,7 @@ class TrainEngine:
         fused_norm = int(self.world == 1 and not self._ddp_selftest)
         _lib.check(self._L.ta3n_time_update_launches(self.plan.handle, self.X.data_ptr(), self.P.data_ptr(), self.G.data_ptr(),
                                                      self.M.data_ptr(), self.ws.data_ptr(), fused_norm, float(lr), float(self.momentum),
-                                                     float(self.weight_decay), float(self.clip) if self.clip is not None else 0.0,
+                                                     float(self.weight_decay), _clip_value(self.clip),
                                                      self._stream(), reps, out), "ta3n_time_update_launches")
         return float(out[0]), float(out[1])
 

@@ -55,22 +55,16 @@ def validate_options(args, module_path: bool = False) -> None:
     else:
         need(args.optimizer == "SGD", f"--optimizer {args.optimizer} (built: SGD with Nesterov momentum, main.py:83)" +
              (" (built on main.py; train_ddp.py trains with SGD)" if args.optimizer == "Adam" else ""))
+    need(args.dis_DA in ("none", "DAN", "JAN"), f"--dis_DA {args.dis_DA} (built: DAN, JAN)")
+    need(args.ens_DA in ("none", "MCD"), f"--ens_DA {args.ens_DA}")
     if module_path:
-        need(args.dis_DA in ("none", "DAN", "JAN"), f"--dis_DA {args.dis_DA} (built: DAN, JAN)")
-        need(args.ens_DA in ("none", "MCD"), f"--ens_DA {args.ens_DA}")
         if args.dis_DA == "DAN":
             need(len(args.place_dis) == args.add_fc + 2 and args.place_dis[2] == "N",
                  "--place_dis takes add_fc + 2 values [logits, video feature, frame features]; the reference itself fails on the "
                  "frame features (loss.py:49 on a 3-D tensor)")
-    else:
-        need(args.dis_DA in ("none", "DAN", "JAN"), f"--dis_DA {args.dis_DA} (built: DAN, JAN)")
-        need(args.ens_DA in ("none", "MCD"), f"--ens_DA {args.ens_DA}")
-        if args.ens_DA == "MCD":
-            need(args.use_bn == "none", "--ens_DA MCD with --use_bn (use main.py, the module path)")
-    if module_path:
-        need(args.use_bn in ("none", "AdaBN", "AutoDIAL"), f"--use_bn {args.use_bn}")
-    else:
-        need(args.use_bn in ("none", "AdaBN", "AutoDIAL"), f"--use_bn {args.use_bn}")
+    elif args.ens_DA == "MCD":
+        need(args.use_bn == "none", "--ens_DA MCD with --use_bn (use main.py, the module path)")
+    need(args.use_bn in ("none", "AdaBN", "AutoDIAL"), f"--use_bn {args.use_bn}")
     # --use_target Sv (main.py:439-446: the class CE over source + target rows) and --add_loss_DA target_entropy (:542-545): main.py trains
     # them, on the engine (TA3N_FLAG_TARGET_LABELS / TA3N_FLAG_TARGET_ENTROPY: single rank) or on its module path
     if module_path:
