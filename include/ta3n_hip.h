@@ -120,6 +120,19 @@ typedef enum {
  * an ADV flag.  ta3n_plan_create refuses it by name together with TA3N_FLAG_ATTN_ENTROPY (one entropy slot, one --add_loss_DA value), with
  * TA3N_FLAG_MCD (MCD rebinds out_target to the second pass's logits: not built) and on TA3N_AGG_AVGPOOL. */
 #define TA3N_FLAG_TARGET_ENTROPY (1u << 14)
+/* use_attn=='general' on trn-m (models.py:320-325, 359-366, 379-388): the relation features are weighted by a learned layer instead of the
+ * relation discriminators' entropy: w = softmax over the T-1 relations of attn_layer.2(tanh(attn_layer.0(R_j))), V = sum_j (1 + w_j) R_j.
+ * Two more live parameters, "attn_layer.0" [NB][NB] and "attn_layer.2" [1][NB] (state_dict names of the reference); the relation
+ * discriminators are still computed (region "Pr") but are live only with TA3N_FLAG_ADV_RELATION.  Regions: "Ua" [B][T-1][NB] (the first
+ * layer's output, tanh applied in place by the attention launch), "gUa" the gradient at that layer's output, "gs" [B][T-1] the gradient
+ * at the scores; "attn" holds w, "g_attn" takes the caller's gradient at it.  Unfused entry points only (ta3n_has_fused_step returns
+ * 0): the attention layer's first product rides in the launch of the relation discriminators' hidden layer, a general-attention launch
+ * stands in place of the pooling launch in the forward and in the backward, and the relation-level launch carries one more K segment
+ * per gR_j and the layer's two weight gradients.  fp32 and TA3N_FLAG_BF16_MFMA (with or without TA3N_FLAG_BF16_STORE);
+ * TA3N_FLAG_FEATURE_GRADS may be set.  ta3n_plan_create refuses it by name together with TA3N_FLAG_TRANS_ATTN or TA3N_FLAG_FRAME_ATTN,
+ * on TA3N_AGG_AVGPOOL, and with TA3N_FLAG_F32_SPLIT, _MCD, _BN_SHARED, shared_fc_layers > 1, chain, split_k, wgrads_late or
+ * phase_tiles. */
+#define TA3N_FLAG_GENERAL_ATTN   (1u << 15)
 
 /* ta3n_config.aggregation */
 #define TA3N_AGG_TRN_M    0   /* 'trn-m': multi-scale TRN - the TA3N path (TRNmodule.py:27-86) */

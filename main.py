@@ -229,6 +229,10 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
     attn_frame = getattr(args, "use_attn_frame", "none")
     if attn_frame != "none" and (attn_frame != "TransAttn" or args.use_attn != "TransAttn" or dis or mcd or args.use_bn != "none" or add_fc != 1):
         return None
+    # --use_attn general: the engine's unfused launch lists with the two general-attention launches (alone: general_attn_refusal)
+    attn_general = args.use_attn == "general"
+    if attn_general and (attn_frame != "none" or dis or mcd or args.use_bn != "none" or add_fc != 1):
+        return None
     # --weighted_class_loss / --weighted_class_loss_DA: the engine takes the weights the two criteria carry (:160-167, 205-206)
     class_w, domain_w = _criterion_weights(criterion, num_class), _criterion_weights(criterion_domain, 2)
     g = optimizer.param_groups[0]
@@ -247,9 +251,9 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
                           clip=args.clip_gradient if args.clip_gradient is not None else 0.0, device=next(m.parameters()).device,
                           use_bn=args.use_bn, **(dict(dis_DA=args.dis_DA, place_dis=tuple(args.place_dis)) if dis else {}),
                           **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc, class_weights=class_w, domain_weights=domain_w)
-        if not eng.fused and not (dis or mcd or attn_frame != "none"):
+        if not eng.fused and not (dis or mcd or attn_frame != "none" or attn_general):
             return None
-        if class_w is not None or domain_w is not None or sv or tent:      # said once: the weighted criteria / target labels / target entropy train on the engine
+        if class_w is not None or domain_w is not None or sv or tent or attn_general:      # said once: the weighted criteria / target labels / target entropy train on the engine
             print("[ta3n] " + eng.describe(), flush=True)
         m.__dict__.setdefault("_main_fast_engine", {})[key] = eng
     return eng

@@ -60,6 +60,8 @@ def engine_checkpoint(eng, model, epoch: int, arch: str, lr: float, best_prec1: 
     sd = {"module." + k: v.cpu() for k, v in eng.state_dict().items()}
     for k, v in model.state_dict().items():
         sd.setdefault("module." + k, v.detach().cpu())
+    if getattr(eng, "general_attn", False):      # --use_attn general: the reference's key order, attn_layer.* last (the engine keeps them inside its live prefix)
+        sd = {"module." + k: sd["module." + k] for k in model.state_dict()}
     names = [n for n, _ in model.named_parameters()]
     if getattr(eng, "optimizer", "SGD") == "Adam":      # torch.optim.Adam creates its state at a parameter's first update too
         opt = adam_optimizer_state_dict(names, eng.adam_views() if eng.adam_step_count > 0 else {}, eng.adam_step_count, lr, eng.betas,

@@ -93,6 +93,14 @@ int launch_frame_attn(const ta3n_plan *p, int kind, const Ptrs &ptrs, hipStream_
                                      : launch_frame_attn_bwd(p->geom, ptrs, o.gF1a, o.gFs, o.gPfT, stream);
 }
 
+// the two general-attention launches (TA3N_FLAG_GENERAL_ATTN), likewise
+int launch_general_attn(const ta3n_plan *p, int kind, const Ptrs &ptrs, hipStream_t stream) {
+    const ta3n_plan::GeneralAttn &o = p->general_attn;
+    if (o.Ua < 0 || o.gUa < 0 || o.gs < 0 || o.p_wa2 < 0 || o.p_ba2 < 0) return -1;
+    return kind == PH_GENERAL_ATTN_FWD ? launch_general_attn_fwd(p->geom, ptrs, o.Ua, o.p_wa2, o.p_ba2, stream)
+                                       : launch_general_attn_bwd(p->geom, ptrs, o.Ua, o.gUa, o.gs, o.p_wa2, stream);
+}
+
 int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float *momentum, hipStream_t stream,
               hipEvent_t join_after_first = nullptr, int first_launch = 0, int n_launches = 1 << 30,
               const SgdSide *side = nullptr) {
@@ -125,6 +133,7 @@ int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float
             case PH_BN_FWD: rc = launch_bn_shared_fwd(p->geom, ptrs, stream); break;
             case PH_BN_BWD: rc = launch_bn_shared_bwd(p->geom, ptrs, stream); break;
             case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: rc = launch_frame_attn(p, ph.kind, ptrs, stream); break;
+            case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: rc = launch_general_attn(p, ph.kind, ptrs, stream); break;
             case PH_GRAD_NORM: rc = launch_grad_norm(p->geom, ptrs.g, ptrs.ws, stream); break;
             case PH_SGD: rc = launch_sgd(p->geom, params_rw, ptrs.g, momentum, ptrs.ws, stream); break;
             default: rc = -1;
@@ -433,6 +442,7 @@ int ta3n_time_phases(ta3n_plan *p, const float *x, float *params, float *grads, 
                 case PH_BN_FWD: lrc = launch_bn_shared_fwd(p->geom, ptrs, s); break;
                 case PH_BN_BWD: lrc = launch_bn_shared_bwd(p->geom, ptrs, s); break;
                 case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: lrc = launch_frame_attn(p, ph.kind, ptrs, s); break;
+                case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: lrc = launch_general_attn(p, ph.kind, ptrs, s); break;
                 case PH_GRAD_NORM: lrc = launch_grad_norm(p->geom, grads, ws, s); break;
                 case PH_SGD: lrc = launch_sgd(p->geom, params, grads, momentum, ws, s); break;
                 default: lrc = -1;

@@ -281,6 +281,9 @@ int launch_loss(const Geom &g, const Ptrs &ptrs, hipStream_t stream);
 // TA3N_FLAG_FRAME_ATTN: ws offsets of regions "F1a", "attn_frame" / "gF1a", the additive base ("gF1s" or "gRa"), "gPfT"
 int launch_frame_attn_fwd(const Geom &g, const Ptrs &ptrs, int o_F1a, int o_attn_frame, hipStream_t stream);
 int launch_frame_attn_bwd(const Geom &g, const Ptrs &ptrs, int o_gF1a, int o_gFs, int o_gPfT, hipStream_t stream);
+// TA3N_FLAG_GENERAL_ATTN: ws offsets of regions "Ua" / "gUa", "gs"; parameter offsets of attn_layer.2.weight / .bias
+int launch_general_attn_fwd(const Geom &g, const Ptrs &ptrs, int o_Ua, int p_wa2, int p_ba2, hipStream_t stream);
+int launch_general_attn_bwd(const Geom &g, const Ptrs &ptrs, int o_Ua, int o_gUa, int o_gs, int p_wa2, hipStream_t stream);
 int launch_pool_bwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream);
 int launch_grad_norm(const Geom &g, const float *grads, float *ws, hipStream_t stream);
 int launch_sgd(const Geom &g, float *params, const float *grads, float *momentum, float *ws, hipStream_t stream,

@@ -13,6 +13,7 @@
 //   w = 1 - H(softmax Pr);  V = sum_j (1+w_j) R_j;  Vd = drop_v(V)   models.py:351-357, 379-388, 651, 679
 //   Y = Wcv Vd + bcv;  Pv = Wcdv relu(Wdv GRL(Vd) + bdv) + bcdv      models.py:686, 464-470
 //   TA3N_FLAG_FRAME_ATTN: wf = 1 - H(softmax Pf);  F1a = (1 + wf) F1 replaces F1 in Z_t             models.py:368-377, 612-614
+//   TA3N_FLAG_GENERAL_ATTN: w = softmax_j(<tanh(Wa1 R_j + ba1), wa2> + ba2) replaces w = 1 - H(softmax Pr)   models.py:320-325, 359-366
 #include "ta3n_plan_builder.h"
 
 #include <cstdlib>
@@ -572,10 +573,13 @@ struct TrnModel {
     // TA3N_FLAG_FRAME_ATTN (models.py:368-377, 612-614): the TRN reads F1a = (1 + wf) F1, wf from the frame discriminator's logits and not
     // detached - so that discriminator is live whatever place_adv[2] says, its logits come BEFORE the tuple products and its backward
     // AFTER the TRN input gradient (add_unfused_lists)
-    const bool frame_attn;
+    // TA3N_FLAG_GENERAL_ATTN (models.py:320-325, 359-366, 379-388): w = softmax over the relations of attn_layer(R_j), a learned layer
+    // (Wa1, ba1, wa2, ba2: always live) in place of the relation discriminators' entropy - those stay computed, and live only with their loss
+    const bool frame_attn, general_attn;
     const bool live_frm, live_vid, live_rel, mcd, feat_grads, bn_shared;
     const int ldZ, ldR, ldF;
     int64_t o_F1a = -1, o_gF1a = -1, o_gFs = -1, o_gPfT = -1;   // frame attention: attended features, TRN input gradient, (1 + wf) gF1a, gPf + attention term
+    int64_t o_Ua = -1, o_gUa = -1, o_gs = -1, Wa1 = -1, ba1 = -1, wa2 = -1, ba2 = -1;   // general attention: U / A = tanh(U), gradient at U, gradient at the scores; attn_layer.0 / .2
     HeadParams w;
     std::vector<int64_t> trnW, trnB, W1, B1, W2, B2;   // per scale j
     SharedStack st;
@@ -584,6 +588,7 @@ struct TrnModel {
 
     TrnModel(ta3n_plan &pl, const Dims &dm)
         : p(pl), b(pl), g(pl.geom), c(pl.cfg), d(dm), NR(dm.T - 1), NT(pl.n_tuples), frame_attn(c.flags & TA3N_FLAG_FRAME_ATTN),
+          general_attn(c.flags & TA3N_FLAG_GENERAL_ATTN),
           live_frm(c.flags & (TA3N_FLAG_ADV_FRAME | TA3N_FLAG_FRAME_ATTN)),
           live_vid(c.flags & TA3N_FLAG_ADV_VIDEO), live_rel(c.flags & (TA3N_FLAG_ADV_RELATION | TA3N_FLAG_TRANS_ATTN)), mcd(c.flags & TA3N_FLAG_MCD),
           feat_grads(c.flags & TA3N_FLAG_FEATURE_GRADS), bn_shared(c.flags & TA3N_FLAG_BN_SHARED), ldZ(NT * dm.NB), ldR(NR * dm.NB), ldF(dm.T * dm.F) {}
@@ -594,6 +599,7 @@ struct TrnModel {
     bool lay_out_workspace(std::string &err);
     void add_unfused_lists();
     void add_frame_attn_lists();
+    void add_general_attn_lists();
     int64_t trn_input() const { return frame_attn ? o_F1a : g.o_F1; }   // what the tuple products and the TRN weight gradients read
     bool add_fused_step(std::string &err);
     void forward_levels(int group, const std::vector<Task> *side, std::string &cerr);
@@ -615,6 +621,7 @@ struct TrnModel {
     }
     GemmSpec spec_Z(int t) const;
     GemmSpec spec_Hr(int j) const;
+    GemmSpec spec_Ua(int j) const;
     GemmSpec spec_gR(int j) const;
     void push_video_head_wgrads(std::vector<GemmSpec> &s) const {   // dWcdv, dbcdv, dWcv, dbcv
         s.push_back(wgrad(2, d.NB, d.B, g.o_gPv, 2, g.o_Hv, d.NB, w.Wcdv, w.bcdv));
@@ -629,6 +636,10 @@ struct TrnModel {
             s.push_back(spec_gR(j));
             s.push_back(wgrad(NB, NB, d.B, g.o_gHr + (int64_t)j * NB, ldR, g.o_R + (int64_t)j * NB, ldR, W1[j], B1[j]));
             s.push_back(wgrad(2, NB, d.B, g.o_gPrT + (int64_t)j * 2, NR * 2, g.o_Hr + (int64_t)j * NB, ldR, W2[j], B2[j]));
+        }
+        if (general_attn) {   // the attention layer, rows flat over (b, j): dWa1 = gUa^T R, dba1; dwa2 = gs^T A, dba2 = sum gs
+            s.push_back(wgrad(NB, NB, d.B * NR, o_gUa, NB, g.o_R, NB, Wa1, ba1));
+            s.push_back(wgrad(1, NB, d.B * NR, o_gs, 1, o_Ua, NB, wa2, ba2));
         }
     }
     void push_trn_wgrads(std::vector<GemmSpec> &s, unsigned scale_mask = ~0u) const;
@@ -663,13 +674,27 @@ GemmSpec TrnModel::spec_Hr(int j) const {   // relation-discriminator hidden lay
     return h;
 }
 
+// relation-attention layer's first product on R_j = sum_t Z_t: U_j = Wa1 R_j + ba1 (models.py:321-322, 362), the K segments of spec_Hr(j)
+GemmSpec TrnModel::spec_Ua(int j) const {
+    const int NB = d.NB;
+    GemmSpec u;
+    u.M = d.B; u.N = NB;
+    for (int t = p.tuple_first[j]; t < p.tuple_first[j + 1]; ++t)
+        u.segs.push_back(mkseg(KC(BASE_WS, g.o_Zr + (int64_t)t * NB, ldZ), KC(BASE_P, Wa1, NB), NB));
+    u.proto = proto(BASE_WS, o_Ua + (int64_t)j * NB, ldR);
+    with_bias(u.proto, ba1);
+    return u;
+}
+
 GemmSpec TrnModel::spec_gR(int j) const {   // gR_j = gRa_j - beta0 * gHr_j W1_j, fanned out through the TRN ReLU masks
     const int NB = d.NB;
     GemmSpec gr;
     gr.M = d.B; gr.N = NB;
-    gr.segs.push_back(mkseg(KC(BASE_WS, g.o_gHr + (int64_t)j * NB, ldR), KM(BASE_P, W1[j], NB), NB));
+    // (general attention: + gUa_j Wa1, a second K segment behind the scaled one - the scale then sits on the first Seg, as in push_f1_grad)
+    gr.segs.push_back(mkseg(KC(BASE_WS, g.o_gHr + (int64_t)j * NB, ldR), KM(BASE_P, W1[j], NB), NB, general_attn ? SK_NEG_BETA_REL : SK_ONE));
+    if (general_attn) gr.segs.push_back(mkseg(KC(BASE_WS, o_gUa + (int64_t)j * NB, ldR), KM(BASE_P, Wa1, NB), NB));
     gr.proto = proto(BASE_WS, g.o_gR + (int64_t)j * NB, ldR);
-    gr.proto.alpha_kind = SK_NEG_BETA_REL;
+    gr.proto.alpha_kind = general_attn ? SK_ONE : SK_NEG_BETA_REL;
     with_add(gr.proto, g.o_gRa + (int64_t)j * NB, ldR);
     const int nt = p.tuple_first[j + 1] - p.tuple_first[j];
     gr.proto.fan_count = nt; gr.proto.fan_ld = ldZ;
@@ -759,6 +784,10 @@ void TrnModel::add_params() {
     if (bn_shared) add_bn_shared_params(b, F);
     if (mcd) b.add_linear("fc_classifier_video_source_2", C, NB, true);  // :276-279 (ens_DA MCD)
     b.lin("fc_classifier_domain_video", 2, NB, live_vid);                // :281
+    if (general_attn) {                                                  // :320-325 (last in the reference's state_dict; here: inside the live prefix)
+        b.add_linear("attn_layer.0", NB, NB, true);
+        b.add_linear("attn_layer.2", 1, NB, true);
+    }
     p.live_floats = p.param_floats;
     b.add_dead_linears();                                                // computed (zero or unused) gradients land past the live prefix
     // never receive a gradient in this configuration: kept for state_dict compatibility
@@ -775,6 +804,10 @@ void TrnModel::add_params() {
         trnW.push_back(p.poff(trn + ".weight")); trnB.push_back(p.poff(trn + ".bias"));
         W1.push_back(p.poff(rel + ".0.weight")); B1.push_back(p.poff(rel + ".0.bias"));
         W2.push_back(p.poff(rel + ".2.weight")); B2.push_back(p.poff(rel + ".2.bias"));
+    }
+    if (general_attn) {
+        Wa1 = p.poff("attn_layer.0.weight"); ba1 = p.poff("attn_layer.0.bias");
+        wa2 = p.poff("attn_layer.2.weight"); ba2 = p.poff("attn_layer.2.bias");
     }
 }
 
@@ -823,6 +856,12 @@ bool TrnModel::lay_out_workspace(std::string &err) {
         o_gFs = (int64_t)B * NR * NB >= (int64_t)BT * F ? (int64_t)g.o_gRa : b.add_region("gF1s", (int64_t)BT * F);
         p.frame_attn = {(int32_t)o_F1a, (int32_t)o_attn, (int32_t)o_gF1a, (int32_t)o_gFs, (int32_t)o_gPfT};
     }
+    if (general_attn) {
+        o_Ua = b.add_region("Ua", (int64_t)B * NR * NB);      // U from the GEMM launch, A = tanh(U) in place from the attention launch
+        o_gUa = b.add_region("gUa", (int64_t)B * NR * NB);
+        o_gs = b.add_region("gs", (int64_t)B * NR);
+        p.general_attn = {(int32_t)o_Ua, (int32_t)o_gUa, (int32_t)o_gs, (int32_t)wa2, (int32_t)ba2};
+    }
 #ifdef TA3N_GEMM_STAMPS
     b.add_region("stamps", 8192 * 16 * 2);            // (debug build: per-workgroup cycle stamps of the GEMM launches, directly in front of "zeros")
 #endif
@@ -860,6 +899,7 @@ bool TrnModel::lay_out_workspace(std::string &err) {
 void TrnModel::add_unfused_lists() {
     const int BT = d.BT, F = d.F;
     if (frame_attn) { add_frame_attn_lists(); return; }
+    if (general_attn) { add_general_attn_lists(); return; }
     b.add_gemm_phase(0, spec_F1());
     if (bn_shared) b.add_simple_phase(PH_BN_FWD, 0);
     add_stack_forward(b, st, 0, BT, F);
@@ -923,6 +963,34 @@ void TrnModel::add_frame_attn_lists() {
     b.add_simple_phase(PH_FRAME_ATTN_BWD, 2);   // gPfT, (1 + wf) gF1a
     { std::vector<GemmSpec> s{spec_gHf(), spec_dWcd()}; b.add_gemm_phase(2, s); }
     { std::vector<GemmSpec> s; push_frame_disc_wgrads(s); s.push_back(spec_gZ1_behind_frame_attn()); b.add_gemm_phase(2, s); }
+    { std::vector<GemmSpec> s; push_shared_fc_wgrad(s); b.add_gemm_phase(2, s); }
+    b.add_simple_phase(PH_GRAD_NORM, 3);
+    b.add_simple_phase(PH_SGD, 3);
+}
+
+// TA3N_FLAG_GENERAL_ATTN: the plain lists (add_fc 1, no BatchNorm, no MCD: general_attn_refusal) in their order, with U_j = Wa1 R_j + ba1
+// riding in the launch of Hr_j and Pf, the general-attention launches in place of the two pooling launches, and the relation-level
+// launch carrying gUa_j Wa1 in gR_j and the attention layer's two weight gradients (push_relation_level).  No launch more than the
+// plain lists have.
+void TrnModel::add_general_attn_lists() {
+    b.add_gemm_phase(0, spec_F1());
+    { std::vector<GemmSpec> s{spec_Hf()}; for (int t = 0; t < NT; ++t) s.push_back(spec_Z(t)); b.add_gemm_phase(0, s); }
+    {
+        std::vector<GemmSpec> s;
+        for (int j = 0; j < NR; ++j) s.push_back(spec_Hr(j));
+        s.push_back(spec_Pf());
+        for (int j = 0; j < NR; ++j) s.push_back(spec_Ua(j));
+        b.add_gemm_phase(0, s);
+    }
+    b.add_simple_phase(PH_GENERAL_ATTN_FWD, 0);   // Pr, R, A, attention weights, V, Vd
+    { std::vector<GemmSpec> s{spec_Y(), spec_Hv()}; b.add_gemm_phase(0, s); }
+    b.add_gemm_phase(0, spec_Pv());
+    b.add_simple_phase(PH_LOSS, 1);
+    { std::vector<GemmSpec> s{spec_gHv(), spec_gHf()}; push_video_head_wgrads(s); s.push_back(spec_dWcd()); b.add_gemm_phase(2, s); }
+    { std::vector<GemmSpec> s{spec_gVt(g, d.NB, w, true, false)}; push_video_disc_wgrads(s); push_frame_disc_wgrads(s); b.add_gemm_phase(2, s); }
+    b.add_simple_phase(PH_GENERAL_ATTN_BWD, 2);   // gs, gUa, gRa = (1 + w) gv, gPrT = gPr, gHr
+    { std::vector<GemmSpec> s; push_relation_level(s); b.add_gemm_phase(2, s); }
+    { std::vector<GemmSpec> s; push_trn_wgrads(s); push_f1_grad(s); b.add_gemm_phase(2, s); }
     { std::vector<GemmSpec> s; push_shared_fc_wgrad(s); b.add_gemm_phase(2, s); }
     b.add_simple_phase(PH_GRAD_NORM, 3);
     b.add_simple_phase(PH_SGD, 3);
@@ -1078,6 +1146,27 @@ std::string frame_attn_refusal(const ta3n_config &c) {
     return with ? what + " with " + with + " is not built" : "";
 }
 
+// "" when the configuration's general attention is built, otherwise the refusal (naming the combination)
+std::string general_attn_refusal(const ta3n_config &c) {
+    if (!(c.flags & TA3N_FLAG_GENERAL_ATTN)) return "";
+    const std::string what = "use_attn general (TA3N_FLAG_GENERAL_ATTN)";
+    if (c.aggregation != TA3N_AGG_TRN_M) return what + " on avgpool is not built: the reference's aggregate_frames ignores use_attn there";
+    const char *with = nullptr;
+    if (c.flags & TA3N_FLAG_TRANS_ATTN) with = "use_attn TransAttn (TA3N_FLAG_TRANS_ATTN): two values of one option";
+    else if (c.flags & TA3N_FLAG_FRAME_ATTN) with = "use_attn_frame (TA3N_FLAG_FRAME_ATTN): the reference sends 'general' frame attention to a 256-wide layer on fc_dim-wide rows";
+    else if (c.flags & TA3N_FLAG_F32_SPLIT) with = "TA3N_FLAG_F32_SPLIT";
+    else if (c.flags & TA3N_FLAG_MCD) with = "ens_DA MCD (TA3N_FLAG_MCD)";
+    else if (c.flags & TA3N_FLAG_BN_SHARED) with = "use_bn (TA3N_FLAG_BN_SHARED)";
+    else if (c.shared_fc_layers > 1) with = "shared_fc_layers (--add_fc) > 1";
+    else if (c.chain) with = "chain";
+    else if (c.split_k) with = "split_k";
+    else if (c.wgrads_late) with = "wgrads_late";
+    else
+        for (int i = 0; i < 16; ++i)
+            if (c.phase_tiles[i]) with = "phase_tiles (indexed by the plain launch order)";
+    return with ? what + " with " + with + " is not built" : "";
+}
+
 int build_plan_trn(ta3n_plan &p, std::string &err) {
     const Dims d = dims_of(p.cfg);
     if (const char *e = bn_shared_refusal(p.cfg, d)) { err = e; return TA3N_ERR_INVALID; }
@@ -1103,6 +1192,10 @@ int build_plan_trn(ta3n_plan &p, std::string &err) {
         // frame attention: the unfused lists only (the fused heads kernel computes Pf behind the tuple products); the frame-attention
         // launch keeps the twin of F1a, which the tuple products and the TRN weight gradients read
         add_bf16_twins(p, m.b, m.g, d.BT, d.D, {}, {}, {Span{m.o_F1a, m.o_F1a + (int64_t)d.BT * d.F}});
+    } else if (m.general_attn) {
+        // general attention: the unfused lists only (the fused heads kernel computes the entropy attention); its two launches keep no twin -
+        // what they write (R, A, gUa, gRa, gHr, gs) is read by the relation-level launch, which reads no twins in the plain lists either
+        add_bf16_twins(p, m.b, m.g, d.BT, d.D, {}, {});
     } else if (heads_supported(d.NB, d.C, d.F) && !m.mcd && !m.feat_grads && !(m.bn_shared && p.cfg.chain != 0)) {
         if (!m.add_fused_step(err)) return TA3N_ERR_INVALID;
     } else {
@@ -1165,6 +1258,7 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     if (c.xcd_aware < 0 || c.xcd_aware > 3) { err = "xcd_aware must be 0, 1, 2 or 3"; return TA3N_ERR_INVALID; }
     if ((int64_t)d.BT * d.D >= (1ll << 31) || (int64_t)d.BT * d.F >= (1ll << 31)) { err = "problem too large for 32-bit offsets"; return TA3N_ERR_INVALID; }
     { const std::string e = shared_layers_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
+    { const std::string e = general_attn_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     { const std::string e = frame_attn_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     if (c.aggregation == TA3N_AGG_TRN_M) return build_plan_trn(p, err);
     p.n_tuples = 0;      // (no relation tuples)

@@ -11,6 +11,8 @@
 //  frame_attn_fwd / _bwd   TA3N_FLAG_FRAME_ATTN: one wavefront per frame row, F1a = (1 + w) F1 with
 //             w = 1 - H(softmax(frame-discriminator logits)) in front of the TRN (models.py:368-377,
 //             612-614) and the way back, the weights not detached.
+//  general_attn_fwd / _bwd   TA3N_FLAG_GENERAL_ATTN: pool_fwd / pool_bwd with w = softmax over the relations of a learned
+//             layer's scores (models.py:320-325, 359-366) in place of the entropy weights.
 //  grad_norm / sgd   clip_grad_norm_ + Nesterov SGD with weight decay over the
 //             flat live-parameter prefix (main.py:578-583).
 #include <hip/hip_runtime.h>
@@ -123,6 +125,133 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(Geom g, Ptrs ptrs) {
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             const int c = q * 64 + lane;
+            ws[g.o_gRa + bj * NB + c] = w1 * gv[q];
+            ws[g.o_gHr + bj * NB + c] = relu_back2(ws[g.o_Hr + bj * NB + c], g0, W2[c], g1, W2[NB + c]);
+        }
+    }
+}
+
+// ---- TA3N_FLAG_GENERAL_ATTN (use_attn general, models.py:320-325, 359-366, 379-388) ----
+// The pooling launches with a learned attention layer in place of the relation discriminators' entropy.  One wavefront per video, four
+// per workgroup, Q = NB / 64 channels per lane, as pool_fwd_kernel / pool_bwd_kernel.  The T - 1 <= 63 scores of a video live in its
+// wave's lanes (lane j holds relation j): the first loop over the relations forms them - every dot product by wave_allreduce_sum, a
+// fixed order, no atomics - the softmax runs over the lanes (lane_log_softmax, e / sum as torch's softmax), and the second loop reads
+// lane j's weight back.  Region "Ua" arrives holding U_j = Wa1 R_j + ba1 from the GEMM launch in front and leaves holding A_j = tanh(U_j).
+// The region offsets the Geom has no field for arrive as kernel arguments (ta3n_plan::general_attn).
+__device__ __forceinline__ float lane_value(float v, int j) {   // lane j's v in every lane (j wave-uniform)
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void general_attn_fwd_kernel(Geom g, Ptrs ptrs, int o_Ua, int p_wa2, int p_ba2) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    float *__restrict__ ws = ptrs.ws;
+    if (blockIdx.x == 0 && threadIdx.x < 8) ws[g.o_losses + threadIdx.x] = 0.f;   // as pool_fwd_kernel: this launch stands between two loss launches
+    if (b >= g.B) return;
+    const Hyper *__restrict__ hy = reinterpret_cast<const Hyper *>(ws + g.o_hyper);
+    const int *__restrict__ tf = reinterpret_cast<const int *>(ws + g.o_tuple_first);
+    const int NB = g.NB, NR = g.n_rel, NT = g.n_tuples;
+    const float *__restrict__ wa2 = ptrs.p + p_wa2;
+    const float ba2 = ptrs.p[p_ba2];
+    float score = 0.f;
+    for (int j = 0; j < NR; ++j) {
+        const size_t bj = (size_t)b * NR + j;
+        const float *__restrict__ W2 = ptrs.p + g.p_W2_0 + (size_t)j * g.p_W2_stride;
+        const float *__restrict__ b2 = ptrs.p + g.p_b2_0 + (size_t)j * g.p_b2_stride;
+        const float *__restrict__ hr = ws + g.o_Hr + bj * NB;
+        float d0 = 0.f, d1 = 0.f, sj = 0.f;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int c = q * 64 + lane;
+            const float h = hr[c];
+            d0 = fmaf(h, W2[c], d0);
+            d1 = fmaf(h, W2[NB + c], d1);
+            float r = 0.f;
+            for (int t = tf[j]; t < tf[j + 1]; ++t) r += ws[g.o_Zr + ((size_t)b * NT + t) * NB + c];
+            ws[g.o_R + bj * NB + c] = r;
+            const float a = tanhf(ws[o_Ua + bj * NB + c]);
+            ws[o_Ua + bj * NB + c] = a;
+            sj = fmaf(a, wa2[c], sj);
+        }
+        d0 = wave_allreduce_sum(d0) + b2[0];      // the relation discriminator's logits: returned, and in the loss with place_adv[0] Y
+        d1 = wave_allreduce_sum(d1) + b2[1];
+        sj = wave_allreduce_sum(sj) + ba2;
+        if (lane == 0) {
+            ws[g.o_Pr + bj * 2 + 0] = d0;
+            ws[g.o_Pr + bj * 2 + 1] = d1;
+        }
+        if (lane == j) score = sj;
+    }
+    const LaneSoft sm = lane_log_softmax(score, lane < NR);
+    const float w = sm.e / sm.sum;      // (one relation: e = exp(0) = 1 = sum, w = 1 exactly)
+    if (lane < NR) ws[g.o_attn + (size_t)b * NR + lane] = w;
+    float vacc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) vacc[q] = 0.f;
+    for (int j = 0; j < NR; ++j) {
+        const float wj = lane_value(w, j);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) vacc[q] += (wj + 1.f) * ws[g.o_R + ((size_t)b * NR + j) * NB + q * 64 + lane];   // (this lane's own store above)
+    }
+    const float inv_keep = hyper_scale(hy, SK_INV_KEEP_V);
+    const bool drop = hy->train != 0 && hy->p_drop_v > 0.f;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int c = q * 64 + lane;
+        const float v = vacc[q];
+        ws[g.o_V + (size_t)b * NB + c] = v;
+        float vd = v;
+        if (drop) vd = v * keep_mask(hy->seed_v, (uint32_t)(b * NB + c), hy->p_drop_v) * inv_keep;      // pool_fwd_kernel's stream: same hash, same index
+        ws[g.o_Vd + (size_t)b * NB + c] = vd;
+    }
+}
+
+// gv = gVt (+ gV_ext): d_j = <R_j, gv> + g_attn[b, j] is the gradient at w_j, gs_j = w_j (d_j - sum_k w_k d_k) the gradient at the score,
+// gUa_j = gs_j wa2 (1 - A_j^2) the gradient at U_j (on to R_j, Wa1 and ba1 in the relation-level launch), gRa_j = (1 + w_j) gv.  The relation
+// discriminators get their loss gradient alone: gPrT = gPr, gHr from it.  Padded videos carry no guard: the kernel is linear in gv and
+// g_attn, and loss_kernel zeroes every logit gradient of a padded video (module path: the caller's, as for frame_attn_bwd_kernel).
+template <int Q>
+__global__ __launch_bounds__(256) void general_attn_bwd_kernel(Geom g, Ptrs ptrs, int o_Ua, int o_gUa, int o_gs, int p_wa2) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= g.B) return;
+    float *__restrict__ ws = ptrs.ws;
+    const int NB = g.NB, NR = g.n_rel;
+    const float *__restrict__ wa2 = ptrs.p + p_wa2;
+    float gv[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) gv[q] = ws[g.o_gVt + (size_t)b * NB + q * 64 + lane];
+    if (g.o_gV_ext > 0) {   // TA3N_FLAG_FEATURE_GRADS: the caller's gradient at the pooled feature
+#pragma unroll
+        for (int q = 0; q < Q; ++q) gv[q] += ws[g.o_gV_ext + (size_t)b * NB + q * 64 + lane];
+    }
+    float d = 0.f;
+    for (int j = 0; j < NR; ++j) {
+        const size_t bj = (size_t)b * NR + j;
+        float dot = 0.f;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) dot = fmaf(ws[g.o_R + bj * NB + q * 64 + lane], gv[q], dot);
+        dot = wave_allreduce_sum(dot) + ws[g.o_gattn + bj];
+        if (lane == j) d = dot;
+    }
+    const float w = lane < NR ? ws[g.o_attn + (size_t)b * NR + lane] : 0.f;
+    const float gs = w * (d - wave_allreduce_sum(w * d));      // softmax backward over the lanes (lanes past NR: w = d = 0)
+    if (lane < NR) ws[o_gs + (size_t)b * NR + lane] = gs;
+    for (int j = 0; j < NR; ++j) {
+        const size_t bj = (size_t)b * NR + j;
+        const float *__restrict__ W2 = ptrs.p + g.p_W2_0 + (size_t)j * g.p_W2_stride;
+        const float g0 = ws[g.o_gPr + bj * 2 + 0], g1 = ws[g.o_gPr + bj * 2 + 1];
+        const float gsj = lane_value(gs, j), w1 = lane_value(w, j) + 1.f;
+        if (lane == 0) {
+            ws[g.o_gPrT + bj * 2 + 0] = g0;
+            ws[g.o_gPrT + bj * 2 + 1] = g1;
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int c = q * 64 + lane;
+            const float a = ws[o_Ua + bj * NB + c];
+            ws[o_gUa + bj * NB + c] = gsj * wa2[c] * (1.f - a * a);
             ws[g.o_gRa + bj * NB + c] = w1 * gv[q];
             ws[g.o_gHr + bj * NB + c] = relu_back2(ws[g.o_Hr + bj * NB + c], g0, W2[c], g1, W2[NB + c]);
         }
@@ -796,6 +925,20 @@ int launch_pool_fwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
 int launch_pool_bwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream) {
     const dim3 grid((g.B + 3) / 4);
     TA3N_DISPATCH_Q(pool_bwd_kernel, grid, stream, g, ptrs)
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_general_attn_fwd(const Geom &g, const Ptrs &ptrs, int o_Ua, int p_wa2, int p_ba2, hipStream_t stream) {
+    if (g.n_rel < 1 || g.n_rel > 63) return -1;      // the scores of a video live in the lanes of one wave
+    const dim3 grid((g.B + 3) / 4);
+    TA3N_DISPATCH_Q(general_attn_fwd_kernel, grid, stream, g, ptrs, o_Ua, p_wa2, p_ba2)
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_general_attn_bwd(const Geom &g, const Ptrs &ptrs, int o_Ua, int o_gUa, int o_gs, int p_wa2, hipStream_t stream) {
+    if (g.n_rel < 1 || g.n_rel > 63) return -1;
+    const dim3 grid((g.B + 3) / 4);
+    TA3N_DISPATCH_Q(general_attn_bwd_kernel, grid, stream, g, ptrs, o_Ua, o_gUa, o_gs, p_wa2)
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -105,6 +105,8 @@ enum PhaseKind : int32_t {
     PH_BN_BWD = 11,          // ... and back: gZ0, d(bn weight), d(bn bias) from gZ1
     PH_FRAME_ATTN_FWD = 12,  // TA3N_FLAG_FRAME_ATTN: attn_frame = 1 - H(softmax(Pf)), F1a = (1 + attn_frame) F1
     PH_FRAME_ATTN_BWD = 13,  // ... and back: gPfT = gPf + <gF1a, F1> dw/dPf, additive base of the gradient at F1 = (1 + attn_frame) gF1a
+    PH_GENERAL_ATTN_FWD = 14,  // TA3N_FLAG_GENERAL_ATTN, in place of PH_POOL_FWD: Pr, R, A = tanh(U), attn = softmax_j(<A_j, wa2> + ba2), V, Vd
+    PH_GENERAL_ATTN_BWD = 15,  // ... in place of PH_POOL_BWD: gs, gUa = gs wa2 (1 - A^2), gRa = (1 + attn) gv, gPrT = gPr, gHr
 };
 
 // work split of the fused heads kernel (ta3n_heads.hip); the plan builder sizes its partial-sum regions from these

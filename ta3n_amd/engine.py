@@ -40,6 +40,8 @@ def flags_from_options(place_adv: Sequence[str] = ("Y", "Y", "Y"), add_loss_DA: 
         f |= _lib.FLAG_ATTN_ENTROPY
     if use_attn == "TransAttn":
         f |= _lib.FLAG_TRANS_ATTN
+    if use_attn == "general":              # models.py:320-325, 359-366 (with which other options it is built: general_attn_refusal)
+        f |= _lib.FLAG_GENERAL_ATTN
     if use_attn_frame not in ("none", "TransAttn"):      # the bit means TransAttn; no other kind may turn into it silently
         raise ValueError(frame_attn_refusal(use_attn_frame))
     if use_attn_frame == "TransAttn":      # (with which other options it is built: frame_attn_refusal)
@@ -137,6 +139,28 @@ def _rank_schedules(world: int, process_group: bool, ddp_selftest: bool, sharded
                             ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest),
                             ("the sharded update (sharded_update / TA3N_DDP_SHARDED)", sharded_update),
                             ("the peer gradient exchange (peer_exchange / TA3N_DDP_PEER)", peer_exchange)) if on]
+
+
+def general_attn_refusal(use_attn: str = "general", frame_aggregation: str = "trn-m", use_attn_frame: str = "none", add_fc: int = 1,
+                         use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", f32_split: bool = False, chain: bool = False,
+                         split_k: int = 0, wgrads_late: bool = False, phase_tiles: bool = False, world: int = 1, process_group: bool = False,
+                         ddp_selftest: bool = False, sharded_update: bool = False, peer_exchange: bool = False) -> str:
+    """'' when --use_attn `use_attn` is not 'general' or is built together with the other options, otherwise the message that refuses it
+    (naming the combination).  Built: conventional attention over the relation features of trn-m (models.py:320-325, 359-366, 379-388),
+    fp32 and bf16, SGD and Adam, on one rank: the unfused launch lists with two attention launches in place of the pooling launches."""
+    if use_attn != "general":
+        return ""
+    if frame_aggregation != "trn-m":
+        return (f"--use_attn general on --frame_aggregation {frame_aggregation}: built for trn-m (the reference's aggregate_frames ignores "
+                f"use_attn on avgpool)")
+    other = [what for what, on in ((f"--use_attn_frame {use_attn_frame} (the reference sends 'general' frame attention to a 256-wide layer on "
+                                    f"fc_dim-wide rows)", use_attn_frame != "none"),
+                                   (f"--add_fc {add_fc}", add_fc != 1), (f"--use_bn {use_bn}", use_bn != "none"),
+                                   (f"--dis_DA {dis_DA}", dis_DA != "none"), (f"--ens_DA {ens_DA}", ens_DA != "none"),
+                                   ("f32_split", f32_split), ("chained launches (chain)", chain), ("split_k", bool(split_k)),
+                                   ("wgrads_late", wgrads_late), ("explicit phase_tiles / tuned tile lists", phase_tiles)) if on]
+    other += _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
+    return f"--use_attn general together with {', '.join(other)} is not built (single rank, the unfused launch lists)" if other else ""
 
 
 def adam_refusal(world: int = 1, sharded_update: bool = False, process_group: bool = False, ddp_selftest: bool = False,
@@ -386,6 +410,20 @@ class TrainEngine:
             flags = ALL_FLAGS if aggregation == "trn-m" else 0
         if self.class_weights is not None:
             flags |= _lib.FLAG_CLASS_WEIGHTS
+        # use_attn general (TA3N_FLAG_GENERAL_ATTN in `flags`, flags_from_options(use_attn="general"); models.py:320-325, 359-366): the relation
+        # weights are the softmax over the relations of a learned layer's scores (parameters attn_layer.0 / attn_layer.2, always live).  The
+        # unfused launch lists with a general-attention launch in place of each pooling launch; single rank.
+        self.general_attn = bool(flags & _lib.FLAG_GENERAL_ATTN)
+        if self.general_attn:
+            if flags & _lib.FLAG_TRANS_ATTN:
+                raise NotImplementedError("--use_attn general together with --use_attn TransAttn (TA3N_FLAG_TRANS_ATTN): two values of one option")
+            refuse(general_attn_refusal, frame_aggregation=aggregation, use_attn_frame="TransAttn" if flags & _lib.FLAG_FRAME_ATTN else "none",
+                   add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA, f32_split=bool(f32_split), chain=sw.chain_arg,
+                   split_k=sw.split_k, wgrads_late=bool(wgrads_late),
+                   phase_tiles=bool(phase_tiles and any(phase_tiles)) or bool(sw.phase_tiles_env),
+                   process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
+                   peer_exchange=sw.peer_exchange)
+            fused = False
         # use_attn_frame TransAttn (TA3N_FLAG_FRAME_ATTN in `flags`, flags_from_options(use_attn_frame=...); models.py:368-377, 612-614): the
         # frame features enter the TRN scaled by 1 + (1 - H(frame-discriminator softmax)).  The frame discriminator's logits come before the
         # tuple products and its backward behind the TRN input gradient: the unfused launch lists with two more pointwise launches.
@@ -455,7 +493,7 @@ class TrainEngine:
 
     def _create_plan(self, sw: "_Switches", flags: int, fused: bool, *, fc_dim, tile_config, phase_tiles, xcd_aware, wgrads_late) -> None:
         """self.plan (and self.chain, self._flags) for the checked options: the launch-shape choices, then the plan builder."""
-        plain = self.aggregation == "trn-m" and self.add_fc == 1 and not self.frame_attn
+        plain = self.aggregation == "trn-m" and self.add_fc == 1 and not self.frame_attn and not self.general_attn
         if phase_tiles is None and tile_config == 0 and plain:      # measured choices for the benchmarked shapes (indexed by the plain launch order)
             from .tuning import tuned_phase_tiles
             phase_tiles = tuned_phase_tiles(self.B, self.T, self.D, self.F, self.bf16, self.bf16_store, split=bool(flags & _lib.FLAG_F32_SPLIT))
@@ -617,6 +655,7 @@ class TrainEngine:
                 f"{', class weights' if self.class_weights is not None else ''}"
                 f"{', target labels (use_target Sv)' if self.target_labels else ''}"
                 f"{', target entropy' if self.target_entropy else ''}"
+                f"{', general attention (use_attn general)' if self.general_attn else ''}"
                 f"{', domain weights ({:.3g}, {:.3g})'.format(*self.domain_weights) if self.domain_weights is not None else ''}: {step}")
 
     # ---- plumbing ----

@@ -216,7 +216,7 @@ class _HipForward(torch.autograd.Function):
             unused += ["fc_feature_domain.", "fc_classifier_domain."]
         if g_pv is None:
             unused += ["fc_feature_domain_video.", "fc_classifier_domain_video."]
-        if g_pr is None and not model._attn_on:      # with TransAttn the weights are not detached (models.py:351-357): the relation
+        if g_pr is None and (model._general_on or not model._attn_on):      # with TransAttn the weights are not detached (models.py:351-357): the relation
             unused += ["relation_domain_classifier_all."]      # discriminators receive a gradient through V whatever the loss uses
         _deliver_grads(model, plan, grads, fresh, tuple(unused), ctx.needs_input_grad[6:])
         return (None,) * (6 + ctx.n_params)
@@ -311,8 +311,13 @@ class VideoModel(nn.Module):
         if use_bn != 'none' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("use_bn with this frame_aggregation")
         if ens_DA not in ('none', 'MCD'): unsupported.append(f"ens_DA={ens_DA!r}")
         if ens_DA == 'MCD' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("ens_DA='MCD' with this frame_aggregation")
-        if use_attn not in ('TransAttn', 'none'): unsupported.append(f"use_attn={use_attn!r}")
-        if use_attn_frame != 'none':      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
+        if use_attn not in ('TransAttn', 'none', 'general'): unsupported.append(f"use_attn={use_attn!r}")
+        if use_attn == 'general':         # models.py:320-325, 359-366: conventional attention over the relation features of trn-m
+            from .engine import general_attn_refusal
+            refused = general_attn_refusal(use_attn, frame_aggregation=frame_aggregation, use_attn_frame=use_attn_frame, add_fc=add_fc,
+                                           use_bn=use_bn, ens_DA=ens_DA)
+            if refused: unsupported.append(f"use_attn='general' ({refused})")
+        if use_attn_frame != 'none' and use_attn != 'general':      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
             from .engine import frame_attn_refusal
             refused = frame_attn_refusal(use_attn_frame, use_attn=use_attn, frame_aggregation=frame_aggregation, add_fc=add_fc, use_bn=use_bn,
                                          ens_DA=ens_DA)
@@ -340,7 +345,8 @@ class VideoModel(nn.Module):
         self.use_attn, self.n_attn, self.use_attn_frame = use_attn, n_attn, use_attn_frame
         self.new_length = (1 if modality == "RGB" else 5) if new_length is None else new_length
         self.num_class = num_class
-        self._attn_on = use_attn == 'TransAttn'
+        self._attn_on = use_attn in ('TransAttn', 'general')      # the attention output takes a gradient
+        self._general_on = use_attn == 'general'                 # ... from a learned layer, not from the relation discriminators
         self._attn_frame_on = use_attn_frame == 'TransAttn'
         self._avg = frame_aggregation == 'avgpool'
         if verbose:
@@ -399,6 +405,8 @@ class VideoModel(nn.Module):
         self.alpha = torch.ones(1)                                       # :314 plain attribute
         if use_bn == 'AutoDIAL':                                         # :315-316; read with .item() in forward: it never gets a gradient
             self.alpha = nn.Parameter(self.alpha)
+        if self._general_on:                                             # :320-325 conventional attention (default init)
+            self.attn_layer = nn.Sequential(nn.Linear(A, A), nn.Tanh(), nn.Linear(A, 1))
         self.relu = nn.ReLU(inplace=True)
         self.dropout_i = nn.Dropout(p=dropout_i)                         # kept as attributes; the HIP kernels apply them
         self.dropout_v = nn.Dropout(p=dropout_v)
@@ -437,7 +445,8 @@ class VideoModel(nn.Module):
             return (_lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_FEATURE_GRADS |
                     (_lib.FLAG_BN_SHARED if self.use_bn != 'none' else 0) | (_lib.FLAG_MCD if self.ens_DA == 'MCD' else 0))
         return (_lib.FLAG_ADV_RELATION | _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME |
-                (_lib.FLAG_TRANS_ATTN if self._attn_on else 0) |
+                (_lib.FLAG_TRANS_ATTN if self._attn_on and not self._general_on else 0) |
+                (_lib.FLAG_GENERAL_ATTN if self._general_on else 0) |          # use_attn general: the learned attention layer
                 (_lib.FLAG_FRAME_ATTN if self._attn_frame_on else 0) |      # use_attn_frame: F1a = (1 + w_frame) F1 into the TRN
                 _lib.FLAG_FEATURE_GRADS |                                   # feat[1] may carry a discrepancy loss (dis_DA)
                 (_lib.FLAG_BN_SHARED if self.use_bn != 'none' else 0) |

@@ -30,7 +30,7 @@ if ROOT not in sys.path:
 
 from ta3n_amd import checkpoint as ckpt  # noqa: E402
 from ta3n_amd import parallel  # noqa: E402
-from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, frame_attn_refusal, lr_dann  # noqa: E402
+from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, frame_attn_refusal, general_attn_refusal, lr_dann  # noqa: E402
 from ta3n_amd.models import ARCH_FEATURE_DIM  # noqa: E402
 from ta3n_amd.opts import parser  # noqa: E402
 
@@ -88,9 +88,17 @@ def validate_options(args, module_path: bool = False) -> None:
     need(args.pred_normalize == "N", "--pred_normalize Y")
     need(not args.pretrain_source, "--pretrain_source")
     need(args.lr_adaptive in ("dann", "none"), f"--lr_adaptive {args.lr_adaptive} (built: dann, none with --lr_steps/--lr_decay)")
-    need(args.use_attn in ("TransAttn", "none"), f"--use_attn {args.use_attn}")
+    # --use_attn general (models.py:320-325, 359-366): main.py trains it, on the engine's unfused launch lists (single rank) or on its module path
+    if module_path:
+        need(args.use_attn in ("TransAttn", "none", "general"), f"--use_attn {args.use_attn} (built: TransAttn, none, general)")
+        general_msg = general_attn_refusal(args.use_attn, frame_aggregation=args.frame_aggregation, use_attn_frame=args.use_attn_frame,
+                                           add_fc=args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA,
+                                           f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
+        need(not general_msg, general_msg)
+    else:
+        need(args.use_attn in ("TransAttn", "none"), f"--use_attn {args.use_attn}" + (" (built on main.py)" if args.use_attn == "general" else ""))
     # --use_attn_frame TransAttn (models.py:368-377, 612-614): with --use_attn TransAttn on trn-m, without the options listed there
-    frame_attn_msg = frame_attn_refusal(args.use_attn_frame, use_attn=args.use_attn, frame_aggregation=args.frame_aggregation, add_fc=args.add_fc,
+    frame_attn_msg = "" if args.use_attn == "general" else frame_attn_refusal(args.use_attn_frame, use_attn=args.use_attn, frame_aggregation=args.frame_aggregation, add_fc=args.add_fc,
                                         use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA,
                                         f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
     need(not frame_attn_msg, frame_attn_msg)
