@@ -133,6 +133,24 @@ typedef enum {
  * on TA3N_AGG_AVGPOOL, and with TA3N_FLAG_F32_SPLIT, _MCD, _BN_SHARED, shared_fc_layers > 1, chain, split_k, wgrads_late or
  * phase_tiles. */
 #define TA3N_FLAG_GENERAL_ATTN   (1u << 15)
+/* share_params=='N' on trn-m (models.py:174-192, 296-305, 565-566, 686-687): the target rows go through a first frame layer and a video
+ * classifier of their own (an asymmetric encoder); the frame discriminator, the TRN, the relation and video discriminators, attention,
+ * dropout and GradReverse are one set of weights for both domains.  Six more parameters under the reference's state_dict names:
+ * "fc_feature_shared_target" [F][D] is a live parameter of the plan when some loss reads a target row (any TA3N_FLAG_ADV_*,
+ * _ATTN_ENTROPY, _TARGET_ENTROPY, _TARGET_LABELS), "fc_classifier_video_target" [C][NB] when some loss reads the target class logits
+ * (_ATTN_ENTROPY, _TARGET_ENTROPY, _TARGET_LABELS) - both with TA3N_FLAG_FEATURE_GRADS, where the caller assembles the loss; otherwise
+ * they sit behind the live prefix, where "fc_feature_target", "fc_classifier_target", "fc_feature_video_target" and
+ * "fc_feature_video_target_2" always sit (the reference never gives them a gradient).  No new region, no new launch: the plain unfused
+ * lists launch for launch (ta3n_has_fused_step and ta3n_has_pipelined_step return 0), with the shared-FC product, the video classifier,
+ * the gradient at the pooled video feature and the weight gradients of the two layers each built as a source and a target GEMM, cut at
+ * row batch_source * num_segments / video batch_source; the dropout masks stay keyed by the global row.  Built with fp32 and
+ * TA3N_FLAG_BF16_MFMA (with or without TA3N_FLAG_BF16_STORE), TA3N_FLAG_TRANS_ATTN or none, any ADV flags, the entropy terms,
+ * _CLASS_WEIGHTS, _TARGET_LABELS and _FEATURE_GRADS.  ta3n_plan_create refuses it by name on TA3N_AGG_AVGPOOL, together with
+ * TA3N_FLAG_MCD, _BN_SHARED, _FRAME_ATTN, _GENERAL_ATTN or _F32_SPLIT, with shared_fc_layers > 1, chain, split_k, wgrads_late or
+ * phase_tiles, and with batch_source == 0 or batch_target == 0.  Validation (main.validate scores the target branch, main.py:707): the caller
+ * places the n videos in the TARGET half of x (rows [batch_source * T, (batch_source + n) * T)) and their labels in region "labels"[0, n);
+ * ta3n_eval_metrics then scores rows [batch_source, batch_source + n) of "Y", n <= min(batch_source, batch_target). */
+#define TA3N_FLAG_UNSHARED       (1u << 16)
 
 /* ta3n_config.aggregation */
 #define TA3N_AGG_TRN_M    0   /* 'trn-m': multi-scale TRN - the TA3N path (TRNmodule.py:27-86) */

@@ -233,6 +233,11 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
     attn_general = args.use_attn == "general"
     if attn_general and (attn_frame != "none" or dis or mcd or args.use_bn != "none" or add_fc != 1):
         return None
+    # --share_params N: the engine's plain unfused launch lists with five GEMMs cut at the domain boundary (alone: share_params_refusal)
+    unshared = getattr(args, "share_params", "Y") == "N"
+    if unshared and (attn_frame != "none" or attn_general or dis or mcd or args.use_bn != "none" or add_fc != 1 or
+                     min(args.batch_size[0], args.batch_size[1]) < 1):
+        return None
     # --weighted_class_loss / --weighted_class_loss_DA: the engine takes the weights the two criteria carry (:160-167, 205-206)
     class_w, domain_w = _criterion_weights(criterion, num_class), _criterion_weights(criterion_domain, 2)
     g = optimizer.param_groups[0]
@@ -241,7 +246,7 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
            args.use_attn, args.adv_DA, args.use_target, float(args.dropout_i), float(args.dropout_v),
            ("Adam", float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) if adam else ("SGD", float(g["momentum"])),
            float(g["weight_decay"]), None if args.clip_gradient is None else float(args.clip_gradient), args.use_bn,
-           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame, class_w, domain_w)
+           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame, class_w, domain_w, unshared)
     eng = m.__dict__.get("_main_fast_engine", {}).get(key)
     if eng is None:
         eng = TrainEngine(args.batch_size[0], args.batch_size[1], args.num_segments, m.feature_dim, args.fc_dim, num_class,
@@ -250,10 +255,11 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
                           **(dict(optimizer="Adam", betas=tuple(g["betas"]), eps=g["eps"]) if adam else dict(momentum=g["momentum"])),
                           clip=args.clip_gradient if args.clip_gradient is not None else 0.0, device=next(m.parameters()).device,
                           use_bn=args.use_bn, **(dict(dis_DA=args.dis_DA, place_dis=tuple(args.place_dis)) if dis else {}),
-                          **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc, class_weights=class_w, domain_weights=domain_w)
-        if not eng.fused and not (dis or mcd or attn_frame != "none" or attn_general):
+                          **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc, class_weights=class_w, domain_weights=domain_w,
+                          share_params="N" if unshared else "Y")
+        if not eng.fused and not (dis or mcd or attn_frame != "none" or attn_general or unshared):
             return None
-        if class_w is not None or domain_w is not None or sv or tent or attn_general:      # said once: the weighted criteria / target labels / target entropy train on the engine
+        if class_w is not None or domain_w is not None or sv or tent or attn_general or unshared:      # said once: the weighted criteria / target labels / target entropy train on the engine
             print("[ta3n] " + eng.describe(), flush=True)
         m.__dict__.setdefault("_main_fast_engine", {})[key] = eng
     return eng

@@ -33,6 +33,7 @@ FLAG_CLASS_WEIGHTS = 1 << 12   # --weighted_class_loss: every class CE weighted 
 FLAG_TARGET_LABELS = 1 << 13   # --use_target Sv: the class CE over the valid rows of both halves, target labels in region "labels"[Bs:]; single rank
 FLAG_TARGET_ENTROPY = 1 << 14  # --add_loss_DA target_entropy: gamma * mean entropy of the valid target rows' class softmax; exclusive with FLAG_ATTN_ENTROPY
 FLAG_GENERAL_ATTN = 1 << 15   # use_attn general: relation weights = softmax over the relations of a learned layer's scores (parameters attn_layer.0 / .2; regions Ua, gUa, gs); unfused entry points, single rank
+FLAG_UNSHARED = 1 << 16       # share_params N: the target rows' own first frame layer and video classifier (parameters fc_*_target); unfused entry points, single rank
 AGG_TRN_M, AGG_AVGPOOL = 0, 1
 
 # every symbol include/ta3n_hip.h declares (tests check the export list)

@@ -60,7 +60,9 @@ def engine_checkpoint(eng, model, epoch: int, arch: str, lr: float, best_prec1: 
     sd = {"module." + k: v.cpu() for k, v in eng.state_dict().items()}
     for k, v in model.state_dict().items():
         sd.setdefault("module." + k, v.detach().cpu())
-    if getattr(eng, "general_attn", False):      # --use_attn general: the reference's key order, attn_layer.* last (the engine keeps them inside its live prefix)
+    # --use_attn general / --share_params N: the reference's key order (attn_layer.* last; fc_feature_shared_target behind fc_classifier_domain, ...) -
+    # the engine keeps those parameters inside its live prefix
+    if getattr(eng, "general_attn", False) or getattr(eng, "unshared", False):
         sd = {"module." + k: sd["module." + k] for k in model.state_dict()}
     names = [n for n, _ in model.named_parameters()]
     if getattr(eng, "optimizer", "SGD") == "Adam":      # torch.optim.Adam creates its state at a parameter's first update too

@@ -564,6 +564,8 @@ int ta3n_gather_segments_bf16_into(ta3n_plan *p, const void *store16, const int6
 int ta3n_eval_metrics(ta3n_plan *p, float *ws, int n_videos, int reset, void *stream) {
     if (!p || !ws) return fail(TA3N_ERR_INVALID, "null argument");
     if (n_videos < 0 || n_videos > p->geom.Bs) return fail(TA3N_ERR_INVALID, "n_videos must be in [0, batch_source]");
+    if ((p->geom.flags & TA3N_FLAG_UNSHARED) && n_videos > p->geom.Bt)
+        return fail(TA3N_ERR_INVALID, "TA3N_FLAG_UNSHARED: n_videos must be in [0, min(batch_source, batch_target)] (the videos are scored in the target half)");
     if (p->geom.C > 64) return fail(TA3N_ERR_INVALID, "num_class > 64 not supported");
     if (launch_eval_metrics(p->geom, ws, n_videos, reset, static_cast<hipStream_t>(stream)) != 0)
         return fail(TA3N_ERR_HIP, std::string("metrics launch failed: ") + hipGetErrorString(hipGetLastError()));

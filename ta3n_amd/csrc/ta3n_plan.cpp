@@ -14,6 +14,7 @@
 //   Y = Wcv Vd + bcv;  Pv = Wcdv relu(Wdv GRL(Vd) + bdv) + bcdv      models.py:686, 464-470
 //   TA3N_FLAG_FRAME_ATTN: wf = 1 - H(softmax Pf);  F1a = (1 + wf) F1 replaces F1 in Z_t             models.py:368-377, 612-614
 //   TA3N_FLAG_GENERAL_ATTN: w = softmax_j(<tanh(Wa1 R_j + ba1), wa2> + ba2) replaces w = 1 - H(softmax Pr)   models.py:320-325, 359-366
+//   TA3N_FLAG_UNSHARED: the target rows of F1 come from Wsh_t / bsh_t, the target rows of Y from Wcv_t / bcv_t   models.py:174-192, 296-305, 565-566, 686-687
 #include "ta3n_plan_builder.h"
 
 #include <cstdlib>
@@ -77,10 +78,23 @@ GemmSpec spec_wgrad(int M, int N, int K, int64_t g_off, int g_ld, int x_base, in
 
 // shared frame FC (models.py:565-575) into out_off: + ReLU + dropout_i, or - bn_shared - the linear output only (BatchNorm, ReLU
 // and dropout follow in the PH_BN_FWD launch)
-GemmSpec spec_shared_fc(const Dims &d, int64_t Wsh, int64_t bsh, int64_t out_off, bool bn_shared, int split) {
+// (TA3N_FLAG_UNSHARED: the rows [r0, r0 + nr) alone, through the layer at Wsh / bsh.  A spec's rows count from its own first row, so
+// the dropout_i element id - the GLOBAL row * F + n - gets the range's first element as its stream offset: the masks of the target
+// half do not restart at row 0)
+GemmSpec spec_shared_fc(const Dims &d, int64_t Wsh, int64_t bsh, int64_t out_off, bool bn_shared, int split, int r0 = 0, int nr = -1) {
     const int D = d.D, F = d.F;
     GemmSpec s;
-    s.M = d.BT; s.N = F;
+    s.M = nr < 0 ? d.BT : nr; s.N = F;
+    if (nr >= 0) {
+        s.segs.push_back(mkseg(KC(BASE_X, (int64_t)r0 * D, D), KC(BASE_P, Wsh, D), D));
+        s.proto = proto(BASE_WS, out_off + (int64_t)r0 * F, F);
+        with_bias(s.proto, bsh);
+        s.proto.epi |= EPI_RELU | EPI_DROP_I;
+        s.proto.gamma_kind = SK_INV_KEEP_I;
+        s.proto.drop_ld = F;
+        s.proto.pad2 = (int32_t)(uint32_t)((uint64_t)r0 * (uint64_t)F);
+        return s;
+    }
     if (split && D >= 512 && (D / 2) % 128 == 0) {
         // split_k bit 2 (round 6 experiment): the launch has ONE tile per compute unit at the headline shape - one resident workgroup
         // pulls its stages at ~15 B/clk where two pull ~21 - so every tile becomes two workgroups over the two halves of K
@@ -116,15 +130,18 @@ HeadParams head_params(const ta3n_plan &p, bool mcd) {
 }
 
 // gVt = drop_v'( -beta1 * gHv Wdv + gY Wcv [+ gY2 Wcv2] ), N = width of the video feature
-GemmSpec spec_gVt(const Geom &g, int N, const HeadParams &w, bool live_vid, bool mcd) {
+// (TA3N_FLAG_UNSHARED: the videos [b0, b0 + nb) alone, through the classifier at Wcv - a spec's rows count from its own first row, so the
+// dropout_v element id, which is the GLOBAL b * N + n, gets the range's first element as its stream offset)
+GemmSpec spec_gVt(const Geom &g, int N, const HeadParams &w, bool live_vid, bool mcd, int b0 = 0, int nb = -1, int64_t Wcv = -1) {
     GemmSpec gv;
-    gv.M = g.B; gv.N = N;
-    if (live_vid) gv.segs.push_back(mkseg(KC(BASE_WS, g.o_gHv, N), KM(BASE_P, w.Wdv, N), N, SK_NEG_BETA_VID));
-    gv.segs.push_back(mkseg(KC(BASE_WS, g.o_gY, g.C), KM(BASE_P, w.Wcv, N), g.C));
+    gv.M = nb < 0 ? g.B : nb; gv.N = N;
+    if (live_vid) gv.segs.push_back(mkseg(KC(BASE_WS, g.o_gHv + (int64_t)b0 * N, N), KM(BASE_P, w.Wdv, N), N, SK_NEG_BETA_VID));
+    gv.segs.push_back(mkseg(KC(BASE_WS, g.o_gY + (int64_t)b0 * g.C, g.C), KM(BASE_P, Wcv < 0 ? w.Wcv : Wcv, N), g.C));
     if (mcd) gv.segs.push_back(mkseg(KC(BASE_WS, g.o_gY2, g.C), KM(BASE_P, w.Wcv2, N), g.C));
-    gv.proto = proto(BASE_WS, g.o_gVt, N);
+    gv.proto = proto(BASE_WS, g.o_gVt + (int64_t)b0 * N, N);
     gv.proto.alpha_kind = SK_REVERSE_MU;      // forward(..., reverse=True): everything behind the video feature sees GradReverse(mu) (models.py:682-684)
     gv.proto.epi |= EPI_DROP_V; gv.proto.gamma_kind = SK_INV_KEEP_V; gv.proto.drop_ld = N;
+    gv.proto.pad2 = (int32_t)(uint32_t)((uint64_t)b0 * (uint64_t)N);
     return gv;
 }
 
@@ -575,8 +592,15 @@ struct TrnModel {
     // AFTER the TRN input gradient (add_unfused_lists)
     // TA3N_FLAG_GENERAL_ATTN (models.py:320-325, 359-366, 379-388): w = softmax over the relations of attn_layer(R_j), a learned layer
     // (Wa1, ba1, wa2, ba2: always live) in place of the relation discriminators' entropy - those stay computed, and live only with their loss
-    const bool frame_attn, general_attn;
+    // TA3N_FLAG_UNSHARED (models.py:174-192, 296-305, 565-566, 686-687): the target rows have a first frame layer (Wsh_t, bsh_t) and a video
+    // classifier (Wcv_t, bcv_t) of their own; everything between is one set of weights.  Five specs become a source and a target spec
+    // each, cut at row Bs T / video Bs, in the launch the whole one sat in.  The first layer is live when some loss reads a target row
+    // (any adversarial level, an entropy term, target labels), the classifier when some loss reads the target class logits (an entropy
+    // term, target labels) - both with TA3N_FLAG_FEATURE_GRADS, where the caller assembles the loss
+    const bool frame_attn, general_attn, unshared;
     const bool live_frm, live_vid, live_rel, mcd, feat_grads, bn_shared;
+    const bool live_cv_t, live_sh_t;
+    int64_t Wsh_t = -1, bsh_t = -1, Wcv_t = -1, bcv_t = -1;
     const int ldZ, ldR, ldF;
     int64_t o_F1a = -1, o_gF1a = -1, o_gFs = -1, o_gPfT = -1;   // frame attention: attended features, TRN input gradient, (1 + wf) gF1a, gPf + attention term
     int64_t o_Ua = -1, o_gUa = -1, o_gs = -1, Wa1 = -1, ba1 = -1, wa2 = -1, ba2 = -1;   // general attention: U / A = tanh(U), gradient at U, gradient at the scores; attn_layer.0 / .2
@@ -588,10 +612,12 @@ struct TrnModel {
 
     TrnModel(ta3n_plan &pl, const Dims &dm)
         : p(pl), b(pl), g(pl.geom), c(pl.cfg), d(dm), NR(dm.T - 1), NT(pl.n_tuples), frame_attn(c.flags & TA3N_FLAG_FRAME_ATTN),
-          general_attn(c.flags & TA3N_FLAG_GENERAL_ATTN),
+          general_attn(c.flags & TA3N_FLAG_GENERAL_ATTN), unshared(c.flags & TA3N_FLAG_UNSHARED),
           live_frm(c.flags & (TA3N_FLAG_ADV_FRAME | TA3N_FLAG_FRAME_ATTN)),
           live_vid(c.flags & TA3N_FLAG_ADV_VIDEO), live_rel(c.flags & (TA3N_FLAG_ADV_RELATION | TA3N_FLAG_TRANS_ATTN)), mcd(c.flags & TA3N_FLAG_MCD),
-          feat_grads(c.flags & TA3N_FLAG_FEATURE_GRADS), bn_shared(c.flags & TA3N_FLAG_BN_SHARED), ldZ(NT * dm.NB), ldR(NR * dm.NB), ldF(dm.T * dm.F) {}
+          feat_grads(c.flags & TA3N_FLAG_FEATURE_GRADS), bn_shared(c.flags & TA3N_FLAG_BN_SHARED),
+          live_cv_t(unshared && (c.flags & (TA3N_FLAG_ATTN_ENTROPY | TA3N_FLAG_TARGET_ENTROPY | TA3N_FLAG_TARGET_LABELS | TA3N_FLAG_FEATURE_GRADS))),
+          live_sh_t(unshared && (live_cv_t || (c.flags & (TA3N_FLAG_ADV_RELATION | TA3N_FLAG_ADV_VIDEO | TA3N_FLAG_ADV_FRAME)))), ldZ(NT * dm.NB), ldR(NR * dm.NB), ldF(dm.T * dm.F) {}
 
     int tau(int t, int pos) const { return p.tuples[(size_t)t * d.T + pos]; }
 
@@ -623,8 +649,30 @@ struct TrnModel {
     GemmSpec spec_Hr(int j) const;
     GemmSpec spec_Ua(int j) const;
     GemmSpec spec_gR(int j) const;
+    // ---- TA3N_FLAG_UNSHARED: the specs that exist once per domain (rows [0, Bs T) / videos [0, Bs): the source layer; the rest: the target's) ----
+    void push_F1(std::vector<GemmSpec> &s) const {
+        if (!unshared) { s.push_back(spec_F1()); return; }
+        s.push_back(spec_shared_fc(d, w.Wsh, w.bsh, g.o_F1, false, 0, 0, d.Bs * d.T));
+        s.push_back(spec_shared_fc(d, Wsh_t, bsh_t, g.o_F1, false, 0, d.Bs * d.T, d.Bt * d.T));
+    }
+    void push_Y(std::vector<GemmSpec> &s) const {
+        if (!unshared) { s.push_back(spec_Y()); return; }
+        s.push_back(spec_linear(d.Bs, d.C, d.NB, BASE_WS, g.o_Vd, d.NB, w.Wcv, w.bcv, g.o_Y, d.C, false));
+        s.push_back(spec_linear(d.Bt, d.C, d.NB, BASE_WS, g.o_Vd + (int64_t)d.Bs * d.NB, d.NB, Wcv_t, bcv_t, g.o_Y + (int64_t)d.Bs * d.C, d.C, false));
+    }
+    void push_gVt(std::vector<GemmSpec> &s) const {
+        if (!unshared) { s.push_back(spec_gVt(g, d.NB, w, true, mcd)); return; }
+        s.push_back(spec_gVt(g, d.NB, w, true, false, 0, d.Bs, w.Wcv));
+        s.push_back(spec_gVt(g, d.NB, w, true, false, d.Bs, d.Bt, Wcv_t));
+    }
     void push_video_head_wgrads(std::vector<GemmSpec> &s) const {   // dWcdv, dbcdv, dWcv, dbcv
         s.push_back(wgrad(2, d.NB, d.B, g.o_gPv, 2, g.o_Hv, d.NB, w.Wcdv, w.bcdv));
+        if (unshared) {   // K over the source videos into the source classifier's gradient, over the target videos into the target's (when it is live)
+            s.push_back(wgrad(d.C, d.NB, d.Bs, g.o_gY, d.C, g.o_Vd, d.NB, w.Wcv, w.bcv));
+            if (live_cv_t)
+                s.push_back(wgrad(d.C, d.NB, d.Bt, g.o_gY + (int64_t)d.Bs * d.C, d.C, g.o_Vd + (int64_t)d.Bs * d.NB, d.NB, Wcv_t, bcv_t));
+            return;
+        }
         s.push_back(wgrad(d.C, d.NB, d.B, g.o_gY, d.C, g.o_Vd, d.NB, w.Wcv, w.bcv));
         if (mcd) s.push_back(wgrad(d.C, d.NB, d.B, g.o_gY2, d.C, g.o_Vd, d.NB, w.Wcv2, w.bcv2));
     }
@@ -646,6 +694,12 @@ struct TrnModel {
     void push_f1_grad(std::vector<GemmSpec> &s) const;
     GemmSpec spec_gZ1_behind_frame_attn() const;
     void push_shared_fc_wgrad(std::vector<GemmSpec> &s) const {   // shared frame FC weight grad (no input gradient: the features are data); behind the BatchNorm with use_bn
+        if (unshared) {   // dWsh_s = gZ1[0 : Bs T]^T X[0 : Bs T], dWsh_t over the other rows (when it is live), with their bias gradients
+            const int rs = d.Bs * d.T;
+            s.push_back(spec_wgrad(d.F, d.D, rs, g.o_gZ1, d.F, BASE_X, 0, d.D, w.Wsh, w.bsh));
+            if (live_sh_t) s.push_back(spec_wgrad(d.F, d.D, d.Bt * d.T, g.o_gZ1 + (int64_t)rs * d.F, d.F, BASE_X, (int64_t)rs * d.D, d.D, Wsh_t, bsh_t));
+            return;
+        }
         s.push_back(spec_wgrad(d.F, d.D, d.BT, bn_shared ? g.o_gZ0 : st.o_gZ[1], d.F, BASE_X, 0, d.D, w.Wsh, w.bsh));   // + dbsh
     }
 };
@@ -771,6 +825,7 @@ GemmSpec TrnModel::spec_gZ1_behind_frame_attn() const {
 void TrnModel::add_params() {
     const int T = d.T, F = d.F, NB = d.NB, C = d.C;
     add_shared_fc_params(p, b, d);                                       // (--add_fc: updated by the first launch's side workgroups)
+    if (unshared) b.lin("fc_feature_shared_target", F, d.D, live_sh_t);  // :175
     b.lin("fc_feature_domain", F, F, live_frm);                          // :161
     b.lin("fc_classifier_domain", 2, F, live_frm);                       // :170
     for (int j = 0; j < NR; ++j)                                         // TRNmodule.py:44-54
@@ -781,6 +836,7 @@ void TrnModel::add_params() {
     }
     b.lin("fc_feature_domain_video", NB, NB, live_vid);                  // :267
     b.add_linear("fc_classifier_video_source", C, NB, true);             // :272
+    if (unshared) b.lin("fc_classifier_video_target", C, NB, live_cv_t); // :303
     if (bn_shared) add_bn_shared_params(b, F);
     if (mcd) b.add_linear("fc_classifier_video_source_2", C, NB, true);  // :276-279 (ens_DA MCD)
     b.lin("fc_classifier_domain_video", 2, NB, live_vid);                // :281
@@ -797,6 +853,14 @@ void TrnModel::add_params() {
     b.add_param("bn_trn_T.weight", NB, 0, false); b.add_param("bn_trn_T.bias", NB, 0, false);
     b.add_linear("fc_feature_video_source", NB, NB, false);              // :258
     b.add_linear("fc_feature_video_source_2", NB, NB, false);            // :262
+    if (unshared) {                                                      // computed by the reference (fc_classifier_target, :618) or not at all: feed no loss
+        b.add_linear("fc_feature_target", F, F, false);                  // :187
+        b.add_linear("fc_classifier_target", C, F, false);               // :190
+        b.add_linear("fc_feature_video_target", NB, NB, false);          // :297
+        b.add_linear("fc_feature_video_target_2", NB, NB, false);        // :300
+        Wsh_t = p.poff("fc_feature_shared_target.weight"); bsh_t = p.poff("fc_feature_shared_target.bias");
+        Wcv_t = p.poff("fc_classifier_video_target.weight"); bcv_t = p.poff("fc_classifier_video_target.bias");
+    }
 
     w = head_params(p, mcd);
     for (int j = 0; j < NR; ++j) {
@@ -900,7 +964,7 @@ void TrnModel::add_unfused_lists() {
     const int BT = d.BT, F = d.F;
     if (frame_attn) { add_frame_attn_lists(); return; }
     if (general_attn) { add_general_attn_lists(); return; }
-    b.add_gemm_phase(0, spec_F1());
+    { std::vector<GemmSpec> s; push_F1(s); b.add_gemm_phase(0, s); }
     if (bn_shared) b.add_simple_phase(PH_BN_FWD, 0);
     add_stack_forward(b, st, 0, BT, F);
     {   // F2
@@ -915,7 +979,7 @@ void TrnModel::add_unfused_lists() {
         b.add_gemm_phase(0, s);
     }
     b.add_simple_phase(PH_POOL_FWD, 0);   // Pr, attention weights, R, V, Vd
-    { std::vector<GemmSpec> s{spec_Y(), spec_Hv()}; if (mcd) s.push_back(spec_Y2()); b.add_gemm_phase(0, s); }   // F6
+    { std::vector<GemmSpec> s; push_Y(s); s.push_back(spec_Hv()); if (mcd) s.push_back(spec_Y2()); b.add_gemm_phase(0, s); }   // F6
     b.add_gemm_phase(0, spec_Pv());       // F7
     b.add_simple_phase(PH_LOSS, 1);
     {   // Q1: heads that depend only on the logit gradients
@@ -925,7 +989,8 @@ void TrnModel::add_unfused_lists() {
         b.add_gemm_phase(2, s);
     }
     {   // Q2: gradient at the pooled video feature + first-layer weight grads of the video/frame discriminators
-        std::vector<GemmSpec> s{spec_gVt(g, d.NB, w, true, mcd)};
+        std::vector<GemmSpec> s;
+        push_gVt(s);
         push_video_disc_wgrads(s);
         push_frame_disc_wgrads(s);
         b.add_gemm_phase(2, s);
@@ -1167,6 +1232,29 @@ std::string general_attn_refusal(const ta3n_config &c) {
     return with ? what + " with " + with + " is not built" : "";
 }
 
+// "" when the configuration's unshared target layers are built, otherwise the refusal (naming the combination)
+std::string share_params_refusal(const ta3n_config &c) {
+    if (!(c.flags & TA3N_FLAG_UNSHARED)) return "";
+    const std::string what = "share_params N (TA3N_FLAG_UNSHARED)";
+    if (c.aggregation != TA3N_AGG_TRN_M) return what + " on avgpool is not built: the unshared target layers are built on the unfused trn-m lists";
+    if (c.batch_source <= 0 || c.batch_target <= 0)
+        return what + " with batch_source == 0 or batch_target == 0 is not built: each domain's layers need rows of their own";
+    const char *with = nullptr;
+    if (c.flags & TA3N_FLAG_MCD) with = "ens_DA MCD (TA3N_FLAG_MCD)";
+    else if (c.flags & TA3N_FLAG_BN_SHARED) with = "use_bn (TA3N_FLAG_BN_SHARED)";
+    else if (c.flags & TA3N_FLAG_FRAME_ATTN) with = "use_attn_frame (TA3N_FLAG_FRAME_ATTN)";
+    else if (c.flags & TA3N_FLAG_GENERAL_ATTN) with = "use_attn general (TA3N_FLAG_GENERAL_ATTN)";
+    else if (c.flags & TA3N_FLAG_F32_SPLIT) with = "TA3N_FLAG_F32_SPLIT";
+    else if (c.shared_fc_layers > 1) with = "shared_fc_layers (--add_fc) > 1";
+    else if (c.chain) with = "chain";
+    else if (c.split_k) with = "split_k";
+    else if (c.wgrads_late) with = "wgrads_late";
+    else
+        for (int i = 0; i < 16; ++i)
+            if (c.phase_tiles[i]) with = "phase_tiles (indexed by the plain launch order)";
+    return with ? what + " with " + with + " is not built" : "";
+}
+
 int build_plan_trn(ta3n_plan &p, std::string &err) {
     const Dims d = dims_of(p.cfg);
     if (const char *e = bn_shared_refusal(p.cfg, d)) { err = e; return TA3N_ERR_INVALID; }
@@ -1196,11 +1284,11 @@ int build_plan_trn(ta3n_plan &p, std::string &err) {
         // general attention: the unfused lists only (the fused heads kernel computes the entropy attention); its two launches keep no twin -
         // what they write (R, A, gUa, gRa, gHr, gs) is read by the relation-level launch, which reads no twins in the plain lists either
         add_bf16_twins(p, m.b, m.g, d.BT, d.D, {}, {});
-    } else if (heads_supported(d.NB, d.C, d.F) && !m.mcd && !m.feat_grads && !(m.bn_shared && p.cfg.chain != 0)) {
+    } else if (heads_supported(d.NB, d.C, d.F) && !m.mcd && !m.feat_grads && !m.unshared && !(m.bn_shared && p.cfg.chain != 0)) {
         if (!m.add_fused_step(err)) return TA3N_ERR_INVALID;
     } else {
-        // no fused step (TA3N_FLAG_FEATURE_GRADS: dis_DA DAN / JAN put a gradient between forward and backward; TA3N_FLAG_MCD; a shape the heads
-        // kernel does not cover): the unfused lists are all there is - round 6: they read twins too (add_bf16_twins: the unfused family)
+        // no fused step (TA3N_FLAG_FEATURE_GRADS: dis_DA DAN / JAN put a gradient between forward and backward; TA3N_FLAG_MCD; TA3N_FLAG_UNSHARED:
+        // the heads kernel keeps one classifier per workgroup; a shape the heads kernel does not cover): the unfused lists are all there is - round 6: they read twins too (add_bf16_twins: the unfused family)
         add_bf16_twins(p, m.b, m.g, d.BT, d.D, {}, {});
     }
     return finish_plan(p, m.b, err);
@@ -1258,6 +1346,7 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     if (c.xcd_aware < 0 || c.xcd_aware > 3) { err = "xcd_aware must be 0, 1, 2 or 3"; return TA3N_ERR_INVALID; }
     if ((int64_t)d.BT * d.D >= (1ll << 31) || (int64_t)d.BT * d.F >= (1ll << 31)) { err = "problem too large for 32-bit offsets"; return TA3N_ERR_INVALID; }
     { const std::string e = shared_layers_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
+    { const std::string e = share_params_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     { const std::string e = general_attn_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     { const std::string e = frame_attn_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     if (c.aggregation == TA3N_AGG_TRN_M) return build_plan_trn(p, err);

@@ -764,9 +764,12 @@ __global__ __launch_bounds__(1024) void eval_metrics_kernel(Geom g, float *__res
     // TA3N_FLAG_CLASS_WEIGHTS: main.validate's criterion(pred, label) is the weighted mean of THIS batch (main.py:725), averaged over batches by
     // batch size: metrics[0] += n * sum_b w[y_b] ce_b / sum_b w[y_b]
     const ClassRule cr = class_rule(g, ws, reinterpret_cast<const Hyper *>(ws + g.o_hyper)->class_w_off, n, 0, 1.f, lane);
+    // TA3N_FLAG_UNSHARED: the videos were forwarded in the TARGET half, through the target layers (main.validate scores the target branch);
+    // their labels sit in labels[0, n) as always
+    const int row0 = (g.flags & TA3N_FLAG_UNSHARED) ? g.Bs : 0;
     float ce = 0.f, t1 = 0.f, t5 = 0.f;
     for (int b = wv; b < n; b += 16) {
-        const float y = lane < C ? ws[g.o_Y + (size_t)b * C + lane] : -INFINITY;
+        const float y = lane < C ? ws[g.o_Y + (size_t)(row0 + b) * C + lane] : -INFINITY;
         const int lab = labels[b];
         const LaneSoft sm = lane_log_softmax(y, lane < C);
         const float ylab = wave_allreduce_sum(lane == lab ? y : 0.f);

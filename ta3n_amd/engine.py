@@ -163,6 +163,31 @@ def general_attn_refusal(use_attn: str = "general", frame_aggregation: str = "tr
     return f"--use_attn general together with {', '.join(other)} is not built (single rank, the unfused launch lists)" if other else ""
 
 
+def share_params_refusal(share_params: str = "N", frame_aggregation: str = "trn-m", use_attn: str = "TransAttn", use_attn_frame: str = "none",
+                         add_fc: int = 1, use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", f32_split: bool = False,
+                         chain: bool = False, split_k: int = 0, wgrads_late: bool = False, phase_tiles: bool = False, world: int = 1,
+                         process_group: bool = False, ddp_selftest: bool = False, sharded_update: bool = False,
+                         peer_exchange: bool = False) -> str:
+    """'' when --share_params `share_params` is 'Y' or 'N' is built together with the other options, otherwise the message that refuses it
+    (naming the combination).  Built: the target rows' own first frame layer and video classifier on trn-m (models.py:174-192, 296-305,
+    565-566, 686-687), use_attn TransAttn or none, fp32 and bf16, SGD and Adam, the weighted criteria, Sv and the entropy terms, any
+    place_adv, on one rank: the plain unfused launch lists with five of their GEMMs cut at the domain boundary."""
+    if share_params == "Y":
+        return ""
+    if share_params != "N":
+        return f"--share_params {share_params} (built: Y, N)"
+    if frame_aggregation != "trn-m":
+        return f"--share_params N on --frame_aggregation {frame_aggregation}: built for trn-m (the unfused launch lists)"
+    other = [what for what, on in ((f"--use_bn {use_bn}", use_bn != "none"), (f"--dis_DA {dis_DA}", dis_DA != "none"),
+                                   (f"--ens_DA {ens_DA}", ens_DA != "none"), (f"--add_fc {add_fc}", add_fc != 1),
+                                   (f"--use_attn_frame {use_attn_frame}", use_attn_frame != "none"),
+                                   (f"--use_attn {use_attn}", use_attn not in ("TransAttn", "none")),
+                                   ("f32_split", f32_split), ("chained launches (chain)", chain), ("split_k", bool(split_k)),
+                                   ("wgrads_late", wgrads_late), ("explicit phase_tiles / tuned tile lists", phase_tiles)) if on]
+    other += _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
+    return f"--share_params N together with {', '.join(other)} is not built (single rank, the unfused launch lists)" if other else ""
+
+
 def adam_refusal(world: int = 1, sharded_update: bool = False, process_group: bool = False, ddp_selftest: bool = False,
                  peer_exchange: bool = False, fused_update: bool = False, side_update: bool = False, capture: bool = False,
                  two_stream: bool = False) -> str:
@@ -313,13 +338,14 @@ class TrainEngine:
                  ens_DA: str = "none", mu: float = 0.0, split_k: Optional[int] = None, sharded_update: Optional[bool] = None,
                  peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False,
                  add_fc: int = 1, optimizer: str = "SGD", betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8,
-                 class_weights: Optional[Sequence[float]] = None, domain_weights: Optional[Sequence[float]] = None):
+                 class_weights: Optional[Sequence[float]] = None, domain_weights: Optional[Sequence[float]] = None,
+                 share_params: str = "Y"):
         sw = self._switches = _resolve_switches(sharded_update, peer_exchange, grad_transport, ddp_buckets, split_k, chain)
         flags, fused, world_checks = self._check_options(
             sw, flags=flags, fused=fused, num_class=num_class, process_group=process_group, optimizer=optimizer, betas=betas, eps=eps,
             class_weights=class_weights, domain_weights=domain_weights, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, place_dis=place_dis,
             alpha=alpha, ens_DA=ens_DA, mu=mu, aggregation=aggregation, wgrads_late=wgrads_late, phase_tiles=phase_tiles,
-            f32_split=f32_split, bf16=bf16, bf16_store=bf16_store)
+            f32_split=f32_split, bf16=bf16, bf16_store=bf16_store, share_params=share_params)
         if not torch.cuda.is_available():
             raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -355,7 +381,8 @@ class TrainEngine:
         self._hyper = _lib.Hyper()
 
     def _check_options(self, sw: "_Switches", *, flags, fused, num_class, process_group, optimizer, betas, eps, class_weights, domain_weights,
-                       add_fc, use_bn, dis_DA, place_dis, alpha, ens_DA, mu, aggregation, wgrads_late, phase_tiles, f32_split, bf16, bf16_store):
+                       add_fc, use_bn, dis_DA, place_dis, alpha, ens_DA, mu, aggregation, wgrads_late, phase_tiles, f32_split, bf16, bf16_store,
+                       share_params="Y"):
         """Refuses what is not built and composes the plan's flags from the options; touches no device and no plan.  Returns (flags,
         fused, world_checks): world_checks are the (refusal, arguments) of the single-rank options, which the constructor asks again
         with the world size once it knows it (Adam's first: the order in which they win over each other)."""
@@ -410,6 +437,22 @@ class TrainEngine:
             flags = ALL_FLAGS if aggregation == "trn-m" else 0
         if self.class_weights is not None:
             flags |= _lib.FLAG_CLASS_WEIGHTS
+        # share_params N (the argument, or TA3N_FLAG_UNSHARED in `flags`; models.py:174-192, 296-305, 565-566, 686-687): the target rows go through
+        # a first frame layer and a video classifier of their own (parameters fc_feature_shared_target / fc_classifier_video_target, live when a
+        # loss reads a target row / the target class logits).  The plain unfused launch lists with five GEMMs cut at the domain boundary;
+        # single rank.  Validation goes through the target layers (evaluate_batch).
+        if share_params == "N":
+            flags |= _lib.FLAG_UNSHARED
+        self.unshared = bool(flags & _lib.FLAG_UNSHARED)
+        if self.unshared or share_params != "Y":
+            refuse(share_params_refusal, share_params="N" if self.unshared else share_params, frame_aggregation=aggregation,
+                   use_attn="general" if flags & _lib.FLAG_GENERAL_ATTN else "TransAttn",
+                   use_attn_frame="TransAttn" if flags & _lib.FLAG_FRAME_ATTN else "none", add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA,
+                   ens_DA=ens_DA, f32_split=bool(f32_split), chain=sw.chain_arg, split_k=sw.split_k, wgrads_late=bool(wgrads_late),
+                   phase_tiles=bool(phase_tiles and any(phase_tiles)) or bool(sw.phase_tiles_env),
+                   process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
+                   peer_exchange=sw.peer_exchange)
+            fused = False
         # use_attn general (TA3N_FLAG_GENERAL_ATTN in `flags`, flags_from_options(use_attn="general"); models.py:320-325, 359-366): the relation
         # weights are the softmax over the relations of a learned layer's scores (parameters attn_layer.0 / attn_layer.2, always live).  The
         # unfused launch lists with a general-attention launch in place of each pooling launch; single rank.
@@ -493,7 +536,7 @@ class TrainEngine:
 
     def _create_plan(self, sw: "_Switches", flags: int, fused: bool, *, fc_dim, tile_config, phase_tiles, xcd_aware, wgrads_late) -> None:
         """self.plan (and self.chain, self._flags) for the checked options: the launch-shape choices, then the plan builder."""
-        plain = self.aggregation == "trn-m" and self.add_fc == 1 and not self.frame_attn and not self.general_attn
+        plain = self.aggregation == "trn-m" and self.add_fc == 1 and not self.frame_attn and not self.general_attn and not self.unshared
         if phase_tiles is None and tile_config == 0 and plain:      # measured choices for the benchmarked shapes (indexed by the plain launch order)
             from .tuning import tuned_phase_tiles
             phase_tiles = tuned_phase_tiles(self.B, self.T, self.D, self.F, self.bf16, self.bf16_store, split=bool(flags & _lib.FLAG_F32_SPLIT))
@@ -656,6 +699,7 @@ class TrainEngine:
                 f"{', target labels (use_target Sv)' if self.target_labels else ''}"
                 f"{', target entropy' if self.target_entropy else ''}"
                 f"{', general attention (use_attn general)' if self.general_attn else ''}"
+                f"{', unshared target layers (share_params N)' if self.unshared else ''}"
                 f"{', domain weights ({:.3g}, {:.3g})'.format(*self.domain_weights) if self.domain_weights is not None else ''}: {step}")
 
     # ---- plumbing ----
@@ -1481,12 +1525,19 @@ class TrainEngine:
         loss / top-1 / top-5 / confusion matrix on the device; read them with eval_results().
         The reference scores the TARGET branch of model(val_data, val_data) (main.py:707-712): with use_bn the videos - which sit in the
         source rows here - go through bn_shared_T, its affine pair and its running statistics (ta3n_hyper.bn_eval_target).
+        share_params N: the videos are placed in the TARGET half of the batch - rows [Bs, Bs + n), through fc_feature_shared_target and
+        fc_classifier_video_target - and ta3n_eval_metrics scores those rows of the class logits (labels stay in labels[0, n)); at most
+        min(batch_source, batch_target) videos per call.
         An update that train_step_pipelined / train_steps left pending is applied first: the parameters scored are current."""
         n = val_data.shape[0]
         if n > self.Bs:
             raise ValueError(f"at most batch_source = {self.Bs} validation videos per call")
+        if self.unshared and n > self.Bt:
+            raise ValueError(f"share_params N: at most min(batch_source, batch_target) = {min(self.Bs, self.Bt)} validation videos per call "
+                             f"(they are scored in the target half)")
         self.flush()
-        self.X[: n * self.T].copy_(val_data.reshape(-1, self.D), non_blocking=True)
+        first = self.Bs * self.T if self.unshared else 0
+        self.X[first: first + n * self.T].copy_(val_data.reshape(-1, self.D), non_blocking=True)
         self.refresh_bf16(x=True)      # (the forward launches of a twin plan read the input's bf16 twin - since round 6 the unfused lists do too)
         self._labels[:n].copy_(val_label.to(torch.int32), non_blocking=True)
         self.set_hyper([0.0, 0.0, 0.0], 0.0, 0.0, train=False, valid_source=n, valid_target=0, bn_eval_target=1)

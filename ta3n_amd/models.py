@@ -11,7 +11,9 @@ Supported configurations = the TA3N hot path and TemPoolin
 frame_aggregation='trn-m' (use_attn in {'TransAttn','none'}) or 'avgpool' (use_attn 'none': BASELINE configs[0] and the
 TemPooling + RevGrad rows), baseline_type='video', share_params='Y', use_bn='none', add_fc=1, ens_DA='none',
 use_attn_frame='none'; add_fc 2 / 3 (models.py:145-153, 581-603) with use_bn 'none' and ens_DA 'none';
-use_attn_frame='TransAttn' (models.py:368-377, 612-614) with use_attn='TransAttn' on 'trn-m', use_bn 'none', ens_DA 'none', add_fc 1.
+use_attn_frame='TransAttn' (models.py:368-377, 612-614) with use_attn='TransAttn' on 'trn-m', use_bn 'none', ens_DA 'none', add_fc 1;
+share_params='N' (models.py:174-192, 296-305, 565-566, 686-687) on 'trn-m' with use_attn 'TransAttn' / 'none', use_bn 'none', ens_DA 'none',
+add_fc 1, use_attn_frame 'none'.
 Anything else raises NotImplementedError at construction (several of those
 branches are broken in the reference itself).
 """
@@ -184,12 +186,20 @@ class _HipForward(torch.autograd.Function):
         if not model._attn_on:
             ctx.mark_non_differentiable(attn)
         ctx.set_materialize_grads(False)      # an output that feeds no loss arrives as None in backward (see there)
-        return (attn, y, pr, pv, pf, v, f1, y2) + lower
+        ctx.Bs = Bs
+        # share_params N: the target rows' class logits are an output of their own - whether a loss read them decides whether
+        # fc_classifier_video_target receives a gradient (backward)
+        return (attn, y, pr, pv, pf, v, f1, y2) + lower + ((y[Bs:].clone(),) if model._unshared else ())
 
     @staticmethod
     def backward(ctx, g_attn, g_y, g_pr, g_pv, g_pf, g_v, g_f1, g_y2, *g_lower):
         model, plan, ws = ctx.model, ctx.plan, ctx.ws
         dev = ws.device
+        g_yt = g_lower[-1] if model._unshared else None
+        if g_yt is not None:      # into the target rows of the logit gradient
+            full = g_yt.new_zeros((ctx.Bs + g_yt.shape[0], g_yt.shape[1])) if g_y is None else g_y.clone()
+            full[ctx.Bs:] += g_yt
+            g_y = full
 
         def put(name, g):
             off, n = plan.region(name)
@@ -218,6 +228,15 @@ class _HipForward(torch.autograd.Function):
             unused += ["fc_feature_domain_video.", "fc_classifier_domain_video."]
         if g_pr is None and (model._general_on or not model._attn_on):      # with TransAttn the weights are not detached (models.py:351-357): the relation
             unused += ["relation_domain_classifier_all."]      # discriminators receive a gradient through V whatever the loss uses
+        if model._unshared:
+            # share_params N: the reference leaves grad None where no loss reads the layer's rows - the target classifier without a loss on
+            # the target class logits, the target rows' first layer when no loss reads a target row at all.  Seen from here: the target
+            # logits' gradient is None, and no gradient arrived at any tensor that holds both domains' rows (a loss on the source rows of
+            # such a tensor alone is told apart no further: the reference's own losses always read both halves)
+            if g_yt is None:
+                unused += ["fc_classifier_video_target."]
+                if g_pr is None and g_pv is None and g_pf is None and g_v is None and g_attn is None:
+                    unused += ["fc_feature_shared_target."]
         _deliver_grads(model, plan, grads, fresh, tuple(unused), ctx.needs_input_grad[6:])
         return (None,) * (6 + ctx.n_params)
 
@@ -306,7 +325,11 @@ class VideoModel(nn.Module):
         if frame_aggregation == 'avgpool' and use_attn != 'none':
             unsupported.append("frame_aggregation='avgpool' with use_attn (the reference's script runs TemPooling with use_attn none)")
         if baseline_type != 'video': unsupported.append(f"baseline_type={baseline_type!r}")
-        if share_params != 'Y': unsupported.append("share_params='N'")
+        if share_params != 'Y':           # models.py:174-192, 296-305, 565-566, 686-687: the target rows' own first frame layer and video classifier
+            from .engine import share_params_refusal
+            refused = share_params_refusal(share_params, frame_aggregation=frame_aggregation, use_attn=use_attn, use_attn_frame=use_attn_frame,
+                                           add_fc=add_fc, use_bn=use_bn, ens_DA=ens_DA)
+            if refused: unsupported.append(f"share_params={share_params!r} ({refused})")
         if use_bn not in ('none', 'AdaBN', 'AutoDIAL'): unsupported.append(f"use_bn={use_bn!r}")
         if use_bn != 'none' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("use_bn with this frame_aggregation")
         if ens_DA not in ('none', 'MCD'): unsupported.append(f"ens_DA={ens_DA!r}")
@@ -349,6 +372,7 @@ class VideoModel(nn.Module):
         self._general_on = use_attn == 'general'                 # ... from a learned layer, not from the relation discriminators
         self._attn_frame_on = use_attn_frame == 'TransAttn'
         self._avg = frame_aggregation == 'avgpool'
+        self._unshared = share_params == 'N'
         if verbose:
             print(f"Initializing TSN with base model: {base_model}. input_modality: {modality}, "
                   f"num_segments: {train_segments}, new_length: {self.new_length}")
@@ -379,6 +403,10 @@ class VideoModel(nn.Module):
         self.fc_feature_domain = lin(F_, F_)                             # :161
         self.fc_classifier_source = lin(F_, num_class)                   # :166 (dead for baseline_type='video')
         self.fc_classifier_domain = lin(F_, 2)                           # :170
+        if self._unshared:                                               # :174-192
+            self.fc_feature_shared_target = lin(self.feature_dim, F_)    # :175 the target rows' first frame layer
+            self.fc_feature_target = lin(F_, F_)                         # :187 (unused in forward)
+            self.fc_classifier_target = lin(F_, num_class)               # :190 (feeds nothing for baseline_type='video')
         self.num_bottleneck = NB
         if self._avg:                                                    # feat_aggregated_dim = feat_shared_dim (models.py:246-247)
             A = F_
@@ -397,6 +425,10 @@ class VideoModel(nn.Module):
         if not self._avg:
             self.relation_domain_classifier_all = nn.ModuleList(         # :286-294 (default init)
                 nn.Sequential(nn.Linear(NB, NB), nn.ReLU(), nn.Linear(NB, 2)) for _ in range(train_segments - 1))
+        if self._unshared:                                               # :296-305
+            self.fc_feature_video_target = lin(A, A)                     # :297 (unused)
+            self.fc_feature_video_target_2 = lin(A, A)                   # :300 (unused)
+            self.fc_classifier_video_target = lin(A, num_class)          # :303 the target rows' video classifier
         if use_bn != 'none':                                             # :307-312 (unused with trn-m)
             self.bn_source_video_S = nn.BatchNorm1d(A)
             self.bn_source_video_T = nn.BatchNorm1d(A)
@@ -448,6 +480,7 @@ class VideoModel(nn.Module):
                 (_lib.FLAG_TRANS_ATTN if self._attn_on and not self._general_on else 0) |
                 (_lib.FLAG_GENERAL_ATTN if self._general_on else 0) |          # use_attn general: the learned attention layer
                 (_lib.FLAG_FRAME_ATTN if self._attn_frame_on else 0) |      # use_attn_frame: F1a = (1 + w_frame) F1 into the TRN
+                (_lib.FLAG_UNSHARED if self._unshared else 0) |             # share_params N: the target rows' own first layer and classifier
                 _lib.FLAG_FEATURE_GRADS |                                   # feat[1] may carry a discrepancy loss (dis_DA)
                 (_lib.FLAG_BN_SHARED if self.use_bn != 'none' else 0) |
                 (_lib.FLAG_MCD if self.ens_DA == 'MCD' else 0))
@@ -598,6 +631,10 @@ class VideoModel(nn.Module):
             attn, y, pr, pv, pf, v, f1, y2, *lower = _HipForward.apply(self, input_source, input_target, list(beta), self.training,
                                                                         float(mu) if reverse else None, *params)
         out_s, out_t = y[s], y[t]
+        if self._unshared:      # the target logits as their own autograd output (_HipForward.forward)
+            out_t = lower.pop()
+            return (attn[s], out_s, out_s, [pr[s], pv[s], pf[s]], [out_s, v[s], f1[s]],
+                    attn[t], out_t, out_t, [pr[t], pv[t], pf[t]], [out_t, v[t], f1[t]])
         out_s2, out_t2 = (y2[s], y2[t]) if self.ens_DA == 'MCD' else (out_s, out_t)      # models.py:713-720
         return (attn[s], out_s, out_s2, [pr[s], pv[s], pf[s]], [y[s], v[s], f1[s]] + [f[s] for f in lower],
                 attn[t], out_t, out_t2, [pr[t], pv[t], pf[t]], [y[t], v[t], f1[t]] + [f[t] for f in lower])

@@ -30,7 +30,7 @@ if ROOT not in sys.path:
 
 from ta3n_amd import checkpoint as ckpt  # noqa: E402
 from ta3n_amd import parallel  # noqa: E402
-from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, frame_attn_refusal, general_attn_refusal, lr_dann  # noqa: E402
+from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, frame_attn_refusal, general_attn_refusal, lr_dann, share_params_refusal  # noqa: E402
 from ta3n_amd.models import ARCH_FEATURE_DIM  # noqa: E402
 from ta3n_amd.opts import parser  # noqa: E402
 
@@ -102,7 +102,15 @@ def validate_options(args, module_path: bool = False) -> None:
                                         use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA,
                                         f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
     need(not frame_attn_msg, frame_attn_msg)
-    need(args.share_params == "Y", "--share_params N")
+    # --share_params N (models.py:174-192, 296-305, 565-566, 686-687): main.py trains it, on the engine's unfused launch lists (single rank) or
+    # on its module path
+    if module_path:
+        share_msg = share_params_refusal(args.share_params, frame_aggregation=args.frame_aggregation, use_attn=args.use_attn,
+                                         use_attn_frame=args.use_attn_frame, add_fc=args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA,
+                                         ens_DA=args.ens_DA, f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
+        need(not share_msg, share_msg)
+    else:
+        need(args.share_params == "Y", "--share_params N (built on main.py)")
     # --add_fc 2 / 3 (models.py:145-153, 581-603): TA3N / trn-m and TemPooling with use_bn none, without dis_DA / ens_DA
     add_fc_msg = add_fc_refusal(args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA)
     need(not add_fc_msg, add_fc_msg)
