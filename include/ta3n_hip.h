@@ -212,6 +212,14 @@ typedef struct {
                               * aggregation and everything behind them read the LAST layer's output (Geom o_F1 / o_gZ1); the
                               * earlier layers' activations and gradients are the workspace regions "F_l<k>" / "gZ_l<k>".
                               * Built for use_bn none without MCD and without chain / split_k / wgrads_late / phase_tiles. */
+    uint32_t layout_flags;   /* 0 (default): the plan lays its parameters out itself.  Otherwise: the flags of a "donor" configuration (every
+                              * other field as in this one) whose flat parameter layout this plan adopts - order, offsets, ta3n_param_floats and
+                              * ta3n_live_param_floats are the donor's - while its launches, its losses and which parameters are live stay those
+                              * of `flags`.  Two plans can then address ONE params / grads / optimiser-state buffer: the source-only pass of
+                              * --pretrain_source (main.py:388-414) beside the step proper.  The live parameters are then no prefix: they are
+                              * the ranges of ta3n_live_range, and ta3n_sgd_live is the update (the prefix updates and the pipelined /
+                              * multi-step entry points refuse such a plan by name).  ta3n_plan_create refuses by message a parameter that is
+                              * live under `flags` and not under `layout_flags`, and a parameter the donor does not have. */
 } ta3n_config;
 
 /* Per-step scalars; lives in device memory inside ws (region "hyper").  The host
@@ -485,6 +493,22 @@ int ta3n_sgd_range(ta3n_plan *plan, float *params, float *grads, float *momentum
                    void *stream);
 int ta3n_train_step_join(ta3n_plan *plan, const float *x, const float *params, float *grads, float *ws,
                          void *stream, void *join_event);
+
+/* The maximal float ranges [begin, end) of the flat buffer that hold this plan's live parameters, in ascending order and disjoint.
+ * Parameters are 8-float aligned, so every bound is a multiple of 4 (float4 access).  A plan without ta3n_config.layout_flags has
+ * one range, [0, ta3n_live_param_floats); a plan on a donor's layout has one per run of parameters that are adjacent there. */
+int ta3n_num_live_ranges(const ta3n_plan *plan);
+int ta3n_live_range(const ta3n_plan *plan, int index, int64_t *begin, int64_t *end);
+
+/* clip_grad_norm_ + Nesterov SGD with weight decay (main.py:409-414) over the plan's live ranges ONLY - the optimiser step of a
+ * loss that reaches part of the parameters (torch skips a parameter whose grad is None: no weight decay, no momentum decay, no
+ * share of the clip norm).  One launch, the range table passed by value; element rule and arithmetic of ta3n_sgd_range, bf16
+ * twins of the new values included.  fused_norm != 0: the norm comes from the per-tile sums of squares this plan's ta3n_train_step
+ * left in ws["sumsq"]; otherwise a norm pass over the live ranges runs first - whatever the gradient buffer holds outside them
+ * never enters.  ws["grad_norm"], ws["grad_norm" + 1] receive norm and clip coefficient.  Every float outside the ranges is left
+ * as it is in params and momentum.  On a plan without layout_flags: ta3n_sgd_range(0, ta3n_live_param_floats) bit for bit. */
+int ta3n_sgd_live(ta3n_plan *plan, float *params, float *grads, float *momentum, float *ws, int fused_norm, float lr,
+                  float momentum_coef, float weight_decay, float clip, void *stream);
 
 /* The same update directly after ta3n_train_step on the same ws, with the gradient buffer untouched in
  * between (single rank: no all-reduce): the global norm is taken from the per-tile sums of squares the

@@ -130,12 +130,16 @@ def main():
     # === training (:215-274) === #
     start_train = time.time()
     beta, gamma, mu = args.beta, args.gamma, args.mu
+    loss_c_current = loss_c_previous = 999                                              # :221-222 (random large number)
     for epoch in range(start_epoch, args.epochs + 1):
         alpha = 2 / (1 + math.exp(-1 * epoch / args.epochs)) - 1 if args.alpha < 0 else args.alpha      # :231
-        if args.lr_adaptive == "none" and epoch in args.lr_steps:                       # :236-237
+        if args.lr_adaptive == "loss":                                                  # :233-234
+            adjust_learning_rate_loss(optimizer, args.lr_decay, loss_c_current, loss_c_previous, ">")
+        elif args.lr_adaptive == "none" and epoch in args.lr_steps:                     # :236-237
             adjust_learning_rate(optimizer, args.lr_decay)
-        train(num_class, source_loader, target_loader, model, criterion, criterion_domain, optimizer, epoch, train_file,
-              train_short_file, alpha, beta, gamma, mu)
+        loss_c, _, _ = train(num_class, source_loader, target_loader, model, criterion, criterion_domain, optimizer, epoch, train_file,
+                             train_short_file, alpha, beta, gamma, mu)
+        loss_c_previous, loss_c_current = loss_c_current, loss_c                        # :246-248
         if epoch % args.eval_freq == 0 or epoch == args.epochs:                         # :252-274
             prec1 = validate(val_loader, model, criterion, num_class, epoch, val_file)
             is_best = prec1 > best_prec1
@@ -186,7 +190,7 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
     optimiser's momentum in at the start of an epoch and back at its end, so validate(), checkpoints and --resume see nn.Parameters and
     torch.optim state as before.  --optimizer Adam (a plain torch.optim.Adam: one group, amsgrad / maximize / decoupled weight decay /
     capturable off) takes the same path with the engine's Adam update; exp_avg / exp_avg_sq / step travel like the momentum buffers."""
-    from ta3n_amd.engine import TrainEngine, flags_from_options
+    from ta3n_amd.engine import TrainEngine, flags_from_options, pretrain_refusal
     m = model.module
     needed = ("frame_aggregation", "dis_DA", "ens_DA", "use_bn", "save_attention", "add_loss_DA", "use_attn", "use_target", "place_adv", "adv_DA",
               "batch_size", "num_segments", "fc_dim", "dropout_i", "dropout_v", "clip_gradient", "no_partialbn", "print_freq", "lr_adaptive", "epochs")
@@ -240,13 +244,24 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
         return None
     # --weighted_class_loss / --weighted_class_loss_DA: the engine takes the weights the two criteria carry (:160-167, 205-206)
     class_w, domain_w = _criterion_weights(criterion, num_class), _criterion_weights(criterion_domain, 2)
+    # --pretrain_source: the engine's source-only pass (a second plan on the step's parameter layout + ta3n_sgd_live) where it is built
+    pretrain = bool(getattr(args, "pretrain_source", False))
+    if pretrain:
+        refused = pretrain_refusal(optimizer="Adam" if adam else "SGD", dis_DA=args.dis_DA if args.use_target != "none" else "none",
+                                   ens_DA=args.ens_DA if args.use_target != "none" else "none", use_attn=args.use_attn, use_attn_frame=attn_frame,
+                                   share_params="N" if unshared else "Y", add_fc=add_fc, use_bn=args.use_bn if args.use_target != "none" else "none")
+        if refused:
+            if not m.__dict__.get("_pretrain_said"):
+                m.__dict__["_pretrain_said"] = True
+                print(f"[ta3n] --pretrain_source trains on the module path: {refused}", flush=True)
+            return None
     g = optimizer.param_groups[0]
     # everything the engine is BUILT from: a later train() call with other options must not find an engine made for these
     key = (args.batch_size[0], args.batch_size[1], args.num_segments, args.fc_dim, num_class, tuple(args.place_adv), args.add_loss_DA,
            args.use_attn, args.adv_DA, args.use_target, float(args.dropout_i), float(args.dropout_v),
            ("Adam", float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) if adam else ("SGD", float(g["momentum"])),
            float(g["weight_decay"]), None if args.clip_gradient is None else float(args.clip_gradient), args.use_bn,
-           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame, class_w, domain_w, unshared)
+           args.dis_DA, tuple(args.place_dis) if dis else (), args.ens_DA, add_fc, attn_frame, class_w, domain_w, unshared, pretrain)
     eng = m.__dict__.get("_main_fast_engine", {}).get(key)
     if eng is None:
         eng = TrainEngine(args.batch_size[0], args.batch_size[1], args.num_segments, m.feature_dim, args.fc_dim, num_class,
@@ -256,10 +271,10 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
                           clip=args.clip_gradient if args.clip_gradient is not None else 0.0, device=next(m.parameters()).device,
                           use_bn=args.use_bn, **(dict(dis_DA=args.dis_DA, place_dis=tuple(args.place_dis)) if dis else {}),
                           **(dict(ens_DA="MCD") if mcd else {}), add_fc=add_fc, class_weights=class_w, domain_weights=domain_w,
-                          share_params="N" if unshared else "Y")
+                          share_params="N" if unshared else "Y", pretrain_source=pretrain)
         if not eng.fused and not (dis or mcd or attn_frame != "none" or attn_general or unshared):
             return None
-        if class_w is not None or domain_w is not None or sv or tent or attn_general or unshared:      # said once: the weighted criteria / target labels / target entropy train on the engine
+        if class_w is not None or domain_w is not None or sv or tent or attn_general or unshared or pretrain:      # said once: the weighted criteria / target labels / target entropy train on the engine
             print("[ta3n] " + eng.describe(), flush=True)
         m.__dict__.setdefault("_main_fast_engine", {})[key] = eng
     return eng
@@ -318,11 +333,16 @@ def _train_fast(eng, num_class, source_loader, target_loader, model, optimizer, 
             lr = optimizer.param_groups[0]["lr"]
             # the dropout seeds come from the global torch RNG exactly as VideoModel.forward draws them (one draw of two per train forward):
             # the same masks as the module path, and the same RNG state for the samplers of the next epoch
+            more = {}
+            if eng.pretrain_source:      # :390: the source-only pass's forward comes first and draws its own pair
+                s0 = torch.randint(0, 2 ** 31 - 1, (2,))
+                more["raw_seeds_pretrain"] = (int(s0[0]), int(s0[1]))
             seeds = torch.randint(0, 2 ** 31 - 1, (2,))
             if mcd:      # the second, reversed forward draws its own pair (:548), right behind the first one's
                 s2 = torch.randint(0, 2 ** 31 - 1, (2,))
                 eng.mcd_raw_seeds = (int(s2[0]), int(s2[1]))
-            eng.train_step(beta_new, gamma, lr, valid_source=batch_source_ori, valid_target=batch_target_ori, raw_seeds=(int(seeds[0]), int(seeds[1])))
+            eng.train_step(beta_new, gamma, lr, valid_source=batch_source_ori, valid_target=batch_target_ori, raw_seeds=(int(seeds[0]), int(seeds[1])),
+                           **more)
             l = eng.losses()                                                # (one host sync per step; the reference has five .item() calls)
             out = eng.outputs()["out"][:batch_source_ori]
             if mcd:      # the terms the loss kernel does not know (train_ddp.py's log_line keeps the same books): the second classifier's
@@ -438,6 +458,18 @@ def train(num_class, source_loader, target_loader, model, criterion, criterion_d
         source_label = source_label.cuda(non_blocking=True)                             # :377-378
         target_label = target_label.cuda(non_blocking=True)
         label_source = source_label
+        if getattr(args, "pretrain_source", False):                                     # :388-414: pre-train on the source data
+            _, out_pre, out_pre_2, _, _, _, _, _, _, _ = model(source_data, target_data, beta_new, mu, is_train=True, reverse=False)
+            loss_pre = criterion(out_pre[:batch_source_ori], label_source)
+            if args.ens_DA == "MCD" and args.use_target != "none":
+                loss_pre = loss_pre + criterion(out_pre_2[:batch_source_ori], label_source)
+            optimizer.zero_grad()      # (set_to_none: a parameter this loss does not reach is skipped by clip and step)
+            loss_pre.backward()
+            if args.clip_gradient is not None:
+                total_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), args.clip_gradient)
+                if total_norm > args.clip_gradient and args.verbose:
+                    print("clipping gradient: {} with coef {}".format(total_norm, args.clip_gradient / total_norm))
+            optimizer.step()
         attn_source, out_source, out_source_2, pred_domain_source, feat_source, attn_target, out_target, out_target_2, \
             pred_domain_target, feat_target = model(source_data, target_data, beta_new, mu, is_train=True, reverse=False)   # :418
         attn_source, out_source, out_source_2, pred_domain_source, feat_source = removeDummy(
@@ -616,6 +648,14 @@ def adjust_learning_rate(optimizer, decay):
     """:789-792."""
     for param_group in optimizer.param_groups:
         param_group["lr"] /= decay
+
+
+def adjust_learning_rate_loss(optimizer, decay, stat_current, stat_previous, op):
+    """:794-798: lr /= decay when the statistic moved the way `op` names."""
+    ops = {">": (lambda x, y: x > y), "<": (lambda x, y: x < y), ">=": (lambda x, y: x >= y), "<=": (lambda x, y: x <= y)}
+    if ops[op](stat_current, stat_previous):
+        for param_group in optimizer.param_groups:
+            param_group["lr"] /= decay
 
 
 def adjust_learning_rate_dann(optimizer, p):

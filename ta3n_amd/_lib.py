@@ -52,6 +52,7 @@ SYMBOLS = [
     "ta3n_gaussian_kernel_scratch_floats", "ta3n_gaussian_kernel", "ta3n_mmd_rowdiff", "ta3n_discrepancy_scratch_floats", "ta3n_discrepancy",
     "ta3n_mcd_source_loss", "ta3n_mcd_second_loss",
     "ta3n_set_heads_waves", "ta3n_get_heads_waves",
+    "ta3n_num_live_ranges", "ta3n_live_range", "ta3n_sgd_live",
     "ta3n_shard_ranges", "ta3n_shard_sumsq", "ta3n_sgd_shard", "ta3n_shard_reduce_scatter", "ta3n_sharded_update", "ta3n_train_steps_sharded",
 ]
 
@@ -62,7 +63,8 @@ class Config(C.Structure):
                 ("num_class", C.c_int32), ("flags", C.c_uint32), ("tile_config", C.c_int32),
                 ("phase_tiles", C.c_int32 * 16), ("xcd_aware", C.c_int32), ("aggregation", C.c_int32),
                 ("wgrads_late", C.c_int32), ("chain", C.c_int32), ("cost_model", C.c_int32), ("split_k", C.c_int32),
-                ("shared_fc_layers", C.c_int32)]      # --add_fc (0 / 1: one shared layer)
+                ("shared_fc_layers", C.c_int32),      # --add_fc (0 / 1: one shared layer)
+                ("layout_flags", C.c_uint32)]         # 0, or the flags of the configuration whose flat parameter layout this plan adopts
 
 
 class Hyper(C.Structure):
@@ -151,6 +153,9 @@ def lib() -> C.CDLL:
     L.ta3n_sgd_step_fused.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ta3n_sgd_range.argtypes = [vp, vp, vp, vp, vp, i64, i64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     L.ta3n_train_step_join.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.ta3n_num_live_ranges.argtypes = [vp]
+    L.ta3n_live_range.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]
+    L.ta3n_sgd_live.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     L.ta3n_train_step_range.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     L.ta3n_refresh_bf16.argtypes = [vp, vp, vp, vp, vp]
     L.ta3n_has_pipelined_step.argtypes = [vp]
@@ -257,7 +262,7 @@ class Plan:
     def __init__(self, batch_source: int, batch_target: int, num_segments: int, feature_dim: int, fc_dim: int,
                  num_class: int, flags: int, num_bottleneck: int = 256, tile_config: int = 0,
                  phase_tiles: Optional[List[int]] = None, xcd_aware: int = 0, aggregation: int = 0, wgrads_late: int = 0,
-                 chain: int = 0, cost_model: int = 0, split_k: int = 0, shared_fc_layers: int = 0):
+                 chain: int = 0, cost_model: int = 0, split_k: int = 0, shared_fc_layers: int = 0, layout_flags: int = 0):
         L = lib()
         self.cfg = Config(batch_source, batch_target, num_segments, feature_dim, fc_dim, num_bottleneck, num_class,
                           flags, tile_config)
@@ -270,6 +275,7 @@ class Plan:
         self.cfg.cost_model = int(cost_model)
         self.cfg.split_k = int(split_k)
         self.cfg.shared_fc_layers = int(shared_fc_layers)      # --add_fc (models.py:145-153)
+        self.cfg.layout_flags = int(layout_flags)              # the parameter layout of the plan these flags would give (0: its own)
         h = C.c_void_p()
         check(L.ta3n_plan_create(C.byref(self.cfg), C.byref(h)), "ta3n_plan_create")
         self.handle = h
@@ -291,6 +297,12 @@ class Plan:
         self.regions: Dict[str, Tuple[int, int]] = {k: tuple(v) for k, v in self.description["regions"].items()}
         self.has_fused_step = L.ta3n_has_fused_step(h) == 1
         self.has_fused_update = L.ta3n_has_fused_update(h) == 1
+        # the float ranges of the flat buffer that hold the live parameters (one, the live prefix, without layout_flags)
+        self.live_ranges: List[Tuple[int, int]] = []
+        for i in range(L.ta3n_num_live_ranges(h)):
+            b = C.c_int64(); e = C.c_int64()
+            check(L.ta3n_live_range(h, i, C.byref(b), C.byref(e)), "ta3n_live_range")
+            self.live_ranges.append((b.value, e.value))
 
     def region(self, name: str) -> Tuple[int, int]:
         return self.regions[name]

@@ -29,6 +29,11 @@ int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
+// A plan on a donor's parameter layout (ta3n_config.layout_flags) has live RANGES, not a live prefix: the prefix updates refuse it by name
+const char *const LAYOUT_PLAN_TEXT = ": this plan lies on another plan's parameter layout (ta3n_config.layout_flags) - its live parameters are "
+                                     "the ranges of ta3n_live_range, update them with ta3n_sgd_live";
+#define REFUSE_LAYOUT_PLAN(p, fn) \
+    do { if ((p)->cfg.layout_flags) return fail(TA3N_ERR_INVALID, std::string(fn) + LAYOUT_PLAN_TEXT); } while (0)
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
@@ -601,7 +606,7 @@ int ta3n_train_step_range(ta3n_plan *p, const float *x, const float *params, flo
 int ta3n_has_pipelined_step(const ta3n_plan *p) {
     if (!p) return TA3N_ERR_INVALID;
     for (const Phase &ph : p->phases)
-        if (ph.group == 5) return 1;
+        if (ph.group == 5) return p->cfg.layout_flags ? 0 : 1;      // (the pipelined step carries a PREFIX update)
     return 0;
 }
 
@@ -768,6 +773,7 @@ namespace {
 struct Shards { int64_t a_chunk = 0, a_end = 0, b_chunk = 0, b_end = 0; };
 int shard_layout(const ta3n_plan *p, int world, Shards &s) {
     if (!p || world < 1) return fail(TA3N_ERR_INVALID, "bad shard arguments");
+    REFUSE_LAYOUT_PLAN(p, "the sharded update");
     if (p->first_floats <= 0 || p->first_floats >= p->live_floats) return fail(TA3N_ERR_INVALID, "no pipelined step for this configuration");
     const int64_t q = 4 * (int64_t)world;
     s.a_end = (p->first_floats + q - 1) / q * q;
@@ -931,7 +937,7 @@ int ta3n_has_fused_update(const ta3n_plan *p) {
     // every live parameter's gradient is produced by a tile / column-sum task of the fused step (those carry the update)
     // (pair twins: the fused-update epilogue keeps no lo plane of the new parameters - the separate update does)
     // (experiments build only: measured time-neutral in round 3, profiles/r03_fused_update_ab.txt)
-    return TA3N_EXPERIMENTS && ta3n_has_fused_step(p) == 1 && p->cfg.aggregation == TA3N_AGG_TRN_M && p->geom.pair_delta == 0 &&
+    return TA3N_EXPERIMENTS && !p->cfg.layout_flags && ta3n_has_fused_step(p) == 1 && p->cfg.aggregation == TA3N_AGG_TRN_M && p->geom.pair_delta == 0 &&
            p->cfg.shared_fc_layers <= 1 ? 1 : 0;      // (--add_fc > 1: not built)
 }
 
@@ -1003,6 +1009,7 @@ int ta3n_sgd_range(ta3n_plan *p, float *params, float *grads, float *momentum, f
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (begin < 0 || end > p->live_floats || begin > end || (begin & 3) || (end & 3))
         return fail(TA3N_ERR_INVALID, "range must be 4-float aligned and inside the live parameter prefix");
+    REFUSE_LAYOUT_PLAN(p, "ta3n_sgd_range");
     if (fused_norm && ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
     int rc = ensure_uploaded(p);
     if (rc != TA3N_OK) return rc;
@@ -1019,6 +1026,7 @@ int ta3n_sgd_step_next(ta3n_plan *p, float *params, float *grads, float *momentu
                        float momentum_coef, float weight_decay, float clip, const ta3n_hyper *next, void *stream) {
     if (!p || !params || !grads || !momentum || !ws || !next) return fail(TA3N_ERR_INVALID, "null argument");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    REFUSE_LAYOUT_PLAN(p, "ta3n_sgd_step_next");
     if (fused_norm && ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
     static_assert(sizeof(ta3n_hyper) == sizeof(Hyper), "ta3n_hyper and its device mirror differ");
     int rc = ensure_uploaded(p);
@@ -1048,6 +1056,7 @@ int ta3n_train_step_join(ta3n_plan *p, const float *x, const float *params, floa
 int ta3n_sgd_step_fused(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, void *stream) {
     if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    REFUSE_LAYOUT_PLAN(p, "ta3n_sgd_step_fused");
     if (ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration: use ta3n_sgd_step");
     int rc = ensure_uploaded(p);
     if (rc != TA3N_OK) return rc;
@@ -1059,10 +1068,46 @@ int ta3n_sgd_step_fused(ta3n_plan *p, float *params, float *grads, float *moment
 int ta3n_sgd_step(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, void *stream) {
     if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    REFUSE_LAYOUT_PLAN(p, "ta3n_sgd_step");
     int rc = ensure_uploaded(p);
     if (rc != TA3N_OK) return rc;
     Ptrs ptrs = make_ptrs(p, nullptr, params, grads, ws);
     return run_group(p, 3, ptrs, params, momentum, static_cast<hipStream_t>(stream));
+}
+
+int ta3n_num_live_ranges(const ta3n_plan *p) { return p ? (int)p->live_ranges.size() : TA3N_ERR_INVALID; }
+
+int ta3n_live_range(const ta3n_plan *p, int i, int64_t *begin, int64_t *end) {
+    if (!p || i < 0 || i >= (int)p->live_ranges.size()) return fail(TA3N_ERR_INVALID, "live range index out of range");
+    if (begin) *begin = p->live_ranges[i].first;
+    if (end) *end = p->live_ranges[i].second;
+    return TA3N_OK;
+}
+
+int ta3n_sgd_live(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, int fused_norm, float lr, float momentum_coef,
+                  float weight_decay, float clip, void *stream) {
+    if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    if (fused_norm && ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
+    LiveRanges lr_tab;
+    std::memset(&lr_tab, 0, sizeof(lr_tab));
+    if ((int)p->live_ranges.size() > LiveRanges::MAX)
+        return fail(TA3N_ERR_INVALID, "ta3n_sgd_live: more than " + std::to_string((int)LiveRanges::MAX) + " live ranges (the table travels by value)");
+    for (const auto &r : p->live_ranges) {
+        if (r.first < 0 || r.second > p->param_floats || r.first > r.second || (r.first & 3) || (r.second & 3))
+            return fail(TA3N_ERR_INVALID, "internal: live range not 4-float aligned inside the parameter buffer");
+        if (r.second == r.first) continue;
+        lr_tab.i0[lr_tab.n] = (int32_t)(r.first / 4);
+        lr_tab.i1[lr_tab.n] = (int32_t)(r.second / 4);
+        ++lr_tab.n;
+    }
+    int rc = ensure_uploaded(p);
+    if (rc != TA3N_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!fused_norm && launch_live_norm(p->geom, grads, ws, lr_tab, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
+    if (launch_sgd_live(p->geom, params, grads, momentum, ws, lr_tab, fused_norm != 0, lr, momentum_coef, weight_decay, clip, s) != 0)
+        return fail(TA3N_ERR_HIP, std::string("sgd launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return TA3N_OK;
 }
 
 // ---- clip + Adam (reference main.py:84-86: torch.optim.Adam(model.parameters(), lr, weight_decay=...); clip_grad_norm_ of :578-581) ----
@@ -1084,6 +1129,7 @@ int check_adam(const ta3n_plan *p, const float *params, const float *grads, cons
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (step < 1) return fail(TA3N_ERR_INVALID, "Adam: step counts from 1 (the number of the update being applied)");
     if (!(eps >= 0.f)) return fail(TA3N_ERR_INVALID, "Adam: eps must be >= 0");
+    REFUSE_LAYOUT_PLAN(p, "the Adam update");
     if (fused_norm && ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
     return TA3N_OK;
 }

@@ -294,6 +294,16 @@ int launch_sgd_fixup(const Geom &g, float *params, const float *grads, float *mo
                      float clip, const Hyper *next, hipStream_t stream);
 int launch_sgd_range(const Geom &g, float *params, const float *grads, float *momentum, float *ws, int64_t begin, int64_t end,
                      bool fused_norm, float lr, float mu, float wd, float clip, const Hyper *next, hipStream_t stream, bool write_norm = false);
+// The live ranges of a plan (ta3n_live_range) in float4 units, as a launch argument of ta3n_sgd_live's two kernels: ascending, disjoint,
+// none empty.  block0: first workgroup of each range in the update launch (filled by launch_sgd_live; block0[n] = the grid).
+struct LiveRanges {
+    static constexpr int MAX = 32;
+    int32_t n;
+    int32_t i0[MAX], i1[MAX], block0[MAX + 1];
+};
+int launch_live_norm(const Geom &g, const float *grads, float *ws, const LiveRanges &ranges, hipStream_t stream);
+int launch_sgd_live(const Geom &g, float *params, const float *grads, float *momentum, float *ws, LiveRanges ranges, bool fused_norm,
+                    float lr, float mu, float wd, float clip, hipStream_t stream);
 // clip + Adam over floats [begin, end) of the live prefix (adam_range_kernel): step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t)
 // already formed by the host (ta3n_adam_scalars); the betas in double so that 1 - beta reaches the kernel as torch's fp32 value of it
 int launch_adam_range(const Geom &g, float *params, const float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int64_t begin,

@@ -1364,13 +1364,46 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
 // plan is laid out (add_bf16_twins): build, look, and rebuild without the blocking where it cannot be used.
 int ta3n::build_plan(ta3n_plan &p, std::string &err) {
     const ta3n_config cfg = p.cfg;
+    // ta3n_config.layout_flags: build the donor first and place this plan's parameters where the donor has them
+    std::vector<ParamInfo> layout;
+    int64_t donor_live = 0;
+    if (cfg.layout_flags) {
+        ta3n_plan donor;
+        donor.cfg = cfg;
+        donor.cfg.flags = cfg.layout_flags;
+        donor.cfg.layout_flags = 0;
+        const int rc = build_plan(donor, err);
+        if (rc != TA3N_OK) { err = "layout_flags: the donor configuration is refused: " + err; return rc; }
+        layout = donor.params;
+        donor_live = donor.live_floats;
+    }
     uint64_t deny = 0;
     for (int attempt = 0; attempt < 16; ++attempt) {
         p = ta3n_plan();
         p.cfg = cfg;
         p.deny_blocking = deny;
+        p.layout = layout;
         const int rc = build_plan_once(p, err);
         if (rc != TA3N_OK) return rc;
+        if (!layout.empty()) {
+            if (p.layout_error.empty() && p.params.size() != layout.size()) p.layout_error = "the two configurations differ in their parameters";
+            if (!p.layout_error.empty()) { err = "layout_flags: " + p.layout_error; return TA3N_ERR_INVALID; }
+            std::stable_sort(p.params.begin(), p.params.end(), [](const ParamInfo &a, const ParamInfo &b) { return a.off < b.off; });   // the donor's order
+            p.live_floats = donor_live;
+            p.geom.live_floats = (int32_t)donor_live;
+        }
+        // the maximal runs of live parameters (8-float aligned slots: adjacent parameters touch)
+        p.live_ranges.clear();
+        if (layout.empty()) {
+            p.live_ranges.push_back({0, p.live_floats});
+        } else {
+            for (const ParamInfo &pi : p.params) {
+                if (!pi.live) continue;
+                const int64_t b0 = pi.off, e0 = align_up(pi.off + (int64_t)pi.rows * (pi.cols ? pi.cols : 1), 8);
+                if (!p.live_ranges.empty() && p.live_ranges.back().second == b0) p.live_ranges.back().second = e0;
+                else p.live_ranges.push_back({b0, e0});
+            }
+        }
         uint64_t bad = 0;
         for (size_t i = 0; i < p.phases.size(); ++i) {
             const Phase &ph = p.phases[i];

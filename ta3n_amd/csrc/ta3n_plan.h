@@ -2,6 +2,7 @@
 // tile tasks for one (Bs, Bt, T, D, F, C) configuration.
 #pragma once
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ta3n_hip.h"
@@ -24,6 +25,11 @@ struct ta3n_plan {
     ta3n::Geom geom;
     std::vector<ParamInfo> params;
     int64_t param_floats = 0, live_floats = 0;
+    // ta3n_config.layout_flags: the donor plan's parameter table (empty without it) - Builder::add_param places every parameter where the
+    // donor has it - what went wrong doing so, and the maximal runs of this plan's live parameters in the flat buffer (every plan has them)
+    std::vector<ParamInfo> layout;
+    std::string layout_error;
+    std::vector<std::pair<int64_t, int64_t>> live_ranges;
     int64_t first_floats = 0;   // size of the leading parameter block the step's first launch reads (shared frame FC weight + bias)
     std::vector<Region> regions;
     int64_t ws_floats = 0;

@@ -88,6 +88,19 @@ struct Builder {
         ParamInfo pi;
         pi.name = name; pi.rows = rows; pi.cols = cols; pi.live = live;
         pi.off = p.param_floats;
+        if (!p.layout.empty()) {   // ta3n_config.layout_flags: where the donor plan has it
+            const ParamInfo *at = nullptr;
+            for (const ParamInfo &d : p.layout) if (d.name == name) at = &d;
+            if (!at || at->rows != rows || at->cols != cols) {
+                if (p.layout_error.empty()) p.layout_error = "parameter " + name + " does not exist under layout_flags";
+            } else {
+                if (live && !at->live && p.layout_error.empty()) p.layout_error = "parameter " + name + " is live under flags and not under layout_flags";
+                pi.off = at->off;
+            }
+            p.params.push_back(pi);
+            p.param_floats = std::max(p.param_floats, align_up(pi.off + (int64_t)rows * (cols ? cols : 1), 8));
+            return;
+        }
         p.params.push_back(pi);
         p.param_floats = align_up(p.param_floats + (int64_t)rows * (cols ? cols : 1), 8);   // 8: a bf16 twin row starts 16-byte aligned too
     }

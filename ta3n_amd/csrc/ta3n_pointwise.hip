@@ -808,6 +808,35 @@ __global__ __launch_bounds__(256) void sgd_range_kernel(Geom g, float *__restric
     update_range(g, params, grads, ws, i0, i1, norm_off, norm_n, clip, SgdRule{{mom}, lr, mu, wd}, next, has_next, (int)gridDim.x, red);
 }
 
+// ta3n_sgd_live: the same update over a plan's live RANGES (a plan on a donor's parameter layout, ta3n_config.layout_flags: the parameters
+// its loss reaches are runs of the flat buffer, not a prefix) in one launch.  The table travels by value; workgroups
+// [block0[r], block0[r + 1]) stride range r exactly as sgd_range_kernel's would (update_range sees the range's start moved back by the
+// range's first workgroup, so blockIdx.x indexes within the range).  Workgroup 0 records norm and coefficient.  Nothing outside the
+// ranges is read or written.
+__global__ __launch_bounds__(256) void sgd_live_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
+                                                       float *__restrict__ mom, float *__restrict__ ws, LiveRanges rg, int norm_off,
+                                                       int norm_n, float lr, float mu, float wd, float clip) {
+    __shared__ float red[8];
+    int r = 0;
+    while (r + 1 < rg.n && (int)blockIdx.x >= rg.block0[r + 1]) ++r;
+    const int shift = rg.block0[r] * (int)blockDim.x, n_blocks = rg.block0[r + 1] - rg.block0[r];
+    const Hyper *__restrict__ hy = reinterpret_cast<const Hyper *>(ws + g.o_hyper);      // (has_next bit 0 clear: never read)
+    update_range(g, params, grads, ws, rg.i0[r] - shift, rg.i1[r], norm_off, norm_n, clip, SgdRule{{mom}, lr, mu, wd}, *hy, 2, n_blocks, red);
+}
+
+// ... and its norm pass: grad_norm_kernel restricted to the ranges (one range from 0: the same partials), so that whatever the
+// gradient buffer holds outside them - the step proper's gradients of the parameters this plan does not reach - never enters
+__global__ __launch_bounds__(256) void live_norm_kernel(const float *__restrict__ grads, float *__restrict__ part, LiveRanges rg) {
+    __shared__ float red[8];
+    float acc = 0.f;
+    const float4 *__restrict__ g4 = reinterpret_cast<const float4 *>(grads);
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (int r = 0; r < rg.n; ++r)
+        for (int i = rg.i0[r] + t; i < rg.i1[r]; i += stride) acc = sumsq4(g4[i], acc);
+    const float s = block_sum(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
 // clip_grad_norm_ + torch.optim.Adam (adam_update) on the same contract; only the range that starts at 0 records norm and coefficient.
 __global__ __launch_bounds__(256) void adam_range_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
                                                          float *__restrict__ exp_avg, float *__restrict__ exp_avg_sq, float *__restrict__ ws,
@@ -1459,6 +1488,23 @@ int launch_sgd_range(const Geom &g, float *params, const float *grads, float *mo
     const NormSource ns = norm_source(g, fused_norm);
     hipLaunchKernelGGL(sgd_range_kernel, dim3(update_blocks(i0, i1)), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1, ns.off, ns.n,
                        lr, mu, wd, clip, next_or_zero(next), (next ? 1 : 0) | (write_norm ? 2 : 0));
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_live_norm(const Geom &g, const float *grads, float *ws, const LiveRanges &ranges, hipStream_t stream) {
+    hipLaunchKernelGGL(live_norm_kernel, dim3(g.n_norm_blocks), dim3(256), 0, stream, grads, ws + g.o_norm_part, ranges);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_sgd_live(const Geom &g, float *params, const float *grads, float *momentum, float *ws, LiveRanges ranges, bool fused_norm,
+                    float lr, float mu, float wd, float clip, hipStream_t stream) {
+    // each range gets the workgroups ta3n_sgd_range would give it; an empty table still runs one workgroup (norm and coefficient are recorded)
+    ranges.block0[0] = 0;
+    for (int r = 0; r < ranges.n; ++r) ranges.block0[r + 1] = ranges.block0[r] + update_blocks(ranges.i0[r], ranges.i1[r]);
+    if (ranges.n == 0) { ranges.i0[0] = ranges.i1[0] = 0; ranges.block0[1] = 1; }
+    const NormSource ns = norm_source(g, fused_norm);
+    hipLaunchKernelGGL(sgd_live_kernel, dim3(ranges.block0[std::max(ranges.n, 1)]), dim3(256), 0, stream, g, params, grads, momentum, ws, ranges,
+                       ns.off, ns.n, lr, mu, wd, clip);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -215,6 +215,33 @@ def target_refusal(use_target: str = "none", add_loss_DA: str = "none", world: i
     return f"{' / '.join(opts)} together with {', '.join(what)} is not built (target labels and target entropy: single rank)" if what else ""
 
 
+# what the source-only pass of --pretrain_source drops from the step's flags (reference main.py:388-414: criterion(out_source, label_source)
+# and nothing else - no target row, no adversarial, entropy or discrepancy term)
+PRETRAIN_DROPPED_FLAGS = (_lib.FLAG_ADV_RELATION | _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_ATTN_ENTROPY |
+                          _lib.FLAG_TARGET_LABELS | _lib.FLAG_TARGET_ENTROPY)
+
+
+def pretrain_refusal(optimizer: str = "SGD", dis_DA: str = "none", ens_DA: str = "none", use_attn: str = "TransAttn",
+                     use_attn_frame: str = "none", share_params: str = "Y", add_fc: int = 1, use_bn: str = "none", f32_split: bool = False,
+                     feeds: bool = False, capture: bool = False, fused_update: bool = False, multi_step: bool = False, world: int = 1,
+                     process_group: bool = False, ddp_selftest: bool = False, sharded_update: bool = False, peer_exchange: bool = False) -> str:
+    """'' when TrainEngine(pretrain_source=True) - the source-only pass of --pretrain_source in front of every step, as a second plan on
+    the step's parameter layout with an update of its own live ranges (ta3n_sgd_live) - is built together with the named options,
+    otherwise the message that refuses it.  Built: trn-m with use_attn TransAttn / none and avgpool, fp32 and bf16 (twins), SGD, one rank."""
+    what = [w for w, on in (
+        ("optimizer Adam (torch keeps a step count per parameter - the parameters the pass does not reach fall behind; the engine keeps one)",
+         optimizer == "Adam"),
+        (f"--dis_DA {dis_DA}", dis_DA != "none"), (f"--ens_DA {ens_DA}", ens_DA != "none"),
+        (f"--use_attn_frame {use_attn_frame}", use_attn_frame != "none"), (f"--use_attn {use_attn}", use_attn not in ("TransAttn", "none")),
+        ("--share_params N", share_params == "N"), (f"--add_fc {add_fc}", int(add_fc) != 1), (f"--use_bn {use_bn}", use_bn != "none"),
+        ("f32_split (f32x3)", f32_split), ("train_steps(feeds=...)", feeds),
+        ("train_steps / the deferred and pipelined steps (the pass is not part of the multi-step calls)", multi_step),
+        ("capture()", capture), ("fused_update", fused_update)) if on]
+    what += _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
+    return (f"pretrain_source together with {', '.join(what)} is not built (the source-only pass: trn-m with use_attn TransAttn / none or "
+            f"avgpool, fp32 or bf16, SGD, add_fc 1, use_bn none, single rank, one step per call)") if what else ""
+
+
 def class_weights_from_list(list_file: str, num_class: int):
     """The class weights of --weighted_class_loss Y, main.py:156-164: 1 / (share of each class among the lines of the source list, whose
     third blank-separated field is the class id).  A class of the class file that the list does not hold would leave the reference with
@@ -327,6 +354,11 @@ class TrainEngine:
     workspace, static input buffers.  Source rows come first in every batch
     tensor (rows [0, Bs) source, [Bs, Bs+Bt) target)."""
 
+    # --pretrain_source is off unless the constructor turns it on (_setup_pretrain)
+    pretrain_source = False
+    plan_pre: Optional["_lib.Plan"] = None
+    ws_pre: Optional[torch.Tensor] = None
+
     def __init__(self, batch_source: int, batch_target: int, num_segments: int = 5, feature_dim: int = 2048,
                  fc_dim: int = 512, num_class: int = 12, flags: Optional[int] = None, dropout_i: float = 0.5,
                  dropout_v: float = 0.5, momentum: float = 0.9, weight_decay: float = 1e-4, clip: float = 20.0,
@@ -339,13 +371,25 @@ class TrainEngine:
                  peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False,
                  add_fc: int = 1, optimizer: str = "SGD", betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8,
                  class_weights: Optional[Sequence[float]] = None, domain_weights: Optional[Sequence[float]] = None,
-                 share_params: str = "Y"):
+                 share_params: str = "Y", pretrain_source: bool = False):
         sw = self._switches = _resolve_switches(sharded_update, peer_exchange, grad_transport, ddp_buckets, split_k, chain)
         flags, fused, world_checks = self._check_options(
             sw, flags=flags, fused=fused, num_class=num_class, process_group=process_group, optimizer=optimizer, betas=betas, eps=eps,
             class_weights=class_weights, domain_weights=domain_weights, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, place_dis=place_dis,
             alpha=alpha, ens_DA=ens_DA, mu=mu, aggregation=aggregation, wgrads_late=wgrads_late, phase_tiles=phase_tiles,
             f32_split=f32_split, bf16=bf16, bf16_store=bf16_store, share_params=share_params)
+        # --pretrain_source (reference main.py:388-414): a source-only pass with an optimiser step of its own in front of every step
+        self.pretrain_source = bool(pretrain_source)
+        if self.pretrain_source:
+            kw = dict(optimizer=optimizer, dis_DA=dis_DA, ens_DA=ens_DA, use_attn="general" if flags & _lib.FLAG_GENERAL_ATTN else "TransAttn",
+                      use_attn_frame="TransAttn" if flags & _lib.FLAG_FRAME_ATTN else "none",
+                      share_params="N" if flags & _lib.FLAG_UNSHARED else "Y", add_fc=add_fc, use_bn=use_bn, f32_split=bool(f32_split),
+                      process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
+                      peer_exchange=sw.peer_exchange)
+            refused = pretrain_refusal(**kw)
+            if refused:
+                raise NotImplementedError(refused)
+            world_checks.append((pretrain_refusal, kw))
         if not torch.cuda.is_available():
             raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -375,6 +419,7 @@ class TrainEngine:
         self._allocate_buffers(sw, fused)
         self._setup_exchange(sw, parallel.shared_native_comm if share_comm else parallel.NativeComm)
         self._setup_batchnorm()
+        self._setup_pretrain()
         self.step_count = 0
         self.skip_collective = False
         self.graph: Optional[torch.cuda.CUDAGraph] = None
@@ -549,11 +594,13 @@ class TrainEngine:
         # TA3N_CHAIN=1 only where it is built
         chain = sw.chain_arg if sw.chain_given else (sw.chain_env and plain and bool(fused))
         self._flags = int(flags)
-        self.plan = _lib.Plan(self.Bs, self.Bt, self.T, self.D, fc_dim, self.C, flags,
-                              tile_config=tile_config, phase_tiles=list(phase_tiles or []), xcd_aware=xcd_aware,
-                              aggregation=_lib.AGG_AVGPOOL if self.aggregation == "avgpool" else _lib.AGG_TRN_M,
-                              wgrads_late=int(wgrads_late), chain=int(chain), cost_model=sw.cost_model, split_k=sw.split_k,
-                              shared_fc_layers=self.add_fc)
+        # (kept: the source-only plan of pretrain_source is built from the same choices, _setup_pretrain)
+        self._plan_args = (self.Bs, self.Bt, self.T, self.D, fc_dim, self.C)
+        self._plan_kw = dict(tile_config=tile_config, phase_tiles=list(phase_tiles or []), xcd_aware=xcd_aware,
+                             aggregation=_lib.AGG_AVGPOOL if self.aggregation == "avgpool" else _lib.AGG_TRN_M,
+                             wgrads_late=int(wgrads_late), chain=int(chain), cost_model=sw.cost_model, split_k=sw.split_k,
+                             shared_fc_layers=self.add_fc)
+        self.plan = _lib.Plan(*self._plan_args, flags, **self._plan_kw)
         self.chain = bool(chain)
 
     def _allocate_buffers(self, sw: "_Switches", fused: bool) -> None:
@@ -689,6 +736,66 @@ class TrainEngine:
             self.bn_running[:, 0] = 0.0
             self.bn_running[:, 1] = 1.0
 
+    def _setup_pretrain(self) -> None:
+        """pretrain_source: the source-only plan - the step's flags without the adversarial, entropy and target-label bits - ON THE STEP'S
+        PARAMETER LAYOUT (ta3n_config.layout_flags), so that both plans address self.P / self.G / self.M, and a workspace of its own."""
+        self.plan_pre: Optional[_lib.Plan] = None
+        self.ws_pre: Optional[torch.Tensor] = None
+        if not self.pretrain_source:
+            return
+        pre_flags = self._flags & ~PRETRAIN_DROPPED_FLAGS
+        self.plan_pre = _lib.Plan(*self._plan_args, pre_flags, layout_flags=0 if pre_flags == self._flags else self._flags, **self._plan_kw)
+        p = self.plan_pre
+        if p.param_floats != self.plan.param_floats or [q[:3] for q in p.params] != [q[:3] for q in self.plan.params]:
+            raise _lib.Ta3nError("pretrain_source: the source-only plan does not lie on the step's parameter layout")
+        with torch.cuda.device(self.device):
+            self.ws_pre = torch.zeros(p.ws_floats, dtype=torch.float32, device=self.device)
+            _lib.check(self._L.ta3n_init_workspace(p.handle, self.ws_pre.data_ptr(), self._stream()), "ta3n_init_workspace")
+        off, n = p.region("labels")
+        self._labels_pre = self.ws_pre[off:off + n].view(torch.int32)
+        if self.class_weights is not None:
+            off, _ = p.region("class_w")
+            self.ws_pre[off:off + self.C].copy_(torch.tensor(self.class_weights, dtype=torch.float32, device=self.device))
+        self._pre_fused = self.fused and p.has_fused_step
+        self._hyper_pre = _lib.Hyper()
+
+    def _pretrain_pass(self, lr: float, raw_seeds: Optional[Sequence[int]]) -> None:
+        """The pass of reference main.py:388-414 on the batch in the static buffers: forward + class cross-entropy on the valid source rows +
+        backward through the source-only plan (its own workspace, its own dropout seeds), then clip + Nesterov SGD over that plan's live
+        ranges only - a parameter the loss does not reach keeps value and momentum, takes no weight decay and has no share in the clip norm
+        (torch skips grad None).  The per-step scalars are the step's (self._hyper, already set) with the class mean over the source rows."""
+        p, L, ws = self.plan_pre, self._L, self.ws_pre
+        h = self._hyper_pre
+        C.memmove(C.byref(h), C.byref(self._hyper), C.sizeof(_lib.Hyper))
+        h.inv_n_cls = 1.0 / max(self._global_source, 1)
+        if raw_seeds is None:
+            h.seed_i, h.seed_v = dropout_seeds(self.step_count ^ 0x40000000, self.rank)
+        else:
+            h.seed_i, h.seed_v = int(raw_seeds[0]) & 0xFFFFFFFF, int(raw_seeds[1]) & 0xFFFFFFFF
+        st = self._stream()
+        _lib.check(L.ta3n_set_hyper(p.handle, ws.data_ptr(), C.byref(h), st), "ta3n_set_hyper")
+        if self.bf16_store:      # the step's update left the new parameters' twins in ITS workspace
+            _lib.check(L.ta3n_refresh_bf16(p.handle, None, self.P.data_ptr(), ws.data_ptr(), st), "ta3n_refresh_bf16")
+        args = (p.handle, self.X.data_ptr(), self.P.data_ptr(), self.G.data_ptr(), ws.data_ptr(), st)
+        if self._pre_fused:
+            _lib.check(L.ta3n_train_step(*args), "ta3n_train_step")
+        else:
+            _lib.check(L.ta3n_forward(p.handle, self.X.data_ptr(), self.P.data_ptr(), ws.data_ptr(), st), "ta3n_forward")
+            _lib.check(L.ta3n_loss(p.handle, ws.data_ptr(), st), "ta3n_loss")
+            _lib.check(L.ta3n_backward(*args), "ta3n_backward")
+        _lib.check(L.ta3n_sgd_live(p.handle, self.P.data_ptr(), self.G.data_ptr(), self.M.data_ptr(), ws.data_ptr(), int(self._pre_fused),
+                                   float(lr), float(h.momentum), float(h.weight_decay), float(h.clip), st), "ta3n_sgd_live")
+        if self.bf16_store:      # ... and this one's went to the pass's workspace
+            self.refresh_bf16(params=True)
+
+    def pretrain_losses(self) -> Dict[str, float]:
+        """The last source-only pass's loss (its class cross-entropy is all of it)."""
+        if self.plan_pre is None:
+            raise _lib.Ta3nError("pretrain_losses: this engine was built without pretrain_source")
+        off, _ = self.plan_pre.region("losses")
+        v = self.ws_pre[off:off + 2].tolist()
+        return dict(loss=v[0], loss_c=v[1])
+
     def describe(self) -> str:
         """One line: the configuration this engine runs, the launch lists of its step included."""
         arith = "bf16" if self.bf16 else "f32x3" if self._flags & _lib.FLAG_F32_SPLIT else "fp32"
@@ -700,6 +807,7 @@ class TrainEngine:
                 f"{', target entropy' if self.target_entropy else ''}"
                 f"{', general attention (use_attn general)' if self.general_attn else ''}"
                 f"{', unshared target layers (share_params N)' if self.unshared else ''}"
+                f"{', source-only pass before every step (pretrain_source)' if self.pretrain_source else ''}"
                 f"{', domain weights ({:.3g}, {:.3g})'.format(*self.domain_weights) if self.domain_weights is not None else ''}: {step}")
 
     # ---- plumbing ----
@@ -810,6 +918,11 @@ class TrainEngine:
         if target_label is not None:
             self._labels[self.Bs:].copy_(target_label.to(torch.int32), non_blocking=True)
         self.refresh_bf16(x=True)
+        if self.plan_pre is not None:      # the source-only pass reads the same rows through its own workspace: labels and the input's twin
+            self._labels_pre[: self.Bs].copy_(self._labels[: self.Bs], non_blocking=True)
+            if self.bf16_store:
+                _lib.check(self._L.ta3n_refresh_bf16(self.plan_pre.handle, self.X.data_ptr(), None, self.ws_pre.data_ptr(), self._stream()),
+                           "ta3n_refresh_bf16")
 
     def set_hyper(self, beta: Sequence[float], gamma: float, lr: float, train: bool = True,
                   valid_source: Optional[int] = None, valid_target: Optional[int] = None,
@@ -1204,6 +1317,8 @@ class TrainEngine:
     def train_step_deferred(self, beta: Sequence[float], gamma: float, lr: float, **hyper_kw) -> None:
         """train_step whose optimiser update is postponed to the start of the next call, where all of it except the shared
         frame FC overlaps the next step's first launch.  Same arithmetic; call flush() before reading parameters."""
+        if self.pretrain_source:
+            raise NotImplementedError(pretrain_refusal(multi_step=True))
         if not self.fused:
             raise _lib.Ta3nError("deferred updates need the fused step")
         join = self._apply_pending(overlap=True)
@@ -1220,6 +1335,8 @@ class TrainEngine:
         """train_step whose optimiser update is postponed to the start of the next call, where ONE launch applies it and
         leaves the next step's scalars in the workspace (ta3n_sgd_step_next): no per-step host-to-device copy.  Same
         arithmetic as train_step; call flush() before reading parameters."""
+        if self.pretrain_source:
+            raise NotImplementedError(pretrain_refusal(multi_step=True))
         if not self.fused:
             raise _lib.Ta3nError("pipelined updates need the fused step")
         first = self._pending is None
@@ -1330,6 +1447,8 @@ class TrainEngine:
         (ta3n_train_steps_fused_update) - bit-identical whenever no step clips, within fp32 rounding of the clip correction otherwise.
         Measured time-neutral (profiles/r03_fused_update_ab.txt: the 63 MB of optimiser traffic cost ~8 us wherever they run), so the
         default stays the update as launches of its own (ta3n_train_steps), which is also what the data-parallel path needs."""
+        if self.pretrain_source:
+            raise NotImplementedError(pretrain_refusal(feeds=feeds is not None, fused_update=bool(fused_update), multi_step=True))
         n = len(schedule)
         if n == 0:
             return
@@ -1460,6 +1579,8 @@ class TrainEngine:
         are static).  set_hyper / set_batch stay outside: they only write device buffers."""
         if self.optimizer == "Adam":
             raise NotImplementedError(adam_refusal(capture=True))
+        if self.pretrain_source:
+            raise NotImplementedError(pretrain_refusal(capture=True))
         torch.cuda.synchronize(self.device)
         keep_p, keep_m = self.P.clone(), self.M.clone()
         side = torch.cuda.Stream(self.device)
@@ -1477,8 +1598,14 @@ class TrainEngine:
         self.graph = g
 
     def train_step(self, beta: Sequence[float], gamma: float, lr: float, **hyper_kw) -> None:
-        """One optimisation step on the batch already in the static buffers."""
+        """One optimisation step on the batch already in the static buffers.  pretrain_source: any pending update is settled, then the
+        source-only pass (its dropout seeds: raw_seeds_pretrain=) and its update of the parameters it reaches, then the step as always."""
+        raw_seeds_pretrain = hyper_kw.pop("raw_seeds_pretrain", None)
+        if self.pretrain_source:
+            self.flush()
         self.set_hyper(beta, gamma, lr, train=True, **hyper_kw)
+        if self.pretrain_source:
+            self._pretrain_pass(lr, raw_seeds_pretrain)
         if self.graph is not None:
             self.graph.replay()
         else:

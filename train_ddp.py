@@ -86,8 +86,12 @@ def validate_options(args, module_path: bool = False) -> None:
         need(args.weighted_class_loss == "N", "--weighted_class_loss Y (built on main.py)")
         need(args.weighted_class_loss_DA == "N", "--weighted_class_loss_DA Y (built on main.py)")
     need(args.pred_normalize == "N", "--pred_normalize Y")
-    need(not args.pretrain_source, "--pretrain_source")
-    need(args.lr_adaptive in ("dann", "none"), f"--lr_adaptive {args.lr_adaptive} (built: dann, none with --lr_steps/--lr_decay)")
+    # --pretrain_source (main.py:388-414: a source-only pass with an optimiser step of its own in front of every step) and --lr_adaptive loss
+    # (:233-234, 794-798: lr /= lr_decay at the top of an epoch whose predecessor's mean class loss rose): main.py trains them
+    if not module_path:
+        need(not args.pretrain_source, "--pretrain_source (built on main.py)")
+        need(args.lr_adaptive in ("dann", "none"), f"--lr_adaptive {args.lr_adaptive} (built: dann, none with --lr_steps/--lr_decay" +
+             ("; loss is built on main.py)" if args.lr_adaptive == "loss" else ")"))
     # --use_attn general (models.py:320-325, 359-366): main.py trains it, on the engine's unfused launch lists (single rank) or on its module path
     if module_path:
         need(args.use_attn in ("TransAttn", "none", "general"), f"--use_attn {args.use_attn} (built: TransAttn, none, general)")
