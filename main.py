@@ -190,7 +190,8 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
     optimiser's momentum in at the start of an epoch and back at its end, so validate(), checkpoints and --resume see nn.Parameters and
     torch.optim state as before.  --optimizer Adam (a plain torch.optim.Adam: one group, amsgrad / maximize / decoupled weight decay /
     capturable off) takes the same path with the engine's Adam update; exp_avg / exp_avg_sq / step travel like the momentum buffers."""
-    from ta3n_amd.engine import TrainEngine, flags_from_options, pretrain_refusal
+    from ta3n_amd.engine import TrainEngine, flags_from_options
+    from ta3n_amd.options import first_refusal, refusal
     m = model.module
     needed = ("frame_aggregation", "dis_DA", "ens_DA", "use_bn", "save_attention", "add_loss_DA", "use_attn", "use_target", "place_adv", "adv_DA",
               "batch_size", "num_segments", "fc_dim", "dropout_i", "dropout_v", "clip_gradient", "no_partialbn", "print_freq", "lr_adaptive", "epochs")
@@ -226,30 +227,23 @@ def _fast_engine(model, optimizer, num_class, criterion=None, criterion_domain=N
         return None      # (source / target batch mixing of domainAlign: the module path says what it does not build)
     if args.add_loss_DA == "attentive_entropy" and args.use_attn != "none" and args.use_target != "none" and list(args.place_adv) != ["Y"] * 3:
         return None      # (:560 indexes the FILTERED list of domain predictions: entry 1 is the video level only when all three are on)
-    add_fc = int(getattr(args, "add_fc", 1))      # --add_fc 2 / 3: the stacked shared layers are part of the engine's step (use_bn none, no dis_DA / MCD)
-    if add_fc != 1 and (dis or mcd or args.use_bn != "none" or add_fc not in (2, 3)):
+    # --add_fc 2 / 3, --use_attn_frame TransAttn, --use_attn general, --share_params N: on the engine where options.FEATURES builds them
+    # together with the rest (each alone, on its own launch lists), otherwise the module path
+    add_fc, attn_frame = int(getattr(args, "add_fc", 1)), getattr(args, "use_attn_frame", "none")
+    attn_general, unshared = args.use_attn == "general", getattr(args, "share_params", "Y") == "N"
+    built_with = dict(add_fc=add_fc, use_attn_frame=attn_frame, use_attn=args.use_attn, share_params="N" if unshared else "Y",
+                      frame_aggregation=args.frame_aggregation, dis_DA=args.dis_DA, ens_DA=args.ens_DA, use_bn=args.use_bn)
+    if first_refusal(("add_fc", "frame_attn", "general_attn", "share_params"), built_with)[1]:
         return None
-    # --use_attn_frame TransAttn: the engine's unfused launch lists with the two frame-attention launches (with --use_attn TransAttn, alone)
-    attn_frame = getattr(args, "use_attn_frame", "none")
-    if attn_frame != "none" and (attn_frame != "TransAttn" or args.use_attn != "TransAttn" or dis or mcd or args.use_bn != "none" or add_fc != 1):
-        return None
-    # --use_attn general: the engine's unfused launch lists with the two general-attention launches (alone: general_attn_refusal)
-    attn_general = args.use_attn == "general"
-    if attn_general and (attn_frame != "none" or dis or mcd or args.use_bn != "none" or add_fc != 1):
-        return None
-    # --share_params N: the engine's plain unfused launch lists with five GEMMs cut at the domain boundary (alone: share_params_refusal)
-    unshared = getattr(args, "share_params", "Y") == "N"
-    if unshared and (attn_frame != "none" or attn_general or dis or mcd or args.use_bn != "none" or add_fc != 1 or
-                     min(args.batch_size[0], args.batch_size[1]) < 1):
+    if unshared and min(args.batch_size[0], args.batch_size[1]) < 1:
         return None
     # --weighted_class_loss / --weighted_class_loss_DA: the engine takes the weights the two criteria carry (:160-167, 205-206)
     class_w, domain_w = _criterion_weights(criterion, num_class), _criterion_weights(criterion_domain, 2)
     # --pretrain_source: the engine's source-only pass (a second plan on the step's parameter layout + ta3n_sgd_live) where it is built
     pretrain = bool(getattr(args, "pretrain_source", False))
     if pretrain:
-        refused = pretrain_refusal(optimizer="Adam" if adam else "SGD", dis_DA=args.dis_DA if args.use_target != "none" else "none",
-                                   ens_DA=args.ens_DA if args.use_target != "none" else "none", use_attn=args.use_attn, use_attn_frame=attn_frame,
-                                   share_params="N" if unshared else "Y", add_fc=add_fc, use_bn=args.use_bn if args.use_target != "none" else "none")
+        no_target = dict(dis_DA="none", ens_DA="none", use_bn="none") if args.use_target == "none" else {}      # (as main() builds the model)
+        refused = refusal("pretrain", dict(built_with, optimizer="Adam" if adam else "SGD", **no_target))[1]
         if refused:
             if not m.__dict__.get("_pretrain_said"):
                 m.__dict__["_pretrain_said"] = True

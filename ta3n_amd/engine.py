@@ -19,6 +19,9 @@ import torch
 
 from . import _lib
 from . import parallel
+# which options are built together: the table (options.FEATURES) and its bindings, importable from here as they always were
+from .options import (add_fc_refusal, adam_refusal, frame_attn_refusal, general_attn_refusal, pretrain_refusal, refusal,  # noqa: F401
+                      share_params_refusal, target_refusal, weights_refusal, weights_refusal_kind, world_refusal)
 
 ALL_FLAGS = (_lib.FLAG_ADV_RELATION | _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_ATTN_ENTROPY |
              _lib.FLAG_TRANS_ATTN)
@@ -40,11 +43,11 @@ def flags_from_options(place_adv: Sequence[str] = ("Y", "Y", "Y"), add_loss_DA: 
         f |= _lib.FLAG_ATTN_ENTROPY
     if use_attn == "TransAttn":
         f |= _lib.FLAG_TRANS_ATTN
-    if use_attn == "general":              # models.py:320-325, 359-366 (with which other options it is built: general_attn_refusal)
+    if use_attn == "general":              # models.py:320-325, 359-366 (with which other options it is built: options.FEATURES["general_attn"])
         f |= _lib.FLAG_GENERAL_ATTN
     if use_attn_frame not in ("none", "TransAttn"):      # the bit means TransAttn; no other kind may turn into it silently
         raise ValueError(frame_attn_refusal(use_attn_frame))
-    if use_attn_frame == "TransAttn":      # (with which other options it is built: frame_attn_refusal)
+    if use_attn_frame == "TransAttn":      # (with which other options it is built: options.FEATURES["frame_attn"])
         f |= _lib.FLAG_FRAME_ATTN
     if use_target == "Sv":                 # main.py:439-446: the class CE over source + target rows (everything else as under uSv)
         f |= _lib.FLAG_TARGET_LABELS
@@ -94,152 +97,10 @@ def _update_scalars(eng, lr: float):
     return float(lr), float(eng.momentum), float(eng.weight_decay), _clip_value(eng.clip)
 
 
-def add_fc_refusal(add_fc: int, use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", chain: bool = False, split_k: int = 0,
-                   wgrads_late: bool = False, phase_tiles: bool = False) -> str:
-    """'' when --add_fc `add_fc` is built together with the other options, otherwise the message that refuses it (naming the
-    combination).  add_fc 2 / 3: TA3N / trn-m and TemPooling with use_bn none, no dis_DA / ens_DA, the default launch shapes."""
-    if add_fc < 1:
-        return "add at least one fc layer (models.py:137-138)"
-    if add_fc > 3:
-        return (f"--add_fc {add_fc}: built for 1, 2 and 3 (the reference builds no fourth layer, models.py:145-153, but shifts the "
-                f"place_dis slicing with add_fc, main.py:368-378)")
-    if add_fc == 1:
-        return ""
-    other = [what for what, on in ((f"--use_bn {use_bn}", use_bn != "none"), (f"--dis_DA {dis_DA}", dis_DA != "none"),
-                                   (f"--ens_DA {ens_DA}", ens_DA != "none"), ("chained launches (chain)", chain),
-                                   ("split_k", bool(split_k)), ("wgrads_late", wgrads_late),
-                                   ("explicit phase_tiles / tuned tile lists", phase_tiles)) if on]
-    return f"--add_fc {add_fc} together with {', '.join(other)} is not built" if other else ""
-
-
-def frame_attn_refusal(use_attn_frame: str, use_attn: str = "TransAttn", frame_aggregation: str = "trn-m", add_fc: int = 1,
-                       use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", f32_split: bool = False, chain: bool = False,
-                       split_k: int = 0, wgrads_late: bool = False) -> str:
-    """'' when --use_attn_frame `use_attn_frame` is built together with the other options, otherwise the message that refuses it
-    (naming the combination).  Built: TransAttn together with --use_attn TransAttn on trn-m (models.py:368-377, 612-614), fp32 and bf16."""
-    if use_attn_frame == "none":
-        return ""
-    if use_attn_frame != "TransAttn":
-        return f"--use_attn_frame {use_attn_frame}: built for TransAttn (the reference's 'general' frame attention needs an attn_layer its model never creates for frames)"
-    if frame_aggregation != "trn-m":
-        return f"--use_attn_frame TransAttn on --frame_aggregation {frame_aggregation}: built for trn-m (frame attention in front of the TRN)"
-    if use_attn != "TransAttn":
-        return (f"--use_attn_frame TransAttn with --use_attn {use_attn}: the reference takes the kind of frame attention from --use_attn "
-                f"(models.py:369-372; with use_attn none it raises UnboundLocalError) - built with --use_attn TransAttn")
-    other = [what for what, on in ((f"--add_fc {add_fc}", add_fc != 1), (f"--use_bn {use_bn}", use_bn != "none"),
-                                   (f"--dis_DA {dis_DA}", dis_DA != "none"), (f"--ens_DA {ens_DA}", ens_DA != "none"),
-                                   ("f32_split", f32_split), ("chained launches (chain)", chain), ("split_k", bool(split_k)),
-                                   ("wgrads_late", wgrads_late)) if on]
-    return f"--use_attn_frame TransAttn together with {', '.join(other)} is not built" if other else ""
-
-
-def _rank_schedules(world: int, process_group: bool, ddp_selftest: bool, sharded_update: bool = False, peer_exchange: bool = False):
-    """The names of the multi-rank schedules that are on, as every refusal of a single-rank option lists them."""
-    return [w for w, on in ((f"world size {world} (a process group)", world > 1 or process_group),
-                            ("the 1-rank self-test of the data-parallel path (TA3N_DDP_SELFTEST)", ddp_selftest),
-                            ("the sharded update (sharded_update / TA3N_DDP_SHARDED)", sharded_update),
-                            ("the peer gradient exchange (peer_exchange / TA3N_DDP_PEER)", peer_exchange)) if on]
-
-
-def general_attn_refusal(use_attn: str = "general", frame_aggregation: str = "trn-m", use_attn_frame: str = "none", add_fc: int = 1,
-                         use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", f32_split: bool = False, chain: bool = False,
-                         split_k: int = 0, wgrads_late: bool = False, phase_tiles: bool = False, world: int = 1, process_group: bool = False,
-                         ddp_selftest: bool = False, sharded_update: bool = False, peer_exchange: bool = False) -> str:
-    """'' when --use_attn `use_attn` is not 'general' or is built together with the other options, otherwise the message that refuses it
-    (naming the combination).  Built: conventional attention over the relation features of trn-m (models.py:320-325, 359-366, 379-388),
-    fp32 and bf16, SGD and Adam, on one rank: the unfused launch lists with two attention launches in place of the pooling launches."""
-    if use_attn != "general":
-        return ""
-    if frame_aggregation != "trn-m":
-        return (f"--use_attn general on --frame_aggregation {frame_aggregation}: built for trn-m (the reference's aggregate_frames ignores "
-                f"use_attn on avgpool)")
-    other = [what for what, on in ((f"--use_attn_frame {use_attn_frame} (the reference sends 'general' frame attention to a 256-wide layer on "
-                                    f"fc_dim-wide rows)", use_attn_frame != "none"),
-                                   (f"--add_fc {add_fc}", add_fc != 1), (f"--use_bn {use_bn}", use_bn != "none"),
-                                   (f"--dis_DA {dis_DA}", dis_DA != "none"), (f"--ens_DA {ens_DA}", ens_DA != "none"),
-                                   ("f32_split", f32_split), ("chained launches (chain)", chain), ("split_k", bool(split_k)),
-                                   ("wgrads_late", wgrads_late), ("explicit phase_tiles / tuned tile lists", phase_tiles)) if on]
-    other += _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
-    return f"--use_attn general together with {', '.join(other)} is not built (single rank, the unfused launch lists)" if other else ""
-
-
-def share_params_refusal(share_params: str = "N", frame_aggregation: str = "trn-m", use_attn: str = "TransAttn", use_attn_frame: str = "none",
-                         add_fc: int = 1, use_bn: str = "none", dis_DA: str = "none", ens_DA: str = "none", f32_split: bool = False,
-                         chain: bool = False, split_k: int = 0, wgrads_late: bool = False, phase_tiles: bool = False, world: int = 1,
-                         process_group: bool = False, ddp_selftest: bool = False, sharded_update: bool = False,
-                         peer_exchange: bool = False) -> str:
-    """'' when --share_params `share_params` is 'Y' or 'N' is built together with the other options, otherwise the message that refuses it
-    (naming the combination).  Built: the target rows' own first frame layer and video classifier on trn-m (models.py:174-192, 296-305,
-    565-566, 686-687), use_attn TransAttn or none, fp32 and bf16, SGD and Adam, the weighted criteria, Sv and the entropy terms, any
-    place_adv, on one rank: the plain unfused launch lists with five of their GEMMs cut at the domain boundary."""
-    if share_params == "Y":
-        return ""
-    if share_params != "N":
-        return f"--share_params {share_params} (built: Y, N)"
-    if frame_aggregation != "trn-m":
-        return f"--share_params N on --frame_aggregation {frame_aggregation}: built for trn-m (the unfused launch lists)"
-    other = [what for what, on in ((f"--use_bn {use_bn}", use_bn != "none"), (f"--dis_DA {dis_DA}", dis_DA != "none"),
-                                   (f"--ens_DA {ens_DA}", ens_DA != "none"), (f"--add_fc {add_fc}", add_fc != 1),
-                                   (f"--use_attn_frame {use_attn_frame}", use_attn_frame != "none"),
-                                   (f"--use_attn {use_attn}", use_attn not in ("TransAttn", "none")),
-                                   ("f32_split", f32_split), ("chained launches (chain)", chain), ("split_k", bool(split_k)),
-                                   ("wgrads_late", wgrads_late), ("explicit phase_tiles / tuned tile lists", phase_tiles)) if on]
-    other += _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
-    return f"--share_params N together with {', '.join(other)} is not built (single rank, the unfused launch lists)" if other else ""
-
-
-def adam_refusal(world: int = 1, sharded_update: bool = False, process_group: bool = False, ddp_selftest: bool = False,
-                 peer_exchange: bool = False, fused_update: bool = False, side_update: bool = False, capture: bool = False,
-                 two_stream: bool = False) -> str:
-    """'' when optimizer="Adam" is built together with the named schedule, otherwise the message that refuses it.  Adam is one launch over
-    the flat prefix behind the step's gradients on one rank; every schedule below is a way of splitting or moving the SGD update."""
-    what = _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange) + [
-        w for w, on in (("fused_update=True (the Nesterov update inside the gradient tiles, TA3N_FUSED_UPDATE)", fused_update),
-                        ("the side-stream / side-workgroup update (TA3N_SIDE_UPDATE)", side_update),
-                        ("capture() (a hipGraph would freeze the step count of the bias corrections)", capture),
-                        ("the two-stream multi-job call (ta3n_train_steps_multi)", two_stream)) if on]
-    return f"optimizer Adam together with {', '.join(what)} is not built (Adam: single rank, the update as one launch behind the step)" if what else ""
-
-
-def target_refusal(use_target: str = "none", add_loss_DA: str = "none", world: int = 1, process_group: bool = False,
-                   ddp_selftest: bool = False, sharded_update: bool = False, peer_exchange: bool = False, ens_DA: str = "none") -> str:
-    """'' when --use_target Sv / --add_loss_DA target_entropy are built together with the named schedule, otherwise the message that refuses
-    them.  Both are means over this rank's rows with labels this rank holds (TA3N_FLAG_TARGET_LABELS / TA3N_FLAG_TARGET_ENTROPY): single rank."""
-    opts = [o for o, on in (("--use_target Sv", use_target == "Sv"),
-                            ("--add_loss_DA target_entropy", add_loss_DA == "target_entropy" and use_target != "none")) if on]
-    if not opts:
-        return ""
-    what = _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
-    if ens_DA == "MCD":
-        what.append("--ens_DA MCD (under Sv the reference itself fails at main.py:448; target entropy on MCD's rebound out_target is not built)")
-    return f"{' / '.join(opts)} together with {', '.join(what)} is not built (target labels and target entropy: single rank)" if what else ""
-
-
 # what the source-only pass of --pretrain_source drops from the step's flags (reference main.py:388-414: criterion(out_source, label_source)
 # and nothing else - no target row, no adversarial, entropy or discrepancy term)
 PRETRAIN_DROPPED_FLAGS = (_lib.FLAG_ADV_RELATION | _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_ATTN_ENTROPY |
                           _lib.FLAG_TARGET_LABELS | _lib.FLAG_TARGET_ENTROPY)
-
-
-def pretrain_refusal(optimizer: str = "SGD", dis_DA: str = "none", ens_DA: str = "none", use_attn: str = "TransAttn",
-                     use_attn_frame: str = "none", share_params: str = "Y", add_fc: int = 1, use_bn: str = "none", f32_split: bool = False,
-                     feeds: bool = False, capture: bool = False, fused_update: bool = False, multi_step: bool = False, world: int = 1,
-                     process_group: bool = False, ddp_selftest: bool = False, sharded_update: bool = False, peer_exchange: bool = False) -> str:
-    """'' when TrainEngine(pretrain_source=True) - the source-only pass of --pretrain_source in front of every step, as a second plan on
-    the step's parameter layout with an update of its own live ranges (ta3n_sgd_live) - is built together with the named options,
-    otherwise the message that refuses it.  Built: trn-m with use_attn TransAttn / none and avgpool, fp32 and bf16 (twins), SGD, one rank."""
-    what = [w for w, on in (
-        ("optimizer Adam (torch keeps a step count per parameter - the parameters the pass does not reach fall behind; the engine keeps one)",
-         optimizer == "Adam"),
-        (f"--dis_DA {dis_DA}", dis_DA != "none"), (f"--ens_DA {ens_DA}", ens_DA != "none"),
-        (f"--use_attn_frame {use_attn_frame}", use_attn_frame != "none"), (f"--use_attn {use_attn}", use_attn not in ("TransAttn", "none")),
-        ("--share_params N", share_params == "N"), (f"--add_fc {add_fc}", int(add_fc) != 1), (f"--use_bn {use_bn}", use_bn != "none"),
-        ("f32_split (f32x3)", f32_split), ("train_steps(feeds=...)", feeds),
-        ("train_steps / the deferred and pipelined steps (the pass is not part of the multi-step calls)", multi_step),
-        ("capture()", capture), ("fused_update", fused_update)) if on]
-    what += _rank_schedules(world, process_group, ddp_selftest, sharded_update, peer_exchange)
-    return (f"pretrain_source together with {', '.join(what)} is not built (the source-only pass: trn-m with use_attn TransAttn / none or "
-            f"avgpool, fp32 or bf16, SGD, add_fc 1, use_bn none, single rank, one step per call)") if what else ""
 
 
 def class_weights_from_list(list_file: str, num_class: int):
@@ -276,38 +137,6 @@ def domain_factors(domain_weights: Optional[Sequence[float]], n_source: int, n_t
     return ws_ * (n_source + n_target) / den, wt_ * (n_source + n_target) / den
 
 
-def weights_refusal(class_weights=None, domain_weights=None, num_class: int = 0, world: int = 1, process_group: bool = False,
-                    ddp_selftest: bool = False) -> str:
-    """The message of weights_refusal_kind (''  when nothing is refused)."""
-    return weights_refusal_kind(class_weights, domain_weights, num_class=num_class, world=world, process_group=process_group,
-                                ddp_selftest=ddp_selftest)[1]
-
-
-def weights_refusal_kind(class_weights=None, domain_weights=None, num_class: int = 0, world: int = 1, process_group: bool = False,
-                         ddp_selftest: bool = False):
-    """(exception type, message): (None, '') when the weighted criteria (class_weights: --weighted_class_loss, domain_weights: --weighted_class_loss_DA) are built as asked,
-    otherwise the message that refuses them.  The class weights' normaliser sum_j w[y_j] is taken by the kernels over the rank's own rows:
-    single rank.  The domain factors are formed from the global counts: any world.  ValueError: a value that no configuration
-    accepts; NotImplementedError: a combination that is not built."""
-    if class_weights is not None:
-        w = [float(v) for v in class_weights]
-        if len(w) != num_class:
-            return ValueError, f"class_weights has {len(w)} entries for {num_class} classes"
-        if any(not (v > 0.0 and math.isfinite(v)) for v in w):
-            return ValueError, "class_weights must be positive and finite (1 / class_freq, main.py:164)"
-        what = _rank_schedules(world, process_group, ddp_selftest)
-        if what:
-            return NotImplementedError, (f"class_weights together with {', '.join(what)} is not built (the weighted mean divides by the sum of the weights of the "
-                    f"rank's own labels: single rank)")
-    if domain_weights is not None:
-        d = [float(v) for v in domain_weights]
-        if len(d) != 2:
-            return ValueError, f"domain_weights has {len(d)} entries, takes (w_source, w_target)"
-        if any(not (v > 0.0 and math.isfinite(v)) for v in d):
-            return ValueError, "domain_weights must be positive and finite (1 / num_source_train, 1 / num_target_train; main.py:167)"
-    return None, ""
-
-
 # What TrainEngine's arguments and the TA3N_* environment settle about an engine, once, at construction (_resolve_switches says what each is)
 _Switches = namedtuple("_Switches", "ddp_selftest sharded_update peer_exchange peer_exchange_arg grad_bf16 ddp_buckets ddp_native split_k "
                                     "chain_given chain_arg chain_env phase_tiles_env cost_model side_update native_mcd native_discrepancy "
@@ -319,11 +148,14 @@ def _resolve_switches(sharded_update: Optional[bool] = None, peer_exchange: Opti
                       env: Optional[Mapping[str, str]] = None) -> _Switches:
     """Every switch TrainEngine takes as an argument and / or from the environment (default: os.environ), read in this one place: an
     argument that is not None wins over its variable.  Pure: no device, no plan.
-    Two places see a switch in another form than the engine runs with, and keep doing so (changing either changes which calls are refused):
-      - adam_refusal sees peer_exchange_arg, not peer_exchange: TA3N_DDP_PEER=1 in the environment does not refuse a single-rank Adam
-        engine (on one rank without the self-test no exchange is set up at all), peer_exchange=True does.  target_refusal sees peer_exchange.
-      - add_fc_refusal and frame_attn_refusal see chain_arg, not the TA3N_CHAIN default: that default is itself off for add_fc > 1 and
-        for frame attention (TrainEngine._create_plan), so only a chain that was asked for by argument is refused there."""
+    Two places see a switch in another form than the engine runs with, and keep doing so (changing either changes which calls are refused);
+    both are the `reads` entry of a row of options.FEATURES:
+      - the "adam" row reads peer_exchange through peer_exchange_arg: TA3N_DDP_PEER=1 in the environment does not refuse a single-rank
+        Adam engine (on one rank without the self-test no exchange is set up at all), peer_exchange=True does.  Every other row ("target",
+        ...) sees the resolved peer_exchange.
+      - the "add_fc", "frame_attn", "general_attn" and "share_params" rows read chain through chain_arg, not the TA3N_CHAIN default:
+        that default is itself off for every one of them (TrainEngine._create_plan), so only a chain that was asked for by argument is
+        refused there."""
     env = os.environ if env is None else env
 
     def either(arg, name):
@@ -373,23 +205,11 @@ class TrainEngine:
                  class_weights: Optional[Sequence[float]] = None, domain_weights: Optional[Sequence[float]] = None,
                  share_params: str = "Y", pretrain_source: bool = False):
         sw = self._switches = _resolve_switches(sharded_update, peer_exchange, grad_transport, ddp_buckets, split_k, chain)
-        flags, fused, world_checks = self._check_options(
+        flags, fused, features, context = self._check_options(
             sw, flags=flags, fused=fused, num_class=num_class, process_group=process_group, optimizer=optimizer, betas=betas, eps=eps,
             class_weights=class_weights, domain_weights=domain_weights, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, place_dis=place_dis,
             alpha=alpha, ens_DA=ens_DA, mu=mu, aggregation=aggregation, wgrads_late=wgrads_late, phase_tiles=phase_tiles,
-            f32_split=f32_split, bf16=bf16, bf16_store=bf16_store, share_params=share_params)
-        # --pretrain_source (reference main.py:388-414): a source-only pass with an optimiser step of its own in front of every step
-        self.pretrain_source = bool(pretrain_source)
-        if self.pretrain_source:
-            kw = dict(optimizer=optimizer, dis_DA=dis_DA, ens_DA=ens_DA, use_attn="general" if flags & _lib.FLAG_GENERAL_ATTN else "TransAttn",
-                      use_attn_frame="TransAttn" if flags & _lib.FLAG_FRAME_ATTN else "none",
-                      share_params="N" if flags & _lib.FLAG_UNSHARED else "Y", add_fc=add_fc, use_bn=use_bn, f32_split=bool(f32_split),
-                      process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
-                      peer_exchange=sw.peer_exchange)
-            refused = pretrain_refusal(**kw)
-            if refused:
-                raise NotImplementedError(refused)
-            world_checks.append((pretrain_refusal, kw))
+            f32_split=f32_split, bf16=bf16, bf16_store=bf16_store, share_params=share_params, pretrain_source=pretrain_source)
         if not torch.cuda.is_available():
             raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -406,11 +226,10 @@ class TrainEngine:
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(process_group)
             self.rank = torch.distributed.get_rank(process_group)
-        if self.world > 1:      # the single-rank options, asked again, with the arguments of the first time, now that the world size is known
-            for refusal, kw in world_checks:
-                refused = refusal(world=self.world, **kw)
-                if refused:
-                    raise NotImplementedError(refused)
+        if self.world > 1:      # the single-rank options, asked again in the context of the first time, now that the world size is known
+            kind, refused = world_refusal(features, context, self.world)
+            if refused:
+                raise kind(refused)
         # The DA options under more than one rank follow what the reference's nn.DataParallel does with them (main.py:79): the discrepancy
         # loss is taken on the gathered global batch (discrepancy()); MCD's discrepancy is a mean over the global target batch
         # (mcd_second_forward()); BatchNorm statistics are PER REPLICA - each replica normalises its own slice of the batch with its own
@@ -427,34 +246,42 @@ class TrainEngine:
 
     def _check_options(self, sw: "_Switches", *, flags, fused, num_class, process_group, optimizer, betas, eps, class_weights, domain_weights,
                        add_fc, use_bn, dis_DA, place_dis, alpha, ens_DA, mu, aggregation, wgrads_late, phase_tiles, f32_split, bf16, bf16_store,
-                       share_params="Y"):
+                       share_params="Y", pretrain_source=False):
         """Refuses what is not built and composes the plan's flags from the options; touches no device and no plan.  Returns (flags,
-        fused, world_checks): world_checks are the (refusal, arguments) of the single-rank options, which the constructor asks again
-        with the world size once it knows it (Adam's first: the order in which they win over each other)."""
-        world_checks = []
+        fused, features, context): the features that are on (rows of options.FEATURES) and the one context all of them were asked in,
+        which the constructor asks again with the world size once it knows it (options.world_refusal)."""
+        if flags is None:        # default: the full TA3N configuration for trn-m, the source-only one (BASELINE configs[0]) for avgpool
+            flags = ALL_FLAGS if aggregation == "trn-m" else 0
+        context = dict(
+            class_weights=class_weights, domain_weights=domain_weights, num_class=num_class, optimizer=optimizer, add_fc=add_fc,
+            use_target="Sv" if flags & _lib.FLAG_TARGET_LABELS else "uSv",
+            add_loss_DA="target_entropy" if flags & _lib.FLAG_TARGET_ENTROPY else "none",
+            share_params="N" if flags & _lib.FLAG_UNSHARED else share_params,
+            use_attn="general" if flags & _lib.FLAG_GENERAL_ATTN else "TransAttn" if flags & _lib.FLAG_TRANS_ATTN else "none",
+            use_attn_frame="TransAttn" if flags & _lib.FLAG_FRAME_ATTN else "none", frame_aggregation=aggregation, use_bn=use_bn,
+            dis_DA=dis_DA, ens_DA=ens_DA, f32_split=bool(f32_split), chain=sw.chain_arg if sw.chain_given else sw.chain_env,
+            chain_arg=sw.chain_arg, split_k=sw.split_k, wgrads_late=bool(wgrads_late),
+            phase_tiles=bool(phase_tiles and any(phase_tiles)) or bool(sw.phase_tiles_env), process_group=process_group is not None,
+            ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update, peer_exchange=sw.peer_exchange,
+            peer_exchange_arg=sw.peer_exchange_arg)
+        features = []
 
-        def refuse(refusal, first: bool = False, **kw):
-            refused = refusal(**kw)
+        def ask(feature):
+            kind, refused = refusal(feature, context)
             if refused:
-                raise NotImplementedError(refused)
-            world_checks.insert(0 if first else len(world_checks), (refusal, kw))
+                raise kind(refused)
+            features.append(feature)
         # --weighted_class_loss / --weighted_class_loss_DA (reference main.py:156-167, 205-206): the two criteria as CrossEntropyLoss(weight=...).
         # class_weights: TA3N_FLAG_CLASS_WEIGHTS and the C weights in workspace region "class_w" - every class cross-entropy of the step, MCD's
         # second classifier and the validation metrics divide by the sum of the weights of the batch's labels, formed inside the kernels.
         # domain_weights (w_s, w_t): two per-step factors in ta3n_hyper.dom_k, from the step's global valid counts (set_hyper).
-        kw = dict(class_weights=class_weights, domain_weights=domain_weights, num_class=num_class, process_group=process_group is not None,
-                  ddp_selftest=sw.ddp_selftest)
-        kind, refused = weights_refusal_kind(**kw)
-        if kind is not None:
-            raise kind(refused)
-        world_checks.append((weights_refusal, kw))
+        ask("class_weights")
+        ask("domain_weights")
         # --use_target Sv (TA3N_FLAG_TARGET_LABELS in `flags`: the class CE over both halves, set_batch(..., target_label=...)) and
         # --add_loss_DA target_entropy (TA3N_FLAG_TARGET_ENTROPY: gamma * mean entropy of the valid target rows); flags_from_options sets them
-        self.target_labels = bool((flags or 0) & _lib.FLAG_TARGET_LABELS)
-        self.target_entropy = bool((flags or 0) & _lib.FLAG_TARGET_ENTROPY)
-        refuse(target_refusal, use_target="Sv" if self.target_labels else "uSv", add_loss_DA="target_entropy" if self.target_entropy else "none",
-               process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
-               peer_exchange=sw.peer_exchange, ens_DA=ens_DA)
+        self.target_labels = bool(flags & _lib.FLAG_TARGET_LABELS)
+        self.target_entropy = bool(flags & _lib.FLAG_TARGET_ENTROPY)
+        ask("target")
         self.class_weights = None if class_weights is None else tuple(float(v) for v in class_weights)
         self.domain_weights = None if domain_weights is None else (float(domain_weights[0]), float(domain_weights[1]))
         # --optimizer Adam (reference main.py:84-86): clip + torch.optim.Adam as ONE launch over the flat live prefix behind the step's
@@ -465,21 +292,14 @@ class TrainEngine:
         self.optimizer = optimizer
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         if optimizer == "Adam":
-            refuse(adam_refusal, first=True, sharded_update=sw.sharded_update, process_group=process_group is not None,
-                   ddp_selftest=sw.ddp_selftest, peer_exchange=sw.peer_exchange_arg)
+            ask("adam")
             if not (0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0) or self.eps < 0.0:
                 raise ValueError(f"Adam: betas {self.betas} must be in [0, 1) and eps {self.eps} >= 0 (torch.optim.Adam's own checks)")
         # --add_fc 2 / 3 (models.py:145-153, 581-603): one or two more Linear(F, F) -> ReLU -> dropout_i layers on the shared frame FC
         # (ta3n_config.shared_fc_layers: one more GEMM launch per layer in the forward and in the backward).  Built for use_bn none without
         # the discrepancy / MCD terms, on the measured default launch shapes (the tuned tile lists are indexed by the one-layer order).
-        add_fc_refused = add_fc_refusal(add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA, chain=sw.chain_arg, split_k=sw.split_k,
-                                        wgrads_late=bool(wgrads_late),
-                                        phase_tiles=bool(phase_tiles and any(phase_tiles)) or bool(sw.phase_tiles_env))
-        if add_fc_refused:
-            raise NotImplementedError(add_fc_refused) if add_fc >= 1 else ValueError(add_fc_refused)
+        ask("add_fc")
         self.add_fc = int(add_fc)
-        if flags is None:        # default: the full TA3N configuration for trn-m, the source-only one (BASELINE configs[0]) for avgpool
-            flags = ALL_FLAGS if aggregation == "trn-m" else 0
         if self.class_weights is not None:
             flags |= _lib.FLAG_CLASS_WEIGHTS
         # share_params N (the argument, or TA3N_FLAG_UNSHARED in `flags`; models.py:174-192, 296-305, 565-566, 686-687): the target rows go through
@@ -490,13 +310,7 @@ class TrainEngine:
             flags |= _lib.FLAG_UNSHARED
         self.unshared = bool(flags & _lib.FLAG_UNSHARED)
         if self.unshared or share_params != "Y":
-            refuse(share_params_refusal, share_params="N" if self.unshared else share_params, frame_aggregation=aggregation,
-                   use_attn="general" if flags & _lib.FLAG_GENERAL_ATTN else "TransAttn",
-                   use_attn_frame="TransAttn" if flags & _lib.FLAG_FRAME_ATTN else "none", add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA,
-                   ens_DA=ens_DA, f32_split=bool(f32_split), chain=sw.chain_arg, split_k=sw.split_k, wgrads_late=bool(wgrads_late),
-                   phase_tiles=bool(phase_tiles and any(phase_tiles)) or bool(sw.phase_tiles_env),
-                   process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
-                   peer_exchange=sw.peer_exchange)
+            ask("share_params")
             fused = False
         # use_attn general (TA3N_FLAG_GENERAL_ATTN in `flags`, flags_from_options(use_attn="general"); models.py:320-325, 359-366): the relation
         # weights are the softmax over the relations of a learned layer's scores (parameters attn_layer.0 / attn_layer.2, always live).  The
@@ -505,23 +319,14 @@ class TrainEngine:
         if self.general_attn:
             if flags & _lib.FLAG_TRANS_ATTN:
                 raise NotImplementedError("--use_attn general together with --use_attn TransAttn (TA3N_FLAG_TRANS_ATTN): two values of one option")
-            refuse(general_attn_refusal, frame_aggregation=aggregation, use_attn_frame="TransAttn" if flags & _lib.FLAG_FRAME_ATTN else "none",
-                   add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA, f32_split=bool(f32_split), chain=sw.chain_arg,
-                   split_k=sw.split_k, wgrads_late=bool(wgrads_late),
-                   phase_tiles=bool(phase_tiles and any(phase_tiles)) or bool(sw.phase_tiles_env),
-                   process_group=process_group is not None, ddp_selftest=sw.ddp_selftest, sharded_update=sw.sharded_update,
-                   peer_exchange=sw.peer_exchange)
+            ask("general_attn")
             fused = False
         # use_attn_frame TransAttn (TA3N_FLAG_FRAME_ATTN in `flags`, flags_from_options(use_attn_frame=...); models.py:368-377, 612-614): the
         # frame features enter the TRN scaled by 1 + (1 - H(frame-discriminator softmax)).  The frame discriminator's logits come before the
         # tuple products and its backward behind the TRN input gradient: the unfused launch lists with two more pointwise launches.
         self.frame_attn = bool(flags & _lib.FLAG_FRAME_ATTN)
         if self.frame_attn:
-            refused = frame_attn_refusal("TransAttn", use_attn="TransAttn" if flags & _lib.FLAG_TRANS_ATTN else "none",
-                                         frame_aggregation=aggregation, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, ens_DA=ens_DA,
-                                         f32_split=bool(f32_split), chain=sw.chain_arg, split_k=sw.split_k, wgrads_late=bool(wgrads_late))
-            if refused:
-                raise NotImplementedError(refused)
+            ask("frame_attn")
             fused = False
         # dis_DA DAN / JAN (main.py:452-505, loss.py:46-120): a discrepancy loss on the class logits (feat[0]) and / or the pooled
         # video feature (feat[1]), weighted by alpha.  It enters the step as one more gradient at those two tensors: the unfused
@@ -577,7 +382,11 @@ class TrainEngine:
         if aggregation == "avgpool":     # TemPooling: no relation features, no attention (use_attn none in the reference's script); with
             # use_target none (BASELINE configs[0]) the caller passes no adversarial flag either (flags_from_options)
             flags &= ~(_lib.FLAG_ATTN_ENTROPY | _lib.FLAG_TRANS_ATTN)
-        return flags, fused, world_checks
+        # --pretrain_source (reference main.py:388-414): a source-only pass with an optimiser step of its own in front of every step
+        self.pretrain_source = bool(pretrain_source)
+        if self.pretrain_source:
+            ask("pretrain")
+        return flags, fused, features, context
 
     def _create_plan(self, sw: "_Switches", flags: int, fused: bool, *, fc_dim, tile_config, phase_tiles, xcd_aware, wgrads_late) -> None:
         """self.plan (and self.chain, self._flags) for the checked options: the launch-shape choices, then the plan builder."""

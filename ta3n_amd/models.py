@@ -325,10 +325,11 @@ class VideoModel(nn.Module):
         if frame_aggregation == 'avgpool' and use_attn != 'none':
             unsupported.append("frame_aggregation='avgpool' with use_attn (the reference's script runs TemPooling with use_attn none)")
         if baseline_type != 'video': unsupported.append(f"baseline_type={baseline_type!r}")
+        from .options import refusal      # with which other options each of the three below is built: options.FEATURES
+        context = dict(share_params=share_params, frame_aggregation=frame_aggregation, use_attn=use_attn, use_attn_frame=use_attn_frame,
+                       add_fc=add_fc, use_bn=use_bn, ens_DA=ens_DA)
         if share_params != 'Y':           # models.py:174-192, 296-305, 565-566, 686-687: the target rows' own first frame layer and video classifier
-            from .engine import share_params_refusal
-            refused = share_params_refusal(share_params, frame_aggregation=frame_aggregation, use_attn=use_attn, use_attn_frame=use_attn_frame,
-                                           add_fc=add_fc, use_bn=use_bn, ens_DA=ens_DA)
+            refused = refusal("share_params", context)[1]
             if refused: unsupported.append(f"share_params={share_params!r} ({refused})")
         if use_bn not in ('none', 'AdaBN', 'AutoDIAL'): unsupported.append(f"use_bn={use_bn!r}")
         if use_bn != 'none' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("use_bn with this frame_aggregation")
@@ -336,14 +337,10 @@ class VideoModel(nn.Module):
         if ens_DA == 'MCD' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("ens_DA='MCD' with this frame_aggregation")
         if use_attn not in ('TransAttn', 'none', 'general'): unsupported.append(f"use_attn={use_attn!r}")
         if use_attn == 'general':         # models.py:320-325, 359-366: conventional attention over the relation features of trn-m
-            from .engine import general_attn_refusal
-            refused = general_attn_refusal(use_attn, frame_aggregation=frame_aggregation, use_attn_frame=use_attn_frame, add_fc=add_fc,
-                                           use_bn=use_bn, ens_DA=ens_DA)
+            refused = refusal("general_attn", context)[1]
             if refused: unsupported.append(f"use_attn='general' ({refused})")
         if use_attn_frame != 'none' and use_attn != 'general':      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
-            from .engine import frame_attn_refusal
-            refused = frame_attn_refusal(use_attn_frame, use_attn=use_attn, frame_aggregation=frame_aggregation, add_fc=add_fc, use_bn=use_bn,
-                                         ens_DA=ens_DA)
+            refused = refusal("frame_attn", context)[1]
             if refused: unsupported.append(f"use_attn_frame={use_attn_frame!r} ({refused})")
         if not before_softmax: unsupported.append("before_softmax=False")
         if add_fc < 1:

@@ -30,7 +30,8 @@ if ROOT not in sys.path:
 
 from ta3n_amd import checkpoint as ckpt  # noqa: E402
 from ta3n_amd import parallel  # noqa: E402
-from ta3n_amd.engine import TrainEngine, add_fc_refusal, beta_dann, flags_from_options, frame_attn_refusal, general_attn_refusal, lr_dann, share_params_refusal  # noqa: E402
+from ta3n_amd.engine import TrainEngine, beta_dann, flags_from_options, lr_dann  # noqa: E402
+from ta3n_amd.options import refusal  # noqa: E402
 from ta3n_amd.models import ARCH_FEATURE_DIM  # noqa: E402
 from ta3n_amd.opts import parser  # noqa: E402
 
@@ -45,6 +46,14 @@ def validate_options(args, module_path: bool = False) -> None:
     def need(cond, msg):
         if not cond:
             bad.append(msg)
+    # what the rows of ta3n_amd.options.FEATURES are asked in: the command line's options, once
+    context = dict(use_attn=args.use_attn, use_attn_frame=args.use_attn_frame, share_params=args.share_params, add_fc=args.add_fc,
+                   frame_aggregation=args.frame_aggregation, use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA,
+                   f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
+
+    def built(feature):
+        refused = refusal(feature, context)[1]
+        need(not refused, refused)
     need(args.baseline_type == "video", f"--baseline_type {args.baseline_type} (built: video)")
     need(args.frame_aggregation in ("trn-m", "avgpool"), f"--frame_aggregation {args.frame_aggregation} (built: trn-m, avgpool)")
     if args.frame_aggregation == "avgpool":      # TemPooling: source-only (BASELINE configs[0]) or with the RevGrad branches; no attention
@@ -95,29 +104,20 @@ def validate_options(args, module_path: bool = False) -> None:
     # --use_attn general (models.py:320-325, 359-366): main.py trains it, on the engine's unfused launch lists (single rank) or on its module path
     if module_path:
         need(args.use_attn in ("TransAttn", "none", "general"), f"--use_attn {args.use_attn} (built: TransAttn, none, general)")
-        general_msg = general_attn_refusal(args.use_attn, frame_aggregation=args.frame_aggregation, use_attn_frame=args.use_attn_frame,
-                                           add_fc=args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA,
-                                           f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
-        need(not general_msg, general_msg)
+        built("general_attn")
     else:
         need(args.use_attn in ("TransAttn", "none"), f"--use_attn {args.use_attn}" + (" (built on main.py)" if args.use_attn == "general" else ""))
     # --use_attn_frame TransAttn (models.py:368-377, 612-614): with --use_attn TransAttn on trn-m, without the options listed there
-    frame_attn_msg = "" if args.use_attn == "general" else frame_attn_refusal(args.use_attn_frame, use_attn=args.use_attn, frame_aggregation=args.frame_aggregation, add_fc=args.add_fc,
-                                        use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA,
-                                        f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
-    need(not frame_attn_msg, frame_attn_msg)
+    if args.use_attn != "general":      # (there the "general_attn" row names the frame attention)
+        built("frame_attn")
     # --share_params N (models.py:174-192, 296-305, 565-566, 686-687): main.py trains it, on the engine's unfused launch lists (single rank) or
     # on its module path
     if module_path:
-        share_msg = share_params_refusal(args.share_params, frame_aggregation=args.frame_aggregation, use_attn=args.use_attn,
-                                         use_attn_frame=args.use_attn_frame, add_fc=args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA,
-                                         ens_DA=args.ens_DA, f32_split=getattr(args, "arithmetic", "f32") == "f32x3")
-        need(not share_msg, share_msg)
+        built("share_params")
     else:
         need(args.share_params == "Y", "--share_params N (built on main.py)")
     # --add_fc 2 / 3 (models.py:145-153, 581-603): TA3N / trn-m and TemPooling with use_bn none, without dis_DA / ens_DA
-    add_fc_msg = add_fc_refusal(args.add_fc, use_bn=args.use_bn, dis_DA=args.dis_DA, ens_DA=args.ens_DA)
-    need(not add_fc_msg, add_fc_msg)
+    built("add_fc")
     need(args.modality == "RGB", f"modality {args.modality} (pre-extracted RGB features)")
     need(args.mu == 0 or args.ens_DA == "MCD", f"--mu {args.mu} (only used by --ens_DA MCD)")
     need(len(args.beta) == 3 and len(args.place_adv) == 3, "--beta and --place_adv take three values [relation, video, frame]")
