@@ -159,6 +159,13 @@ typedef enum {
                                * flags must carry no TA3N_FLAG_ADV_x / _ATTN_ENTROPY / _TRANS_ATTN bit.  The step is
                                * F1 -> mean over segments -> dropout -> classifier -> CE on the source rows -> backward;
                                * the discriminators (forwarded by the reference, feeding nothing) are not computed. */
+#define TA3N_AGG_RNN      2   /* 'rnn' (models.py:202-215, 392-422): slot max-pooling of the frame features to n_ts steps, one
+                               * LSTM / GRU layer (ta3n_config.rnn_cell), one direction, zero initial state; the video feature is
+                               * the last hidden state, F wide.  Everything else is the general TemPooling plan: the same launch
+                               * list with the two aggregator launches replaced by the recurrence, forward and backward through
+                               * time.  fp32; any TA3N_FLAG_ADV_x (also none), _FEATURE_GRADS, _CLASS_WEIGHTS, _TARGET_LABELS.
+                               * ta3n_plan_create refuses every other flag by name, shared_fc_layers > 1, chain, split_k,
+                               * wgrads_late, phase_tiles, layout_flags, and an n_ts for which ta3n_rnn_slots fails. */
 
 typedef struct {
     int32_t batch_source;    /* Bs: rows of the source half (after the reference's zero padding, main.py:359-372) */
@@ -220,6 +227,10 @@ typedef struct {
                               * the ranges of ta3n_live_range, and ta3n_sgd_live is the update (the prefix updates and the pipelined /
                               * multi-step entry points refuse such a plan by name).  ta3n_plan_create refuses by message a parameter that is
                               * live under `flags` and not under `layout_flags`, and a parameter the donor does not have. */
+    int32_t rnn_cell;        /* TA3N_AGG_RNN: 0 = LSTM (gates i, f, g, o), 1 = GRU (gates r, z, n): opts.py --rnn_cell.  Parameters
+                              * rnn.weight_ih_l0 [gF][F], rnn.weight_hh_l0 [gF][F], rnn.bias_ih_l0, rnn.bias_hh_l0 [gF], g = 4 / 3,
+                              * in the live prefix.  Ignored by the other aggregations. */
+    int32_t n_ts;            /* TA3N_AGG_RNN: number of temporal segments = recurrent steps (opts.py --n_ts); 0 means 5 */
 } ta3n_config;
 
 /* Per-step scalars; lives in device memory inside ws (region "hyper").  The host
@@ -276,6 +287,14 @@ int ta3n_relation_table(int num_frames, int32_t *tuples, int32_t *scale_len, int
 /* TSNDataSet._get_test_indices (dataset.py:103-116), 1-based frame ids.
  * Returns TA3N_ERR_INVALID where the reference raises (no selectable frame). */
 int ta3n_segment_indices(int num_frames, int num_segments, int new_length, int64_t *out);
+
+/* Temporal pooling in front of the recurrent aggregator (TA3N_AGG_RNN; models.py:397-409): len_ts = round(num_segments / n_ts)
+ * as Python rounds the float quotient (half to even), by an integer rule; slot (j, i), j < n_ts, i < len_ts, reads frame
+ * frames[j * len_ts + i] = min(j * len_ts + i, num_segments - 1) - frames past len_ts * n_ts are dropped, the last frame is
+ * repeated where there are too few.  frames (may be NULL) has room for len_ts * n_ts entries, at most num_segments + n_ts / 2.
+ * Returns TA3N_ERR_INVALID with a message where the reference fails (len_ts == 0) or an argument is out of range
+ * (num_segments in [1,64], n_ts in [1,128]).  The plan builder and the kernels use this table. */
+int ta3n_rnn_slots(int num_segments, int n_ts, int32_t *len_ts, int32_t *frames);
 
 /* TSNDataSet.__getitem__ for a whole batch on the device (dataset.py:118-144 with the test-mode sampler
  * dataset.py:103-116 - the only one main.py uses, main.py:171-197 - and new_length 1): the dataset lives in HBM

@@ -34,11 +34,12 @@ FLAG_TARGET_LABELS = 1 << 13   # --use_target Sv: the class CE over the valid ro
 FLAG_TARGET_ENTROPY = 1 << 14  # --add_loss_DA target_entropy: gamma * mean entropy of the valid target rows' class softmax; exclusive with FLAG_ATTN_ENTROPY
 FLAG_GENERAL_ATTN = 1 << 15   # use_attn general: relation weights = softmax over the relations of a learned layer's scores (parameters attn_layer.0 / .2; regions Ua, gUa, gs); unfused entry points, single rank
 FLAG_UNSHARED = 1 << 16       # share_params N: the target rows' own first frame layer and video classifier (parameters fc_*_target); unfused entry points, single rank
-AGG_TRN_M, AGG_AVGPOOL = 0, 1
+AGG_TRN_M, AGG_AVGPOOL, AGG_RNN = 0, 1, 2      # AGG_RNN: slot max-pooling + one LSTM / GRU layer (rnn_cell, n_ts)
+RNN_CELLS = {"LSTM": 0, "GRU": 1}
 
 # every symbol include/ta3n_hip.h declares (tests check the export list)
 SYMBOLS = [
-    "ta3n_num_relation_tuples", "ta3n_relation_table", "ta3n_segment_indices", "ta3n_gather_segments", "ta3n_plan_create",
+    "ta3n_num_relation_tuples", "ta3n_relation_table", "ta3n_segment_indices", "ta3n_rnn_slots", "ta3n_gather_segments", "ta3n_plan_create",
     "ta3n_plan_destroy", "ta3n_num_params", "ta3n_param_info", "ta3n_param_floats", "ta3n_live_param_floats",
     "ta3n_workspace_floats", "ta3n_ws_offset", "ta3n_ws_size", "ta3n_plan_describe", "ta3n_set_hyper",
     "ta3n_init_workspace", "ta3n_forward", "ta3n_loss", "ta3n_backward", "ta3n_has_fused_step", "ta3n_train_step", "ta3n_eval_metrics",
@@ -64,7 +65,8 @@ class Config(C.Structure):
                 ("phase_tiles", C.c_int32 * 16), ("xcd_aware", C.c_int32), ("aggregation", C.c_int32),
                 ("wgrads_late", C.c_int32), ("chain", C.c_int32), ("cost_model", C.c_int32), ("split_k", C.c_int32),
                 ("shared_fc_layers", C.c_int32),      # --add_fc (0 / 1: one shared layer)
-                ("layout_flags", C.c_uint32)]         # 0, or the flags of the configuration whose flat parameter layout this plan adopts
+                ("layout_flags", C.c_uint32),         # 0, or the flags of the configuration whose flat parameter layout this plan adopts
+                ("rnn_cell", C.c_int32), ("n_ts", C.c_int32)]      # AGG_RNN: 0 LSTM / 1 GRU; recurrent steps (0: 5)
 
 
 class Hyper(C.Structure):
@@ -126,6 +128,7 @@ def lib() -> C.CDLL:
     L.ta3n_num_relation_tuples.argtypes = [C.c_int]
     L.ta3n_relation_table.argtypes = [C.c_int, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.ta3n_segment_indices.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(i64)]
+    L.ta3n_rnn_slots.argtypes = [C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)]
     L.ta3n_gather_segments.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.ta3n_plan_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     L.ta3n_plan_destroy.argtypes = [vp]
@@ -256,13 +259,24 @@ def segment_indices(num_frames: int, num_segments: int, new_length: int = 1) -> 
     return list(out)
 
 
+def rnn_slots(num_segments: int, n_ts: int) -> Tuple[int, List[int]]:
+    """(len_ts, frame read by each of the len_ts * n_ts pooling slots) of the recurrent aggregator (reference models.py:397-409);
+    raises ValueError where the reference fails (len_ts == 0)."""
+    L = lib()
+    len_ts = C.c_int32()
+    frames = (C.c_int32 * 256)()
+    check(L.ta3n_rnn_slots(num_segments, n_ts, C.byref(len_ts), frames), "ta3n_rnn_slots")
+    return len_ts.value, list(frames[:len_ts.value * n_ts])
+
+
 class Plan:
     """Owns a ta3n_plan handle and caches its layout tables."""
 
     def __init__(self, batch_source: int, batch_target: int, num_segments: int, feature_dim: int, fc_dim: int,
                  num_class: int, flags: int, num_bottleneck: int = 256, tile_config: int = 0,
                  phase_tiles: Optional[List[int]] = None, xcd_aware: int = 0, aggregation: int = 0, wgrads_late: int = 0,
-                 chain: int = 0, cost_model: int = 0, split_k: int = 0, shared_fc_layers: int = 0, layout_flags: int = 0):
+                 chain: int = 0, cost_model: int = 0, split_k: int = 0, shared_fc_layers: int = 0, layout_flags: int = 0,
+                 rnn_cell: int = 0, n_ts: int = 0):
         L = lib()
         self.cfg = Config(batch_source, batch_target, num_segments, feature_dim, fc_dim, num_bottleneck, num_class,
                           flags, tile_config)
@@ -276,6 +290,8 @@ class Plan:
         self.cfg.split_k = int(split_k)
         self.cfg.shared_fc_layers = int(shared_fc_layers)      # --add_fc (models.py:145-153)
         self.cfg.layout_flags = int(layout_flags)              # the parameter layout of the plan these flags would give (0: its own)
+        self.cfg.rnn_cell = int(rnn_cell)                      # AGG_RNN: 0 LSTM, 1 GRU
+        self.cfg.n_ts = int(n_ts)                              # AGG_RNN: recurrent steps (0: 5)
         h = C.c_void_p()
         check(L.ta3n_plan_create(C.byref(self.cfg), C.byref(h)), "ta3n_plan_create")
         self.handle = h

@@ -106,6 +106,17 @@ int launch_general_attn(const ta3n_plan *p, int kind, const Ptrs &ptrs, hipStrea
                                        : launch_general_attn_bwd(p->geom, ptrs, o.Ua, o.gUa, o.gs, o.p_wa2, stream);
 }
 
+// the four launches of the recurrent aggregator (TA3N_AGG_RNN); a cell phase carries its step in Phase.task_begin
+int launch_rnn(const ta3n_plan *p, const Phase &ph, const Ptrs &ptrs, hipStream_t stream) {
+    if (p->rnn.n_ts <= 0) return -1;
+    switch (ph.kind) {
+        case PH_RNN_POOL_FWD: return launch_rnn_pool_fwd(p->geom, ptrs, p->rnn, stream);
+        case PH_RNN_CELL_FWD: return launch_rnn_cell_fwd(p->geom, ptrs, p->rnn, ph.task_begin, stream);
+        case PH_RNN_CELL_BWD: return launch_rnn_cell_bwd(p->geom, ptrs, p->rnn, ph.task_begin, stream);
+        default: return launch_rnn_pool_bwd(p->geom, ptrs, p->rnn, stream);
+    }
+}
+
 int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float *momentum, hipStream_t stream,
               hipEvent_t join_after_first = nullptr, int first_launch = 0, int n_launches = 1 << 30,
               const SgdSide *side = nullptr) {
@@ -139,6 +150,7 @@ int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float
             case PH_BN_BWD: rc = launch_bn_shared_bwd(p->geom, ptrs, stream); break;
             case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: rc = launch_frame_attn(p, ph.kind, ptrs, stream); break;
             case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: rc = launch_general_attn(p, ph.kind, ptrs, stream); break;
+            case PH_RNN_POOL_FWD: case PH_RNN_CELL_FWD: case PH_RNN_CELL_BWD: case PH_RNN_POOL_BWD: rc = launch_rnn(p, ph, ptrs, stream); break;
             case PH_GRAD_NORM: rc = launch_grad_norm(p->geom, ptrs.g, ptrs.ws, stream); break;
             case PH_SGD: rc = launch_sgd(p->geom, params_rw, ptrs.g, momentum, ptrs.ws, stream); break;
             default: rc = -1;
@@ -448,6 +460,7 @@ int ta3n_time_phases(ta3n_plan *p, const float *x, float *params, float *grads, 
                 case PH_BN_BWD: lrc = launch_bn_shared_bwd(p->geom, ptrs, s); break;
                 case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: lrc = launch_frame_attn(p, ph.kind, ptrs, s); break;
                 case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: lrc = launch_general_attn(p, ph.kind, ptrs, s); break;
+                case PH_RNN_POOL_FWD: case PH_RNN_CELL_FWD: case PH_RNN_CELL_BWD: case PH_RNN_POOL_BWD: lrc = launch_rnn(p, ph, ptrs, s); break;
                 case PH_GRAD_NORM: lrc = launch_grad_norm(p->geom, grads, ws, s); break;
                 case PH_SGD: lrc = launch_sgd(p->geom, params, grads, momentum, ws, s); break;
                 default: lrc = -1;

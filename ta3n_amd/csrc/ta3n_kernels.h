@@ -285,6 +285,11 @@ int launch_frame_attn_bwd(const Geom &g, const Ptrs &ptrs, int o_gF1a, int o_gFs
 int launch_general_attn_fwd(const Geom &g, const Ptrs &ptrs, int o_Ua, int p_wa2, int p_ba2, hipStream_t stream);
 int launch_general_attn_bwd(const Geom &g, const Ptrs &ptrs, int o_Ua, int o_gUa, int o_gs, int p_wa2, hipStream_t stream);
 int launch_pool_bwd(const Geom &g, const Ptrs &ptrs, hipStream_t stream);
+// TA3N_AGG_RNN (ta3n_rnn.hip): slot max-pooling and one cell step t, forward and backward
+int launch_rnn_pool_fwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, hipStream_t stream);
+int launch_rnn_cell_fwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, int t, hipStream_t stream);
+int launch_rnn_cell_bwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, int t, hipStream_t stream);
+int launch_rnn_pool_bwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, hipStream_t stream);
 int launch_grad_norm(const Geom &g, const float *grads, float *ws, hipStream_t stream);
 int launch_sgd(const Geom &g, float *params, const float *grads, float *momentum, float *ws, hipStream_t stream,
                bool fused_norm = false);

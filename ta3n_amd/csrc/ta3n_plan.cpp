@@ -435,6 +435,48 @@ struct AvgpoolDa {
     HeadParams w;
     SharedStack st;
     bool live_frm, live_vid, mcd, bn_shared;
+    // TA3N_AGG_RNN (models.py:202-215, 392-422): the two aggregator launches become the recurrence; nullptr: TemPooling
+    const RnnArgs *rnn = nullptr;
+    int64_t Wih = -1, bih = -1, Whh = -1, bhh = -1;
+
+    void add_step_phase(int kind, int group, int t) { b.add_simple_phase(kind, group); b.p.phases.back().task_begin = t; }
+
+    // Xp | Gx = Xp W_ih^T + b_ih over all n_ts B rows | per step { Gh_t = h_{t-1} W_hh^T + b_hh | cell }.  h keeps n_ts + 1 slabs with
+    // slab 0 zero, so every step has the same shape (and dW_hh is one weight gradient over all the rows)
+    void rnn_forward(int group) {
+        const int B = d.B, F = d.F, GF = (rnn->cell ? 3 : 4) * F;
+        b.add_simple_phase(PH_RNN_POOL_FWD, group);
+        b.add_gemm_phase(group, spec_linear(rnn->n_ts * B, GF, F, BASE_WS, rnn->o_Xp, F, Wih, bih, rnn->o_Gx, GF, false));
+        for (int t = 0; t < rnn->n_ts; ++t) {
+            b.add_gemm_phase(group, spec_linear(B, GF, F, BASE_WS, rnn->o_h + (int64_t)t * B * F, F, Whh, bhh, rnn->o_Gh + (int64_t)t * B * GF, GF, false));
+            add_step_phase(PH_RNN_CELL_FWD, group, t);
+        }
+    }
+
+    // t descending { cell backward | gh_{t-1} = gGh_t W_hh + its direct part } | {dW_ih, db_ih, dW_hh, db_hh, gXp} | route gXp to the frames
+    void rnn_backward(int group) {
+        const int B = d.B, F = d.F, GF = (rnn->cell ? 3 : 4) * F, rows = rnn->n_ts * B;
+        for (int t = rnn->n_ts - 1; t >= 0; --t) {
+            add_step_phase(PH_RNN_CELL_BWD, group, t);
+            if (t == 0) break;                                    // (nobody reads the gradient at the zero initial state)
+            GemmSpec gh;
+            gh.M = B; gh.N = F;
+            gh.segs.push_back(mkseg(KC(BASE_WS, rnn->o_gGh + (int64_t)t * B * GF, GF), KM(BASE_P, Whh, F), GF));
+            gh.proto = proto(BASE_WS, rnn->o_gh, F);
+            with_add(gh.proto, rnn->o_ghd, F);
+            b.add_gemm_phase(group, gh);
+        }
+        std::vector<GemmSpec> s;
+        s.push_back(spec_wgrad(GF, F, rows, rnn->o_gGx, GF, BASE_WS, rnn->o_Xp, F, Wih, bih));   // dW_ih = gGx^T Xp, db_ih
+        s.push_back(spec_wgrad(GF, F, rows, rnn->o_gGh, GF, BASE_WS, rnn->o_h, F, Whh, bhh));    // dW_hh = gGh^T h_prev (slabs 0 .. n_ts - 1), db_hh
+        GemmSpec gx;                                                                              // gXp = gGx W_ih
+        gx.M = rows; gx.N = F;
+        gx.segs.push_back(mkseg(KC(BASE_WS, rnn->o_gGx, GF), KM(BASE_P, Wih, F), GF));
+        gx.proto = proto(BASE_WS, rnn->o_gXp, F);
+        s.push_back(gx);
+        b.add_gemm_phase(group, s);
+        b.add_simple_phase(PH_RNN_POOL_BWD, group);
+    }
 
     void forward(int group) {
         const int B = d.B, BT = d.BT, F = d.F, C = d.C;
@@ -442,7 +484,7 @@ struct AvgpoolDa {
         if (bn_shared) b.add_simple_phase(PH_BN_FWD, group);
         add_stack_forward(b, st, group, BT, F);
         if (live_frm) b.add_gemm_phase(group, spec_linear(BT, F, F, BASE_WS, g.o_F1, F, w.Wfd, w.bfd, g.o_Hf, F, true));   // models.py:458-459
-        b.add_simple_phase(PH_POOL_AVG_FWD, group);
+        if (rnn) rnn_forward(group); else b.add_simple_phase(PH_POOL_AVG_FWD, group);
         {
             std::vector<GemmSpec> s{spec_linear(B, C, F, BASE_WS, g.o_Vd, F, w.Wcv, w.bcv, g.o_Y, C, false)};                     // :686
             if (mcd) s.push_back(spec_linear(B, C, F, BASE_WS, g.o_Vd, F, w.Wcv2, w.bcv2, g.o_Y2, C, false));                     // :717-718
@@ -479,7 +521,7 @@ struct AvgpoolDa {
             if (live_frm) s.push_back(spec_wgrad(F, F, BT, g.o_gHf, F, BASE_WS, g.o_F1, F, w.Wfd, w.bfd));
             b.add_gemm_phase(group, s);
         }
-        b.add_simple_phase(PH_POOL_AVG_BWD, group);
+        if (rnn) rnn_backward(group); else b.add_simple_phase(PH_POOL_AVG_BWD, group);
         if (live_frm) {   // gZ1 = ( -beta2 gHf Wfd + gVt / T ) * [F1 > 0] / keep_i
             GemmSpec gz;
             gz.M = BT; gz.N = F;
@@ -496,10 +538,34 @@ struct AvgpoolDa {
     }
 };
 
+// "" when the configuration is built on TA3N_AGG_RNN, otherwise the refusal, naming what is not built there
+std::string rnn_refusal(const ta3n_config &c) {
+    const std::pair<uint32_t, const char *> flags[] = {
+        {TA3N_FLAG_BF16_MFMA, "TA3N_FLAG_BF16_MFMA"}, {TA3N_FLAG_BF16_STORE, "TA3N_FLAG_BF16_STORE"}, {TA3N_FLAG_F32_SPLIT, "TA3N_FLAG_F32_SPLIT"},
+        {TA3N_FLAG_MCD, "TA3N_FLAG_MCD (ens_DA MCD)"}, {TA3N_FLAG_BN_SHARED, "TA3N_FLAG_BN_SHARED (use_bn)"},
+        {TA3N_FLAG_TRANS_ATTN, "TA3N_FLAG_TRANS_ATTN (use_attn TransAttn)"}, {TA3N_FLAG_ATTN_ENTROPY, "TA3N_FLAG_ATTN_ENTROPY (add_loss_DA attentive_entropy)"},
+        {TA3N_FLAG_TARGET_ENTROPY, "TA3N_FLAG_TARGET_ENTROPY (add_loss_DA target_entropy)"}, {TA3N_FLAG_FRAME_ATTN, "TA3N_FLAG_FRAME_ATTN (use_attn_frame)"},
+        {TA3N_FLAG_GENERAL_ATTN, "TA3N_FLAG_GENERAL_ATTN (use_attn general)"}, {TA3N_FLAG_UNSHARED, "TA3N_FLAG_UNSHARED (share_params N)"}};
+    const std::string head = "TA3N_AGG_RNN (frame_aggregation rnn) with ";
+    for (const auto &f : flags)
+        if (c.flags & f.first) return head + f.second + " is not built";
+    if (c.shared_fc_layers > 1) return head + "shared_fc_layers (--add_fc) " + std::to_string(c.shared_fc_layers) + " is not built";
+    if (c.chain) return head + "chain is not built";
+    if (c.split_k) return head + "split_k is not built";
+    if (c.wgrads_late) return head + "wgrads_late is not built";
+    for (int i = 0; i < 16; ++i)
+        if (c.phase_tiles[i]) return head + "phase_tiles is not built";
+    if (c.layout_flags) return head + "layout_flags is not built";
+    if (c.rnn_cell != 0 && c.rnn_cell != 1) return "rnn_cell must be 0 (LSTM) or 1 (GRU), not " + std::to_string(c.rnn_cell);
+    if (c.n_ts < 0) return "n_ts must not be negative (0 means 5), not " + std::to_string(c.n_ts);
+    return "";
+}
+
 int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     const ta3n_config &c = p.cfg;
     const Dims d = dims_of(c);
     const int B = d.B, BT = d.BT, F = d.F, C = d.C;
+    const bool is_rnn = c.aggregation == TA3N_AGG_RNN;
     if (c.flags & (TA3N_FLAG_ATTN_ENTROPY | TA3N_FLAG_TRANS_ATTN)) {
         err = "avgpool: attention / attentive entropy are not built (the reference's script switches them off with use_attn none)";
         return TA3N_ERR_INVALID;
@@ -522,6 +588,11 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     if (mcd) b.add_linear("fc_classifier_video_source_2", C, F, true); // :276-279
     if (bn_shared) add_bn_shared_params(b, F);                         // :195-196
     b.lin("fc_classifier_domain_video", 2, F, live_vid);               // :281
+    const int GF = (c.rnn_cell ? 3 : 4) * F;                           // TA3N_AGG_RNN: nn.LSTM / nn.GRU(F, F), one layer (:202-207)
+    if (is_rnn) {                                                      // (bn_before_rnn / bn_after_rnn, :213-214, are never called: no parameters of the plan)
+        b.add_param("rnn.weight_ih_l0", GF, F, true); b.add_param("rnn.weight_hh_l0", GF, F, true);
+        b.add_param("rnn.bias_ih_l0", GF, 0, true); b.add_param("rnn.bias_hh_l0", GF, 0, true);
+    }
     p.live_floats = p.param_floats;
     b.add_dead_linears();
     b.add_linear("fc_feature_source", F, F, false);
@@ -553,6 +624,32 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     g.o_gZ1 = (int32_t)b.add_region("gZ1", (int64_t)BT * F);
     AvgpoolDa m{b, g, d, w, SharedStack(), live_frm, live_vid, mcd, bn_shared};
     lay_out_stack(p, b, m.st, BT, F, g.o_F1, g.o_gZ1);
+    if (is_rnn) {
+        RnnArgs &r = p.rnn;
+        int32_t len_ts = 0, frames[RNN_MAX_SLOTS + 64];
+        r.cell = c.rnn_cell; r.n_ts = c.n_ts ? c.n_ts : 5;
+        if (ta3n_rnn_slots(d.T, r.n_ts, &len_ts, frames) != TA3N_OK) { err = ta3n_last_error(); return TA3N_ERR_INVALID; }
+        if (len_ts * r.n_ts > RNN_MAX_SLOTS) { err = "n_ts: more than 128 pooling slots"; return TA3N_ERR_INVALID; }
+        r.len_ts = len_ts;
+        for (int i = 0; i < len_ts * r.n_ts; ++i) r.frames[i] = (uint8_t)frames[i];
+        const int64_t rows = (int64_t)r.n_ts * B;
+        if (rows * GF >= (1ll << 31)) { err = "problem too large for 32-bit offsets"; return TA3N_ERR_INVALID; }
+        r.o_Xp = (int32_t)b.add_region("rnn_Xp", rows * F);
+        r.o_Gx = (int32_t)b.add_region("rnn_Gx", rows * GF);
+        r.o_Gh = (int32_t)b.add_region("rnn_Gh", rows * GF);
+        r.o_gates = (int32_t)b.add_region("rnn_gates", rows * GF);
+        r.o_c = (int32_t)b.add_region("rnn_c", (rows + B) * F);
+        r.o_h = (int32_t)b.add_region("rnn_h", (rows + B) * F);
+        r.o_gGx = (int32_t)b.add_region("rnn_gGx", rows * GF);
+        r.o_gGh = (int32_t)b.add_region("rnn_gGh", rows * GF);
+        r.o_gc = (int32_t)b.add_region("rnn_gc", rows * F);
+        r.o_gh = (int32_t)b.add_region("rnn_gh", (int64_t)B * F);
+        r.o_ghd = (int32_t)b.add_region("rnn_ghd", (int64_t)B * F);
+        r.o_gXp = (int32_t)b.add_region("rnn_gXp", rows * F);
+        m.rnn = &p.rnn;
+        m.Wih = p.poff("rnn.weight_ih_l0"); m.Whh = p.poff("rnn.weight_hh_l0");
+        m.bih = p.poff("rnn.bias_ih_l0"); m.bhh = p.poff("rnn.bias_hh_l0");
+    }
     g.o_attn = (int32_t)b.add_region("attn", 4); g.o_gattn = (int32_t)b.add_region("g_attn", 4);
     if (feat_grads) g.o_gV_ext = (int32_t)b.add_region("gV_ext", (int64_t)B * F);
     if (mcd) add_mcd_regions(b, g, d);
@@ -1302,7 +1399,11 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     const ta3n_config &c = p.cfg;
     const Dims d = dims_of(c);
     if (d.Bs < 0 || d.Bt < 0 || d.Bs + d.Bt <= 0) { err = "batch sizes must be non-negative and not both zero"; return TA3N_ERR_INVALID; }
-    if (c.aggregation != TA3N_AGG_TRN_M && c.aggregation != TA3N_AGG_AVGPOOL) { err = "aggregation must be TA3N_AGG_TRN_M or TA3N_AGG_AVGPOOL"; return TA3N_ERR_INVALID; }
+    if (c.aggregation != TA3N_AGG_TRN_M && c.aggregation != TA3N_AGG_AVGPOOL && c.aggregation != TA3N_AGG_RNN) {
+        err = "aggregation must be TA3N_AGG_TRN_M or TA3N_AGG_AVGPOOL";      // (the text tests/golden/plan_fingerprints.json pins; TA3N_AGG_RNN is the third)
+        return TA3N_ERR_INVALID;
+    }
+    if (c.aggregation == TA3N_AGG_RNN) { const std::string e = rnn_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     if (d.T < 2 || d.T > 64) { err = "num_segments must be in [2,64] for trn-m"; return TA3N_ERR_INVALID; }
     if (d.D <= 0 || d.F <= 0 || d.C <= 0) { err = "feature_dim, fc_dim and num_class must be positive"; return TA3N_ERR_INVALID; }
     if (d.NB <= 0 || d.NB % 64 != 0 || d.NB > 1024) { err = "num_bottleneck must be a multiple of 64 (<= 1024)"; return TA3N_ERR_INVALID; }
@@ -1352,6 +1453,7 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     if (c.aggregation == TA3N_AGG_TRN_M) return build_plan_trn(p, err);
     p.n_tuples = 0;      // (no relation tuples)
     p.tuple_first.assign(1, 0);
+    if (c.aggregation == TA3N_AGG_RNN) return build_plan_avgpool_general(p, err);      // (also with no flag at all: there is no source-only fast path)
     // avgpool, source-only: the fused fast path (BASELINE configs[0]); with adversarial branches or a module-path option: the general one
     const uint32_t general = TA3N_FLAG_ADV_RELATION | TA3N_FLAG_ADV_VIDEO | TA3N_FLAG_ADV_FRAME | TA3N_FLAG_MCD | TA3N_FLAG_FEATURE_GRADS |
                              TA3N_FLAG_BN_SHARED;
@@ -1359,6 +1461,24 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
 }
 
 }  // namespace
+
+// models.py:397-409.  Python's round(T / n_ts) is half-to-even on the float quotient; T <= 64 and n_ts <= 128 make every quotient with
+// fraction 1/2 exact in binary and keep every other one away from it, so the integer rule below is that rounding.
+extern "C" int ta3n_rnn_slots(int num_segments, int n_ts, int32_t *len_ts, int32_t *frames) {
+    if (num_segments < 1 || num_segments > 64) { ta3n::set_error("ta3n_rnn_slots: num_segments must be in [1,64]"); return TA3N_ERR_INVALID; }
+    if (n_ts < 1 || n_ts > 128) { ta3n::set_error("ta3n_rnn_slots: n_ts must be in [1,128]"); return TA3N_ERR_INVALID; }
+    const int q = num_segments / n_ts, r = num_segments % n_ts;
+    const int len = 2 * r < n_ts ? q : 2 * r > n_ts ? q + 1 : q + (q & 1);
+    if (len == 0) {
+        ta3n::set_error("n_ts " + std::to_string(n_ts) + " with " + std::to_string(num_segments) + " segments: len_ts = round(num_segments / n_ts) is 0 "
+                        "(the reference fails there, models.py:397-409)");
+        return TA3N_ERR_INVALID;
+    }
+    if (len_ts) *len_ts = len;
+    if (frames)
+        for (int s = 0; s < len * n_ts; ++s) frames[s] = std::min(s, num_segments - 1);
+    return TA3N_OK;
+}
 
 // Register-blocked tiles exist for launches that read bf16 twins only, and whether a launch does is known once the whole
 // plan is laid out (add_bf16_twins): build, look, and rebuild without the blocking where it cannot be used.

@@ -107,6 +107,27 @@ enum PhaseKind : int32_t {
     PH_FRAME_ATTN_BWD = 13,  // ... and back: gPfT = gPf + <gF1a, F1> dw/dPf, additive base of the gradient at F1 = (1 + attn_frame) gF1a
     PH_GENERAL_ATTN_FWD = 14,  // TA3N_FLAG_GENERAL_ATTN, in place of PH_POOL_FWD: Pr, R, A = tanh(U), attn = softmax_j(<A_j, wa2> + ba2), V, Vd
     PH_GENERAL_ATTN_BWD = 15,  // ... in place of PH_POOL_BWD: gs, gUa = gs wa2 (1 - A^2), gRa = (1 + attn) gv, gPrT = gPr, gHr
+    // TA3N_AGG_RNN (ta3n_rnn.hip; offsets in ta3n_plan::rnn).  The two cell kinds carry their step t in Phase.task_begin.
+    PH_RNN_POOL_FWD = 16,    // Xp[j][b] = max over the frames of slot window j of F1[b] (time-major), h_{-1} = c_{-1} = 0
+    PH_RNN_CELL_FWD = 17,    // step t: gates from Gx_t + Gh_t, c_t, h_t; the last step also V = h_t, Vd = dropout_v(V), loss slots = 0
+    PH_RNN_CELL_BWD = 18,    // step t: gGx_t, gGh_t, gc_{t-1}, direct part of gh_{t-1} from gh_t (last step: gVt [+ gV_ext]) and gc_t
+    PH_RNN_POOL_BWD = 19,    // gXp routed to the argmax frame of its window (-> gZ1 or its additive base), zero elsewhere
+};
+
+// TA3N_AGG_RNN: what the four kernels of ta3n_rnn.hip take by value.  Workspace offsets (floats) of the time-major tensors - row
+// t * B + b - and the slot table of ta3n_rnn_slots.  H = F (models.py:203), G = 4 (LSTM: i, f, g, o) or 3 (GRU: r, z, n).
+constexpr int RNN_MAX_SLOTS = 128;
+struct RnnArgs {
+    int32_t cell, n_ts, len_ts;      // cell: 0 LSTM, 1 GRU
+    int32_t o_Xp;                    // [n_ts][B][F] pooled input
+    int32_t o_Gx, o_Gh;              // [n_ts][B][G F] input / recurrent projections (with their biases)
+    int32_t o_gates;                 // [n_ts][B][G F] activated gates, kept for the backward pass
+    int32_t o_c, o_h;                // [n_ts + 1][B][F], slab 0 = the zero initial state (o_c: LSTM only)
+    int32_t o_gGx, o_gGh;            // [n_ts][B][G F] gradients at Gx / Gh (they differ in the GRU's n gate)
+    int32_t o_gc;                    // [n_ts][B][F], slab t = gradient at c_{t-1} (LSTM only)
+    int32_t o_gh, o_ghd;             // [B][F] gradient at h_{t-1}: complete (the GEMM's output) / direct part (its additive operand)
+    int32_t o_gXp;                   // [n_ts][B][F]
+    uint8_t frames[RNN_MAX_SLOTS];   // slot j * len_ts + i reads this frame
 };
 
 // work split of the fused heads kernel (ta3n_heads.hip); the plan builder sizes its partial-sum regions from these

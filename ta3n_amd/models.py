@@ -8,8 +8,9 @@ by the HIP kernels (no eager-PyTorch or CPU fallback: calling forward without th
 HIP library or without a GPU raises).
 
 Supported configurations = the TA3N hot path and TemPooling:
-frame_aggregation='trn-m' (use_attn in {'TransAttn','none'}) or 'avgpool' (use_attn 'none': BASELINE configs[0] and the
-TemPooling + RevGrad rows), baseline_type='video', share_params='Y', use_bn='none', add_fc=1, ens_DA='none',
+frame_aggregation='trn-m' (use_attn in {'TransAttn','none'}), 'avgpool' (use_attn 'none': BASELINE configs[0] and the
+TemPooling + RevGrad rows) or 'rnn' (models.py:202-215, 392-422: rnn_cell LSTM / GRU, n_rnn 1, n_directions 1, use_attn 'none',
+nothing of the options below), baseline_type='video', share_params='Y', use_bn='none', add_fc=1, ens_DA='none',
 use_attn_frame='none'; add_fc 2 / 3 (models.py:145-153, 581-603) with use_bn 'none' and ens_DA 'none';
 use_attn_frame='TransAttn' (models.py:368-377, 612-614) with use_attn='TransAttn' on 'trn-m', use_bn 'none', ens_DA 'none', add_fc 1;
 share_params='N' (models.py:174-192, 296-305, 565-566, 686-687) on 'trn-m' with use_attn 'TransAttn' / 'none', use_bn 'none', ens_DA 'none',
@@ -309,6 +310,30 @@ class _HipForwardAvg(torch.autograd.Function):
         return (None,) * (6 + ctx.n_params)
 
 
+def rnn_unsupported(use_attn='none', rnn_cell='LSTM', n_rnn=1, n_directions=1, n_ts=5, use_bn='none', ens_DA='none', add_fc=1,
+                    share_params='Y', use_attn_frame='none', segments=()) -> List[str]:
+    """What frame_aggregation 'rnn' is not built with, one entry per unmet condition (VideoModel and train_ddp.validate_options
+    share it).  segments: the segment counts the model will see - each needs round(T / n_ts) >= 1, where the reference fails
+    (models.py:397-409)."""
+    out = []
+    if use_attn != 'none':
+        out.append("frame_aggregation='rnn' with use_attn (it is not read on that branch: set use_attn none)")
+    if rnn_cell not in ('LSTM', 'GRU'): out.append(f"rnn_cell={rnn_cell!r} (LSTM or GRU)")
+    if n_rnn != 1: out.append(f"n_rnn={n_rnn} with frame_aggregation='rnn' (one recurrent layer is built)")
+    if n_directions != 1: out.append(f"n_directions={n_directions} with frame_aggregation='rnn' (one direction is built)")
+    if not isinstance(n_ts, int) or n_ts < 1: out.append(f"n_ts={n_ts!r} (a positive number of temporal segments)")
+    if use_bn != 'none': out.append(f"use_bn={use_bn!r} with frame_aggregation='rnn'")
+    if ens_DA != 'none': out.append(f"ens_DA={ens_DA!r} with frame_aggregation='rnn'")
+    if add_fc != 1: out.append(f"add_fc={add_fc} with frame_aggregation='rnn'")
+    if share_params != 'Y': out.append(f"share_params={share_params!r} with frame_aggregation='rnn'")
+    if use_attn_frame != 'none': out.append(f"use_attn_frame={use_attn_frame!r} with frame_aggregation='rnn'")
+    if isinstance(n_ts, int) and n_ts >= 1:
+        for T in segments:
+            if round(T / n_ts) < 1:
+                out.append(f"n_ts={n_ts} with {T} segments: round({T} / {n_ts}) = 0 frames per temporal segment (the reference fails there)")
+    return out
+
+
 class VideoModel(nn.Module):
     def __init__(self, num_class, baseline_type, frame_aggregation, modality,
                  train_segments=5, val_segments=25,
@@ -321,14 +346,17 @@ class VideoModel(nn.Module):
                  share_params='Y'):
         super().__init__()
         unsupported = []
-        if frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append(f"frame_aggregation={frame_aggregation!r}")
+        if frame_aggregation not in ('trn-m', 'avgpool', 'rnn'): unsupported.append(f"frame_aggregation={frame_aggregation!r}")
         if frame_aggregation == 'avgpool' and use_attn != 'none':
             unsupported.append("frame_aggregation='avgpool' with use_attn (the reference's script runs TemPooling with use_attn none)")
+        if frame_aggregation == 'rnn':        # models.py:202-215, 392-422: one LSTM / GRU layer over n_ts max-pooled temporal segments
+            unsupported += rnn_unsupported(use_attn=use_attn, rnn_cell=rnn_cell, n_rnn=n_rnn, n_directions=n_directions, n_ts=n_ts, use_bn=use_bn,
+                                           ens_DA=ens_DA, add_fc=add_fc, share_params=share_params, use_attn_frame=use_attn_frame)
         if baseline_type != 'video': unsupported.append(f"baseline_type={baseline_type!r}")
         from .options import refusal      # with which other options each of the three below is built: options.FEATURES
         context = dict(share_params=share_params, frame_aggregation=frame_aggregation, use_attn=use_attn, use_attn_frame=use_attn_frame,
                        add_fc=add_fc, use_bn=use_bn, ens_DA=ens_DA)
-        if share_params != 'Y':           # models.py:174-192, 296-305, 565-566, 686-687: the target rows' own first frame layer and video classifier
+        if share_params != 'Y' and frame_aggregation != 'rnn':           # models.py:174-192, 296-305, 565-566, 686-687: the target rows' own first frame layer and video classifier
             refused = refusal("share_params", context)[1]
             if refused: unsupported.append(f"share_params={share_params!r} ({refused})")
         if use_bn not in ('none', 'AdaBN', 'AutoDIAL'): unsupported.append(f"use_bn={use_bn!r}")
@@ -339,14 +367,14 @@ class VideoModel(nn.Module):
         if use_attn == 'general':         # models.py:320-325, 359-366: conventional attention over the relation features of trn-m
             refused = refusal("general_attn", context)[1]
             if refused: unsupported.append(f"use_attn='general' ({refused})")
-        if use_attn_frame != 'none' and use_attn != 'general':      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
+        if use_attn_frame != 'none' and use_attn != 'general' and frame_aggregation != 'rnn':      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
             refused = refusal("frame_attn", context)[1]
             if refused: unsupported.append(f"use_attn_frame={use_attn_frame!r} ({refused})")
         if not before_softmax: unsupported.append("before_softmax=False")
         if add_fc < 1:
             raise ValueError('add at least one fc layer')          # models.py:137-138
         if add_fc > 3: unsupported.append(f"add_fc={add_fc} (built: 1, 2, 3)")
-        elif add_fc > 1:       # models.py:145-153, 581-603: built for the configurations without BatchNorm / MCD
+        elif add_fc > 1 and frame_aggregation != 'rnn':       # models.py:145-153, 581-603: built for the configurations without BatchNorm / MCD
             if use_bn != 'none': unsupported.append(f"add_fc={add_fc} with use_bn={use_bn!r}")
             if ens_DA != 'none': unsupported.append(f"add_fc={add_fc} with ens_DA={ens_DA!r}")
         if unsupported:
@@ -368,7 +396,8 @@ class VideoModel(nn.Module):
         self._attn_on = use_attn in ('TransAttn', 'general')      # the attention output takes a gradient
         self._general_on = use_attn == 'general'                 # ... from a learned layer, not from the relation discriminators
         self._attn_frame_on = use_attn_frame == 'TransAttn'
-        self._avg = frame_aggregation == 'avgpool'
+        self._rnn = frame_aggregation == 'rnn'                   # the general TemPooling plan with the recurrence in place of the mean
+        self._avg = frame_aggregation == 'avgpool' or self._rnn
         self._unshared = share_params == 'N'
         if verbose:
             print(f"Initializing TSN with base model: {base_model}. input_modality: {modality}, "
@@ -405,7 +434,14 @@ class VideoModel(nn.Module):
             self.fc_feature_target = lin(F_, F_)                         # :187 (unused in forward)
             self.fc_classifier_target = lin(F_, num_class)               # :190 (feeds nothing for baseline_type='video')
         self.num_bottleneck = NB
-        if self._avg:                                                    # feat_aggregated_dim = feat_shared_dim (models.py:246-247)
+        if self._rnn:                                                    # :202-215; feat_aggregated_dim = hidden_dim = F (:250-251)
+            A = self.hidden_dim = F_
+            self.rnn = (nn.LSTM if rnn_cell == 'LSTM' else nn.GRU)(F_, F_, 1, batch_first=True, bidirectional=False)
+            nn.init.kaiming_normal_(self.rnn.all_weights[0][0])          # :210-211 (the biases keep torch's default)
+            nn.init.kaiming_normal_(self.rnn.all_weights[0][1])
+            self.bn_before_rnn = nn.BatchNorm2d(1)                       # :213-214: created, never called; kept for checkpoints
+            self.bn_after_rnn = nn.BatchNorm2d(1)
+        elif self._avg:                                                  # feat_aggregated_dim = feat_shared_dim (models.py:246-247)
             A = F_
         else:
             A = NB
@@ -470,6 +506,8 @@ class VideoModel(nn.Module):
     def _flags(self) -> int:
         # losses are assembled by the caller (main.py:439-562), so every discriminator has to be able to receive a gradient:
         # the adversarial flags only decide the plan's live parameter set here (the loss kernel is not used on this path)
+        if self._rnn:
+            return _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_FEATURE_GRADS
         if self._avg:
             return (_lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_FEATURE_GRADS |
                     (_lib.FLAG_BN_SHARED if self.use_bn != 'none' else 0) | (_lib.FLAG_MCD if self.ens_DA == 'MCD' else 0))
@@ -487,8 +525,9 @@ class VideoModel(nn.Module):
         key = (Bs, Bt, T)
         if key not in self._plans:
             self._plans[key] = _lib.Plan(Bs, Bt, T, self.feature_dim, self._feat_dim_F, self.num_class,
-                                         self._flags(), aggregation=_lib.AGG_AVGPOOL if self._avg else _lib.AGG_TRN_M,
-                                         shared_fc_layers=self.add_fc)
+                                         self._flags(), aggregation=_lib.AGG_RNN if self._rnn else _lib.AGG_AVGPOOL if self._avg else _lib.AGG_TRN_M,
+                                         shared_fc_layers=self.add_fc, rnn_cell=_lib.RNN_CELLS[self.rnn_cell] if self._rnn else 0,
+                                         n_ts=self.n_ts if self._rnn else 0)
         return self._plans[key]
 
     def _ws_template(self, plan: _lib.Plan) -> torch.Tensor:

@@ -38,6 +38,22 @@ def synth_state(shapes: Dict[str, Tuple[int, ...]], seed: int = 7, scale: str = 
     return out
 
 
+def synth_rnn_state(shapes: Dict[str, Tuple[int, ...]], seed: int, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """The recurrent aggregator's four tensors (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0; frame_aggregation
+    'rnn') at a scale of their own: weights ~ N(0, 1 / fan_in), biases ~ N(0, 0.01).  synth_state's 'trained' scale gives every tensor
+    whose name does not end in '.weight' a standard deviation of 0.01 - gate pre-activations of a few hundredths, a cell that is linear
+    to four digits and tests nothing; here they are O(1) and stay well inside +-8 (no saturated gate).  A generator of its own: the
+    other tensors' draws do not depend on it."""
+    rng = np.random.default_rng([seed, 0x726E6E])
+    out = {}
+    for name, shp in sorted(shapes.items()):
+        if not name.startswith("rnn."):
+            continue
+        arr = rng.standard_normal(shp) * (1.0 / math.sqrt(shp[1]) if len(shp) == 2 else 0.01)
+        out[name] = torch.tensor(arr, dtype=dtype)
+    return out
+
+
 def synth_batch(num_class: int, num_segments: int, feature_dim: int, batch_source: int,
                 batch_target: int, seed: int = 1234, dtype=torch.float32):
     """Half-normal features [B,T,D] for source and target plus integer labels."""

@@ -55,7 +55,18 @@ def validate_options(args, module_path: bool = False) -> None:
         refused = refusal(feature, context)[1]
         need(not refused, refused)
     need(args.baseline_type == "video", f"--baseline_type {args.baseline_type} (built: video)")
-    need(args.frame_aggregation in ("trn-m", "avgpool"), f"--frame_aggregation {args.frame_aggregation} (built: trn-m, avgpool)")
+    if module_path and args.frame_aggregation == "rnn":
+        # models.py:202-215, 392-422: one LSTM / GRU layer over n_ts max-pooled temporal segments; VideoModel's conditions, each one a line,
+        # for --num_segments and for the segment count validation runs on (main.py: val_segments < 0 means num_segments)
+        from ta3n_amd.models import rnn_unsupported
+        val_segments = args.val_segments if args.val_segments > 0 else args.num_segments
+        for line in rnn_unsupported(use_attn=args.use_attn, rnn_cell=args.rnn_cell, n_rnn=args.n_rnn, n_directions=args.n_directions, n_ts=args.n_ts,
+                                    use_bn=args.use_bn, ens_DA=args.ens_DA, add_fc=args.add_fc, share_params=args.share_params,
+                                    use_attn_frame=args.use_attn_frame, segments=sorted({args.num_segments, val_segments})):
+            need(False, "--frame_aggregation rnn: " + line)
+    else:
+        need(args.frame_aggregation in ("trn-m", "avgpool"), f"--frame_aggregation {args.frame_aggregation} (built: trn-m, avgpool)" +
+             (" (built on main.py)" if args.frame_aggregation == "rnn" else ""))
     if args.frame_aggregation == "avgpool":      # TemPooling: source-only (BASELINE configs[0]) or with the RevGrad branches; no attention
         need(args.use_attn == "none" and (args.add_loss_DA == "none" or args.use_target == "none"),
              "avgpool is built without attention / attentive entropy (--use_attn none --add_loss_DA none, as the reference's script runs it)")
