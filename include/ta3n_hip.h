@@ -166,6 +166,18 @@ typedef enum {
                                * time.  fp32; any TA3N_FLAG_ADV_x (also none), _FEATURE_GRADS, _CLASS_WEIGHTS, _TARGET_LABELS.
                                * ta3n_plan_create refuses every other flag by name, shared_fc_layers > 1, chain, split_k,
                                * wgrads_late, phase_tiles, layout_flags, and an n_ts for which ta3n_rnn_slots fails. */
+/* (3 is 'trn' in the reference's list of aggregators: the reference fails there before it computes anything - not built, no constant) */
+#define TA3N_AGG_TEMCONV  4   /* 'temconv' (models.py:44-56, 228-243, 654-672): tcl_3_1, a Conv2d(1, 1, (3, 1), padding (1, 0)) over
+                               * the segment axis of the frame features - three scalar taps and one scalar bias shared by every
+                               * channel, zero rows outside 0 .. T-1 - then ReLU and the mean over the segments:
+                               * V = mean_t relu(w0 F1[t-1] + w1 F1[t] + w2 F1[t+1] + c).  Parameters tcl_3_1.conv2d.weight (3) and
+                               * tcl_3_1.conv2d.bias (1), last of the live prefix; the reference's other temconv layers are never
+                               * called and are no parameters of the plan.  Everything else is the general TemPooling plan: the
+                               * same launch list with the two aggregator launches replaced by the filter's, plus one small launch
+                               * that sums the per-video parts of the four parameter gradients in a fixed order (no atomics: the
+                               * same step twice gives the same bits).  fp32; any TA3N_FLAG_ADV_x (also none), _FEATURE_GRADS,
+                               * _CLASS_WEIGHTS, _TARGET_LABELS.  ta3n_plan_create refuses every other flag by name,
+                               * shared_fc_layers > 1, chain, split_k, wgrads_late, phase_tiles and layout_flags. */
 
 typedef struct {
     int32_t batch_source;    /* Bs: rows of the source half (after the reference's zero padding, main.py:359-372) */

@@ -35,6 +35,7 @@ FLAG_TARGET_ENTROPY = 1 << 14  # --add_loss_DA target_entropy: gamma * mean entr
 FLAG_GENERAL_ATTN = 1 << 15   # use_attn general: relation weights = softmax over the relations of a learned layer's scores (parameters attn_layer.0 / .2; regions Ua, gUa, gs); unfused entry points, single rank
 FLAG_UNSHARED = 1 << 16       # share_params N: the target rows' own first frame layer and video classifier (parameters fc_*_target); unfused entry points, single rank
 AGG_TRN_M, AGG_AVGPOOL, AGG_RNN = 0, 1, 2      # AGG_RNN: slot max-pooling + one LSTM / GRU layer (rnn_cell, n_ts)
+AGG_TEMCONV = 4                                 # the 3-tap filter tcl_3_1 over the segments + ReLU + mean (3 would be the reference's 'trn', which it cannot run)
 RNN_CELLS = {"LSTM": 0, "GRU": 1}
 
 # every symbol include/ta3n_hip.h declares (tests check the export list)

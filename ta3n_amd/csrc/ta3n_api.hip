@@ -117,6 +117,16 @@ int launch_rnn(const ta3n_plan *p, const Phase &ph, const Ptrs &ptrs, hipStream_
     }
 }
 
+// the three launches of the temporal-convolution aggregator (TA3N_AGG_TEMCONV)
+int launch_temconv(const ta3n_plan *p, int kind, const Ptrs &ptrs, hipStream_t stream) {
+    if (p->temconv.p_w < 0) return -1;
+    switch (kind) {
+        case PH_TEMCONV_FWD: return launch_temconv_fwd(p->geom, ptrs, p->temconv, stream);
+        case PH_TEMCONV_BWD: return launch_temconv_bwd(p->geom, ptrs, p->temconv, stream);
+        default: return launch_temconv_wgrad(p->geom, ptrs, p->temconv, stream);
+    }
+}
+
 int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float *momentum, hipStream_t stream,
               hipEvent_t join_after_first = nullptr, int first_launch = 0, int n_launches = 1 << 30,
               const SgdSide *side = nullptr) {
@@ -151,6 +161,7 @@ int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float
             case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: rc = launch_frame_attn(p, ph.kind, ptrs, stream); break;
             case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: rc = launch_general_attn(p, ph.kind, ptrs, stream); break;
             case PH_RNN_POOL_FWD: case PH_RNN_CELL_FWD: case PH_RNN_CELL_BWD: case PH_RNN_POOL_BWD: rc = launch_rnn(p, ph, ptrs, stream); break;
+            case PH_TEMCONV_FWD: case PH_TEMCONV_BWD: case PH_TEMCONV_WGRAD: rc = launch_temconv(p, ph.kind, ptrs, stream); break;
             case PH_GRAD_NORM: rc = launch_grad_norm(p->geom, ptrs.g, ptrs.ws, stream); break;
             case PH_SGD: rc = launch_sgd(p->geom, params_rw, ptrs.g, momentum, ptrs.ws, stream); break;
             default: rc = -1;
@@ -461,6 +472,7 @@ int ta3n_time_phases(ta3n_plan *p, const float *x, float *params, float *grads, 
                 case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: lrc = launch_frame_attn(p, ph.kind, ptrs, s); break;
                 case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: lrc = launch_general_attn(p, ph.kind, ptrs, s); break;
                 case PH_RNN_POOL_FWD: case PH_RNN_CELL_FWD: case PH_RNN_CELL_BWD: case PH_RNN_POOL_BWD: lrc = launch_rnn(p, ph, ptrs, s); break;
+                case PH_TEMCONV_FWD: case PH_TEMCONV_BWD: case PH_TEMCONV_WGRAD: lrc = launch_temconv(p, ph.kind, ptrs, s); break;
                 case PH_GRAD_NORM: lrc = launch_grad_norm(p->geom, grads, ws, s); break;
                 case PH_SGD: lrc = launch_sgd(p->geom, params, grads, momentum, ws, s); break;
                 default: lrc = -1;

@@ -290,6 +290,10 @@ int launch_rnn_pool_fwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, hipSt
 int launch_rnn_cell_fwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, int t, hipStream_t stream);
 int launch_rnn_cell_bwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, int t, hipStream_t stream);
 int launch_rnn_pool_bwd(const Geom &g, const Ptrs &ptrs, const RnnArgs &a, hipStream_t stream);
+// TA3N_AGG_TEMCONV (ta3n_temconv.hip): the 3-tap filter over the segments + ReLU + mean, its way back, the parameter-gradient sum
+int launch_temconv_fwd(const Geom &g, const Ptrs &ptrs, const TemconvArgs &a, hipStream_t stream);
+int launch_temconv_bwd(const Geom &g, const Ptrs &ptrs, const TemconvArgs &a, hipStream_t stream);
+int launch_temconv_wgrad(const Geom &g, const Ptrs &ptrs, const TemconvArgs &a, hipStream_t stream);
 int launch_grad_norm(const Geom &g, const float *grads, float *ws, hipStream_t stream);
 int launch_sgd(const Geom &g, float *params, const float *grads, float *momentum, float *ws, hipStream_t stream,
                bool fused_norm = false);

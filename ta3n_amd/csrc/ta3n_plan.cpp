@@ -438,6 +438,9 @@ struct AvgpoolDa {
     // TA3N_AGG_RNN (models.py:202-215, 392-422): the two aggregator launches become the recurrence; nullptr: TemPooling
     const RnnArgs *rnn = nullptr;
     int64_t Wih = -1, bih = -1, Whh = -1, bhh = -1;
+    // TA3N_AGG_TEMCONV (models.py:228-243, 654-672): the two aggregator launches become the filter's, and one more launch at the end of the
+    // way back sums the per-video parts of the four parameter gradients
+    bool temconv = false;
 
     void add_step_phase(int kind, int group, int t) { b.add_simple_phase(kind, group); b.p.phases.back().task_begin = t; }
 
@@ -484,7 +487,7 @@ struct AvgpoolDa {
         if (bn_shared) b.add_simple_phase(PH_BN_FWD, group);
         add_stack_forward(b, st, group, BT, F);
         if (live_frm) b.add_gemm_phase(group, spec_linear(BT, F, F, BASE_WS, g.o_F1, F, w.Wfd, w.bfd, g.o_Hf, F, true));   // models.py:458-459
-        if (rnn) rnn_forward(group); else b.add_simple_phase(PH_POOL_AVG_FWD, group);
+        if (rnn) rnn_forward(group); else b.add_simple_phase(temconv ? PH_TEMCONV_FWD : PH_POOL_AVG_FWD, group);
         {
             std::vector<GemmSpec> s{spec_linear(B, C, F, BASE_WS, g.o_Vd, F, w.Wcv, w.bcv, g.o_Y, C, false)};                     // :686
             if (mcd) s.push_back(spec_linear(B, C, F, BASE_WS, g.o_Vd, F, w.Wcv2, w.bcv2, g.o_Y2, C, false));                     // :717-718
@@ -521,7 +524,7 @@ struct AvgpoolDa {
             if (live_frm) s.push_back(spec_wgrad(F, F, BT, g.o_gHf, F, BASE_WS, g.o_F1, F, w.Wfd, w.bfd));
             b.add_gemm_phase(group, s);
         }
-        if (rnn) rnn_backward(group); else b.add_simple_phase(PH_POOL_AVG_BWD, group);
+        if (rnn) rnn_backward(group); else b.add_simple_phase(temconv ? PH_TEMCONV_BWD : PH_POOL_AVG_BWD, group);
         if (live_frm) {   // gZ1 = ( -beta2 gHf Wfd + gVt / T ) * [F1 > 0] / keep_i
             GemmSpec gz;
             gz.M = BT; gz.N = F;
@@ -535,8 +538,30 @@ struct AvgpoolDa {
         add_stack_backward(b, st, group, BT, F);
         if (bn_shared) b.add_simple_phase(PH_BN_BWD, group);
         b.add_gemm_phase(group, spec_wgrad(F, D, BT, bn_shared ? g.o_gZ0 : st.o_gZ[1], F, BASE_X, 0, D, w.Wsh, w.bsh));
+        if (temconv) b.add_simple_phase(PH_TEMCONV_WGRAD, group);      // (the last launch of the way back: in front of PH_GRAD_NORM)
     }
 };
+
+// "" when the configuration is built on TA3N_AGG_TEMCONV, otherwise the refusal, naming what is not built there
+std::string temconv_refusal(const ta3n_config &c) {
+    const std::pair<uint32_t, const char *> flags[] = {
+        {TA3N_FLAG_BF16_MFMA, "TA3N_FLAG_BF16_MFMA"}, {TA3N_FLAG_BF16_STORE, "TA3N_FLAG_BF16_STORE"}, {TA3N_FLAG_F32_SPLIT, "TA3N_FLAG_F32_SPLIT"},
+        {TA3N_FLAG_MCD, "TA3N_FLAG_MCD (ens_DA MCD)"}, {TA3N_FLAG_BN_SHARED, "TA3N_FLAG_BN_SHARED (use_bn)"},
+        {TA3N_FLAG_TRANS_ATTN, "TA3N_FLAG_TRANS_ATTN (use_attn TransAttn)"}, {TA3N_FLAG_ATTN_ENTROPY, "TA3N_FLAG_ATTN_ENTROPY (add_loss_DA attentive_entropy)"},
+        {TA3N_FLAG_TARGET_ENTROPY, "TA3N_FLAG_TARGET_ENTROPY (add_loss_DA target_entropy)"}, {TA3N_FLAG_FRAME_ATTN, "TA3N_FLAG_FRAME_ATTN (use_attn_frame)"},
+        {TA3N_FLAG_GENERAL_ATTN, "TA3N_FLAG_GENERAL_ATTN (use_attn general)"}, {TA3N_FLAG_UNSHARED, "TA3N_FLAG_UNSHARED (share_params N)"}};
+    const std::string head = "TA3N_AGG_TEMCONV (frame_aggregation temconv) with ";
+    for (const auto &f : flags)
+        if (c.flags & f.first) return head + f.second + " is not built";
+    if (c.shared_fc_layers > 1) return head + "shared_fc_layers (--add_fc) " + std::to_string(c.shared_fc_layers) + " is not built";
+    if (c.chain) return head + "chain is not built";
+    if (c.split_k) return head + "split_k is not built";
+    if (c.wgrads_late) return head + "wgrads_late is not built";
+    for (int i = 0; i < 16; ++i)
+        if (c.phase_tiles[i]) return head + "phase_tiles is not built";
+    if (c.layout_flags) return head + "layout_flags is not built";
+    return "";
+}
 
 // "" when the configuration is built on TA3N_AGG_RNN, otherwise the refusal, naming what is not built there
 std::string rnn_refusal(const ta3n_config &c) {
@@ -565,7 +590,7 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     const ta3n_config &c = p.cfg;
     const Dims d = dims_of(c);
     const int B = d.B, BT = d.BT, F = d.F, C = d.C;
-    const bool is_rnn = c.aggregation == TA3N_AGG_RNN;
+    const bool is_rnn = c.aggregation == TA3N_AGG_RNN, is_temconv = c.aggregation == TA3N_AGG_TEMCONV;
     if (c.flags & (TA3N_FLAG_ATTN_ENTROPY | TA3N_FLAG_TRANS_ATTN)) {
         err = "avgpool: attention / attentive entropy are not built (the reference's script switches them off with use_attn none)";
         return TA3N_ERR_INVALID;
@@ -592,6 +617,10 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     if (is_rnn) {                                                      // (bn_before_rnn / bn_after_rnn, :213-214, are never called: no parameters of the plan)
         b.add_param("rnn.weight_ih_l0", GF, F, true); b.add_param("rnn.weight_hh_l0", GF, F, true);
         b.add_param("rnn.bias_ih_l0", GF, 0, true); b.add_param("rnn.bias_hh_l0", GF, 0, true);
+    }
+    if (is_temconv) {      // TA3N_AGG_TEMCONV: tcl_3_1 = Conv2d(1, 1, (3, 1)) (:230); tcl_5_1, tcl_3_2, tcl_5_2, bn_1_*, bn_2_*, conv_fusion (:231-243) are
+        b.add_param("tcl_3_1.conv2d.weight", 3, 0, true);      // never called: no parameters of the plan
+        b.add_param("tcl_3_1.conv2d.bias", 1, 0, true);
     }
     p.live_floats = p.param_floats;
     b.add_dead_linears();
@@ -650,6 +679,11 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
         m.Wih = p.poff("rnn.weight_ih_l0"); m.Whh = p.poff("rnn.weight_hh_l0");
         m.bih = p.poff("rnn.bias_ih_l0"); m.bhh = p.poff("rnn.bias_hh_l0");
     }
+    if (is_temconv) {
+        p.temconv.p_w = (int32_t)p.poff("tcl_3_1.conv2d.weight"); p.temconv.p_b = (int32_t)p.poff("tcl_3_1.conv2d.bias");
+        p.temconv.o_part = (int32_t)b.add_region("tc_part", (int64_t)B * 4);
+        m.temconv = true;
+    }
     g.o_attn = (int32_t)b.add_region("attn", 4); g.o_gattn = (int32_t)b.add_region("g_attn", 4);
     if (feat_grads) g.o_gV_ext = (int32_t)b.add_region("gV_ext", (int64_t)B * F);
     if (mcd) add_mcd_regions(b, g, d);
@@ -665,7 +699,9 @@ int build_plan_avgpool_general(ta3n_plan &p, std::string &err) {
     m.forward(4);                           // ta3n_train_step: the same launches as one sequence
     b.add_simple_phase(PH_LOSS, 4);
     m.backward(4);
-    assign_sumsq_slots(p, b, g, bn_sumsq_slots(bn_shared, F));
+    // (TA3N_AGG_TEMCONV - never with bn_shared - : the four tcl_3_1 gradients come from PH_TEMCONV_WGRAD, which leaves their sum of squares in the last slot)
+    assign_sumsq_slots(p, b, g, bn_sumsq_slots(bn_shared, F) + (is_temconv ? 1 : 0));
+    if (is_temconv) p.temconv.o_sumsq = g.o_sumsq + g.n_sumsq - 1;
     // (no bf16 twins on this path: the small kernels between the launches do not maintain them; the contractions still
     // round their operands in registers with TA3N_FLAG_BF16_MFMA)
     return finish_plan(p, b, err);
@@ -1399,10 +1435,11 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     const ta3n_config &c = p.cfg;
     const Dims d = dims_of(c);
     if (d.Bs < 0 || d.Bt < 0 || d.Bs + d.Bt <= 0) { err = "batch sizes must be non-negative and not both zero"; return TA3N_ERR_INVALID; }
-    if (c.aggregation != TA3N_AGG_TRN_M && c.aggregation != TA3N_AGG_AVGPOOL && c.aggregation != TA3N_AGG_RNN) {
-        err = "aggregation must be TA3N_AGG_TRN_M or TA3N_AGG_AVGPOOL";      // (the text tests/golden/plan_fingerprints.json pins; TA3N_AGG_RNN is the third)
+    if (c.aggregation != TA3N_AGG_TRN_M && c.aggregation != TA3N_AGG_AVGPOOL && c.aggregation != TA3N_AGG_RNN && c.aggregation != TA3N_AGG_TEMCONV) {
+        err = "aggregation must be TA3N_AGG_TRN_M or TA3N_AGG_AVGPOOL";      // (the text tests/golden/plan_fingerprints.json pins; TA3N_AGG_RNN and _TEMCONV are the others)
         return TA3N_ERR_INVALID;
     }
+    if (c.aggregation == TA3N_AGG_TEMCONV) { const std::string e = temconv_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     if (c.aggregation == TA3N_AGG_RNN) { const std::string e = rnn_refusal(c); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
     if (d.T < 2 || d.T > 64) { err = "num_segments must be in [2,64] for trn-m"; return TA3N_ERR_INVALID; }
     if (d.D <= 0 || d.F <= 0 || d.C <= 0) { err = "feature_dim, fc_dim and num_class must be positive"; return TA3N_ERR_INVALID; }
@@ -1453,7 +1490,7 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     if (c.aggregation == TA3N_AGG_TRN_M) return build_plan_trn(p, err);
     p.n_tuples = 0;      // (no relation tuples)
     p.tuple_first.assign(1, 0);
-    if (c.aggregation == TA3N_AGG_RNN) return build_plan_avgpool_general(p, err);      // (also with no flag at all: there is no source-only fast path)
+    if (c.aggregation == TA3N_AGG_RNN || c.aggregation == TA3N_AGG_TEMCONV) return build_plan_avgpool_general(p, err);      // (also with no flag at all: there is no source-only fast path)
     // avgpool, source-only: the fused fast path (BASELINE configs[0]); with adversarial branches or a module-path option: the general one
     const uint32_t general = TA3N_FLAG_ADV_RELATION | TA3N_FLAG_ADV_VIDEO | TA3N_FLAG_ADV_FRAME | TA3N_FLAG_MCD | TA3N_FLAG_FEATURE_GRADS |
                              TA3N_FLAG_BN_SHARED;

@@ -49,6 +49,8 @@ struct ta3n_plan {
     struct GeneralAttn { int32_t Ua = -1, gUa = -1, gs = -1, p_wa2 = -1, p_ba2 = -1; } general_attn;
     // TA3N_AGG_RNN: the launch argument of the four recurrent kernels (n_ts == 0 on every other plan)
     ta3n::RnnArgs rnn = {};
+    // TA3N_AGG_TEMCONV: the launch argument of the three temporal-convolution kernels (p_w < 0 on every other plan)
+    ta3n::TemconvArgs temconv = {-1, -1, -1, -1};
     int64_t class_w_off = 0;     // ws offset of region "class_w" (TA3N_FLAG_CLASS_WEIGHTS; 0 without it): what the launchers put into Hyper::class_w_off
     uint64_t deny_blocking = 0;   // bit i: phase i must not use register-blocked tiles (it does not read bf16 twins; build_plan's retry)
     // device copies (created lazily by the launcher)

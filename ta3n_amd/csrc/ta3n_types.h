@@ -112,6 +112,17 @@ enum PhaseKind : int32_t {
     PH_RNN_CELL_FWD = 17,    // step t: gates from Gx_t + Gh_t, c_t, h_t; the last step also V = h_t, Vd = dropout_v(V), loss slots = 0
     PH_RNN_CELL_BWD = 18,    // step t: gGx_t, gGh_t, gc_{t-1}, direct part of gh_{t-1} from gh_t (last step: gVt [+ gV_ext]) and gc_t
     PH_RNN_POOL_BWD = 19,    // gXp routed to the argmax frame of its window (-> gZ1 or its additive base), zero elsewhere
+    // TA3N_AGG_TEMCONV (ta3n_temconv.hip; offsets in ta3n_plan::temconv)
+    PH_TEMCONV_FWD = 20,     // V = mean_t relu(w0 F1[t-1] + w1 F1[t] + w2 F1[t+1] + c), Vd = dropout_v(V), loss slots = 0
+    PH_TEMCONV_BWD = 21,     // gradient at V back through the mean, the ReLU and the filter (-> gZ1 or its additive base); tc_part[b] = this video's share of the four parameter gradients
+    PH_TEMCONV_WGRAD = 22,   // fixed-order sum of tc_part over the videos -> gradient entries of tcl_3_1.conv2d.{weight, bias}, their sum of squares
+};
+
+// TA3N_AGG_TEMCONV: what the three kernels of ta3n_temconv.hip take by value
+struct TemconvArgs {
+    int32_t p_w, p_b;                // parameter offsets of tcl_3_1.conv2d.weight (3 taps) and .bias (1)
+    int32_t o_part;                  // ws "tc_part" [B][4]: per video sum_t gR_t F1[t-1], gR_t F1[t], gR_t F1[t+1], gR_t
+    int32_t o_sumsq;                 // ws slot (the last of "sumsq") for the four gradients' sum of squares: the fused optimiser's norm
 };
 
 // TA3N_AGG_RNN: what the four kernels of ta3n_rnn.hip take by value.  Workspace offsets (floats) of the time-major tensors - row

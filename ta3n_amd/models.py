@@ -9,8 +9,10 @@ HIP library or without a GPU raises).
 
 Supported configurations = the TA3N hot path and TemPooling:
 frame_aggregation='trn-m' (use_attn in {'TransAttn','none'}), 'avgpool' (use_attn 'none': BASELINE configs[0] and the
-TemPooling + RevGrad rows) or 'rnn' (models.py:202-215, 392-422: rnn_cell LSTM / GRU, n_rnn 1, n_directions 1, use_attn 'none',
-nothing of the options below), baseline_type='video', share_params='Y', use_bn='none', add_fc=1, ens_DA='none',
+TemPooling + RevGrad rows), 'rnn' (models.py:202-215, 392-422: rnn_cell LSTM / GRU, n_rnn 1, n_directions 1, use_attn 'none',
+nothing of the options below) or 'temconv' (models.py:44-56, 228-243, 654-672: the 3-tap filter tcl_3_1 over the segments, ReLU and
+the mean; use_attn 'none', nothing of the options below; the reference's own forward computes this branch and then fails at its
+return on two unbound attention placeholders - here they are V[:, 0], as for 'avgpool' and 'rnn'), baseline_type='video', share_params='Y', use_bn='none', add_fc=1, ens_DA='none',
 use_attn_frame='none'; add_fc 2 / 3 (models.py:145-153, 581-603) with use_bn 'none' and ens_DA 'none';
 use_attn_frame='TransAttn' (models.py:368-377, 612-614) with use_attn='TransAttn' on 'trn-m', use_bn 'none', ens_DA 'none', add_fc 1;
 share_params='N' (models.py:174-192, 296-305, 565-566, 686-687) on 'trn-m' with use_attn 'TransAttn' / 'none', use_bn 'none', ens_DA 'none',
@@ -334,6 +336,30 @@ def rnn_unsupported(use_attn='none', rnn_cell='LSTM', n_rnn=1, n_directions=1, n
     return out
 
 
+def temconv_unsupported(use_attn='none', use_bn='none', ens_DA='none', add_fc=1, share_params='Y', use_attn_frame='none') -> List[str]:
+    """What frame_aggregation 'temconv' is not built with, one entry per unmet condition (VideoModel and train_ddp.validate_options
+    share it)."""
+    out = []
+    if use_attn != 'none':
+        out.append("frame_aggregation='temconv' with use_attn (it is not read on that branch: set use_attn none)")
+    if use_bn != 'none': out.append(f"use_bn={use_bn!r} with frame_aggregation='temconv' (the temconv_1 BatchNorm site is not built)")
+    if ens_DA != 'none': out.append(f"ens_DA={ens_DA!r} with frame_aggregation='temconv'")
+    if add_fc != 1: out.append(f"add_fc={add_fc} with frame_aggregation='temconv'")
+    if share_params != 'Y': out.append(f"share_params={share_params!r} with frame_aggregation='temconv'")
+    if use_attn_frame != 'none': out.append(f"use_attn_frame={use_attn_frame!r} with frame_aggregation='temconv'")
+    return out
+
+
+class _TCL(nn.Module):
+    """models.py:44-56: the reference's temporal-convolution layer, a Conv2d over (segments, 1) with kaiming-normal weights.  Only
+    tcl_3_1's four scalars are computed with (by the HIP kernels); the module holds the parameters under the reference's names."""
+
+    def __init__(self, conv_size, dim):
+        super().__init__()
+        self.conv2d = nn.Conv2d(dim, dim, kernel_size=(conv_size, 1), padding=(conv_size // 2, 0))
+        nn.init.kaiming_normal_(self.conv2d.weight)
+
+
 class VideoModel(nn.Module):
     def __init__(self, num_class, baseline_type, frame_aggregation, modality,
                  train_segments=5, val_segments=25,
@@ -346,35 +372,39 @@ class VideoModel(nn.Module):
                  share_params='Y'):
         super().__init__()
         unsupported = []
-        if frame_aggregation not in ('trn-m', 'avgpool', 'rnn'): unsupported.append(f"frame_aggregation={frame_aggregation!r}")
+        if frame_aggregation not in ('trn-m', 'avgpool', 'rnn', 'temconv'): unsupported.append(f"frame_aggregation={frame_aggregation!r}")
         if frame_aggregation == 'avgpool' and use_attn != 'none':
             unsupported.append("frame_aggregation='avgpool' with use_attn (the reference's script runs TemPooling with use_attn none)")
         if frame_aggregation == 'rnn':        # models.py:202-215, 392-422: one LSTM / GRU layer over n_ts max-pooled temporal segments
             unsupported += rnn_unsupported(use_attn=use_attn, rnn_cell=rnn_cell, n_rnn=n_rnn, n_directions=n_directions, n_ts=n_ts, use_bn=use_bn,
                                            ens_DA=ens_DA, add_fc=add_fc, share_params=share_params, use_attn_frame=use_attn_frame)
+        if frame_aggregation == 'temconv':    # models.py:228-243, 654-672: the 3-tap filter tcl_3_1 over the segments, ReLU, mean
+            unsupported += temconv_unsupported(use_attn=use_attn, use_bn=use_bn, ens_DA=ens_DA, add_fc=add_fc, share_params=share_params,
+                                               use_attn_frame=use_attn_frame)
+        own_list = frame_aggregation in ('rnn', 'temconv')      # ... whose conditions are all in the list above
         if baseline_type != 'video': unsupported.append(f"baseline_type={baseline_type!r}")
         from .options import refusal      # with which other options each of the three below is built: options.FEATURES
         context = dict(share_params=share_params, frame_aggregation=frame_aggregation, use_attn=use_attn, use_attn_frame=use_attn_frame,
                        add_fc=add_fc, use_bn=use_bn, ens_DA=ens_DA)
-        if share_params != 'Y' and frame_aggregation != 'rnn':           # models.py:174-192, 296-305, 565-566, 686-687: the target rows' own first frame layer and video classifier
+        if share_params != 'Y' and not own_list:           # models.py:174-192, 296-305, 565-566, 686-687: the target rows' own first frame layer and video classifier
             refused = refusal("share_params", context)[1]
             if refused: unsupported.append(f"share_params={share_params!r} ({refused})")
         if use_bn not in ('none', 'AdaBN', 'AutoDIAL'): unsupported.append(f"use_bn={use_bn!r}")
-        if use_bn != 'none' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("use_bn with this frame_aggregation")
+        if use_bn != 'none' and frame_aggregation not in ('trn-m', 'avgpool', 'temconv'): unsupported.append("use_bn with this frame_aggregation")
         if ens_DA not in ('none', 'MCD'): unsupported.append(f"ens_DA={ens_DA!r}")
-        if ens_DA == 'MCD' and frame_aggregation not in ('trn-m', 'avgpool'): unsupported.append("ens_DA='MCD' with this frame_aggregation")
+        if ens_DA == 'MCD' and frame_aggregation not in ('trn-m', 'avgpool', 'temconv'): unsupported.append("ens_DA='MCD' with this frame_aggregation")
         if use_attn not in ('TransAttn', 'none', 'general'): unsupported.append(f"use_attn={use_attn!r}")
         if use_attn == 'general':         # models.py:320-325, 359-366: conventional attention over the relation features of trn-m
             refused = refusal("general_attn", context)[1]
             if refused: unsupported.append(f"use_attn='general' ({refused})")
-        if use_attn_frame != 'none' and use_attn != 'general' and frame_aggregation != 'rnn':      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
+        if use_attn_frame != 'none' and use_attn != 'general' and not own_list:      # models.py:368-377, 612-614: built as TransAttn in front of the TRN, together with use_attn TransAttn
             refused = refusal("frame_attn", context)[1]
             if refused: unsupported.append(f"use_attn_frame={use_attn_frame!r} ({refused})")
         if not before_softmax: unsupported.append("before_softmax=False")
         if add_fc < 1:
             raise ValueError('add at least one fc layer')          # models.py:137-138
         if add_fc > 3: unsupported.append(f"add_fc={add_fc} (built: 1, 2, 3)")
-        elif add_fc > 1 and frame_aggregation != 'rnn':       # models.py:145-153, 581-603: built for the configurations without BatchNorm / MCD
+        elif add_fc > 1 and not own_list:       # models.py:145-153, 581-603: built for the configurations without BatchNorm / MCD
             if use_bn != 'none': unsupported.append(f"add_fc={add_fc} with use_bn={use_bn!r}")
             if ens_DA != 'none': unsupported.append(f"add_fc={add_fc} with ens_DA={ens_DA!r}")
         if unsupported:
@@ -397,7 +427,8 @@ class VideoModel(nn.Module):
         self._general_on = use_attn == 'general'                 # ... from a learned layer, not from the relation discriminators
         self._attn_frame_on = use_attn_frame == 'TransAttn'
         self._rnn = frame_aggregation == 'rnn'                   # the general TemPooling plan with the recurrence in place of the mean
-        self._avg = frame_aggregation == 'avgpool' or self._rnn
+        self._temconv = frame_aggregation == 'temconv'           # ... or with the 3-tap filter + ReLU in front of the mean
+        self._avg = frame_aggregation == 'avgpool' or self._rnn or self._temconv
         self._unshared = share_params == 'N'
         if verbose:
             print(f"Initializing TSN with base model: {base_model}. input_modality: {modality}, "
@@ -441,6 +472,17 @@ class VideoModel(nn.Module):
             nn.init.kaiming_normal_(self.rnn.all_weights[0][1])
             self.bn_before_rnn = nn.BatchNorm2d(1)                       # :213-214: created, never called; kept for checkpoints
             self.bn_after_rnn = nn.BatchNorm2d(1)
+        elif self._temconv:                                              # :228-243; feat_aggregated_dim = feat_shared_dim (:252-253)
+            A = F_
+            self.tcl_3_1 = _TCL(3, 1)                                    # the one layer the forward calls (:659-660)
+            self.tcl_5_1 = _TCL(5, 1)                                    # :231-243: created, never called; kept for checkpoints
+            self.bn_1_S = nn.BatchNorm1d(F_)                             # (bn_1_*: only under use_bn, which is not built here)
+            self.bn_1_T = nn.BatchNorm1d(F_)
+            self.tcl_3_2 = _TCL(3, 1)
+            self.tcl_5_2 = _TCL(5, 2)
+            self.bn_2_S = nn.BatchNorm1d(F_)
+            self.bn_2_T = nn.BatchNorm1d(F_)
+            self.conv_fusion = nn.Sequential(nn.Conv2d(2, 1, kernel_size=(1, 1), padding=(0, 0)), nn.ReLU(inplace=True))
         elif self._avg:                                                  # feat_aggregated_dim = feat_shared_dim (models.py:246-247)
             A = F_
         else:
@@ -506,7 +548,7 @@ class VideoModel(nn.Module):
     def _flags(self) -> int:
         # losses are assembled by the caller (main.py:439-562), so every discriminator has to be able to receive a gradient:
         # the adversarial flags only decide the plan's live parameter set here (the loss kernel is not used on this path)
-        if self._rnn:
+        if self._rnn or self._temconv:
             return _lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_FEATURE_GRADS
         if self._avg:
             return (_lib.FLAG_ADV_VIDEO | _lib.FLAG_ADV_FRAME | _lib.FLAG_FEATURE_GRADS |
@@ -525,7 +567,8 @@ class VideoModel(nn.Module):
         key = (Bs, Bt, T)
         if key not in self._plans:
             self._plans[key] = _lib.Plan(Bs, Bt, T, self.feature_dim, self._feat_dim_F, self.num_class,
-                                         self._flags(), aggregation=_lib.AGG_RNN if self._rnn else _lib.AGG_AVGPOOL if self._avg else _lib.AGG_TRN_M,
+                                         self._flags(), aggregation=(_lib.AGG_RNN if self._rnn else _lib.AGG_TEMCONV if self._temconv else _lib.AGG_AVGPOOL if self._avg else
+                                                                      _lib.AGG_TRN_M),
                                          shared_fc_layers=self.add_fc, rnn_cell=_lib.RNN_CELLS[self.rnn_cell] if self._rnn else 0,
                                          n_ts=self.n_ts if self._rnn else 0)
         return self._plans[key]
@@ -576,7 +619,8 @@ class VideoModel(nn.Module):
 
     def _named_flat_params(self, plan: _lib.Plan):
         named = dict(self.named_parameters())
-        return [(name, off, shape, named[name]) for name, off, shape, _ in plan.params]
+        # (the parameter's own shape: the plan knows tcl_3_1.conv2d.weight as 3 floats, the module as [1, 1, 3, 1])
+        return [(name, off, tuple(named[name].shape), named[name]) for name, off, _, _ in plan.params]
 
     def _flat_items(self, plan: _lib.Plan):
         """[(name, offset, shape, nn.Parameter)] in the plan's order, cached per plan (walking the module tree costs ~0.1 ms per

@@ -54,6 +54,21 @@ def synth_rnn_state(shapes: Dict[str, Tuple[int, ...]], seed: int, dtype=torch.f
     return out
 
 
+def synth_temconv_state(shapes: Dict[str, Tuple[int, ...]], seed: int, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """The temporal-convolution aggregator's two live tensors (tcl_3_1.conv2d.weight, tcl_3_1.conv2d.bias; frame_aggregation 'temconv')
+    at a scale of their own: taps ~ N(0, 2 / 3) - kaiming_normal_'s variance at fan-in 3 -, bias ~ N(0, 0.1).  synth_state's 'trained'
+    scale would leave the taps at a few thousandths - a filter output near zero, nothing for the ReLU to cut.  A generator of its own:
+    the other tensors' draws do not depend on it."""
+    rng = np.random.default_rng([seed, 0x74636C])
+    out = {}
+    for name, shp in sorted(shapes.items()):
+        if not name.startswith("tcl_3_1."):
+            continue
+        arr = rng.standard_normal(shp) * (math.sqrt(2.0 / 3.0) if name.endswith(".weight") else math.sqrt(0.1))
+        out[name] = torch.tensor(arr, dtype=dtype)
+    return out
+
+
 def synth_batch(num_class: int, num_segments: int, feature_dim: int, batch_source: int,
                 batch_target: int, seed: int = 1234, dtype=torch.float32):
     """Half-normal features [B,T,D] for source and target plus integer labels."""

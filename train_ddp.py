@@ -64,9 +64,15 @@ def validate_options(args, module_path: bool = False) -> None:
                                     use_bn=args.use_bn, ens_DA=args.ens_DA, add_fc=args.add_fc, share_params=args.share_params,
                                     use_attn_frame=args.use_attn_frame, segments=sorted({args.num_segments, val_segments})):
             need(False, "--frame_aggregation rnn: " + line)
+    elif module_path and args.frame_aggregation == "temconv":
+        # models.py:228-243, 654-672: the 3-tap filter tcl_3_1 over the segments, ReLU, mean; VideoModel's conditions, each one a line
+        from ta3n_amd.models import temconv_unsupported
+        for line in temconv_unsupported(use_attn=args.use_attn, use_bn=args.use_bn, ens_DA=args.ens_DA, add_fc=args.add_fc,
+                                        share_params=args.share_params, use_attn_frame=args.use_attn_frame):
+            need(False, "--frame_aggregation temconv: " + line)
     else:
         need(args.frame_aggregation in ("trn-m", "avgpool"), f"--frame_aggregation {args.frame_aggregation} (built: trn-m, avgpool)" +
-             (" (built on main.py)" if args.frame_aggregation == "rnn" else ""))
+             (" (built on main.py)" if args.frame_aggregation in ("rnn", "temconv") else ""))
     if args.frame_aggregation == "avgpool":      # TemPooling: source-only (BASELINE configs[0]) or with the RevGrad branches; no attention
         need(args.use_attn == "none" and (args.add_loss_DA == "none" or args.use_target == "none"),
              "avgpool is built without attention / attentive entropy (--use_attn none --add_loss_DA none, as the reference's script runs it)")
