@@ -127,6 +127,35 @@ int launch_temconv(const ta3n_plan *p, int kind, const Ptrs &ptrs, hipStream_t s
     }
 }
 
+// The one place that starts the kernel of a launch kind: phase `index` of the plan on `stream`, the launcher's raw code returned (0: started,
+// -5: launch_gemm has set the message - an experiments-only launch list on the default library; anything else: the launch failed).
+// `side`: the update that rides in a pipelined step's first GEMM launch; params_rw / momentum: what PH_SGD writes.
+int launch_phase(const ta3n_plan *p, int index, const Ptrs &ptrs, float *params_rw, float *momentum, hipStream_t stream, const SgdSide *side) {
+    const Phase &ph = p->phases[index];
+    switch (ph.kind) {
+        case PH_GEMM:
+            return launch_gemm(ph, static_cast<const Task *>(p->d_tasks), static_cast<const Seg *>(p->d_segs), ptrs,
+                               p->geom.o_hyper, p->geom.o_zeros, p->geom.o_ws16, stream, side, static_cast<const Wait *>(p->d_waits),
+                               p->geom.pair_delta, p->phase_kinds.empty() ? 0 : p->phase_kinds[index]);
+        case PH_POOL_FWD: return launch_pool_fwd(p->geom, ptrs, stream);
+        case PH_LOSS: return launch_loss(p->geom, ptrs, stream);
+        case PH_POOL_BWD: return launch_pool_bwd(p->geom, ptrs, stream);
+        case PH_HEADS: return launch_heads(p->geom, ptrs, stream);
+        case PH_POOL_CLS: return launch_pool_cls(p->geom, ptrs, stream);
+        case PH_POOL_AVG_FWD: return launch_pool_avg_fwd(p->geom, ptrs, stream);
+        case PH_POOL_AVG_BWD: return launch_pool_avg_bwd(p->geom, ptrs, stream);
+        case PH_BN_FWD: return launch_bn_shared_fwd(p->geom, ptrs, stream);
+        case PH_BN_BWD: return launch_bn_shared_bwd(p->geom, ptrs, stream);
+        case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: return launch_frame_attn(p, ph.kind, ptrs, stream);
+        case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: return launch_general_attn(p, ph.kind, ptrs, stream);
+        case PH_RNN_POOL_FWD: case PH_RNN_CELL_FWD: case PH_RNN_CELL_BWD: case PH_RNN_POOL_BWD: return launch_rnn(p, ph, ptrs, stream);
+        case PH_TEMCONV_FWD: case PH_TEMCONV_BWD: case PH_TEMCONV_WGRAD: return launch_temconv(p, ph.kind, ptrs, stream);
+        case PH_GRAD_NORM: return launch_grad_norm(p->geom, ptrs.g, ptrs.ws, stream);
+        case PH_SGD: return launch_sgd(p->geom, params_rw, ptrs.g, momentum, ptrs.ws, stream);
+        default: return -1;
+    }
+}
+
 int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float *momentum, hipStream_t stream,
               hipEvent_t join_after_first = nullptr, int first_launch = 0, int n_launches = 1 << 30,
               const SgdSide *side = nullptr) {
@@ -134,7 +163,6 @@ int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float
     int index = -1;
     for (const Phase &ph : p->phases) {
         if (ph.group != group) continue;
-        const int kinds = p->phase_kinds.empty() ? 0 : p->phase_kinds[&ph - p->phases.data()];
         ++index;
         if (index < first_launch || index >= first_launch + n_launches) continue;
         if (!first && join_after_first) {   // everything after the first launch also depends on work the caller put on another stream
@@ -142,30 +170,7 @@ int run_group(ta3n_plan *p, int group, const Ptrs &ptrs, float *params_rw, float
             join_after_first = nullptr;
         }
         first = false;
-        int rc = 0;
-        switch (ph.kind) {
-            case PH_GEMM:
-                rc = launch_gemm(ph, static_cast<const Task *>(p->d_tasks), static_cast<const Seg *>(p->d_segs), ptrs,
-                                 p->geom.o_hyper, p->geom.o_zeros, p->geom.o_ws16, stream, side, static_cast<const Wait *>(p->d_waits),
-                                 p->geom.pair_delta, kinds);
-                break;
-            case PH_POOL_FWD: rc = launch_pool_fwd(p->geom, ptrs, stream); break;
-            case PH_LOSS: rc = launch_loss(p->geom, ptrs, stream); break;
-            case PH_POOL_BWD: rc = launch_pool_bwd(p->geom, ptrs, stream); break;
-            case PH_HEADS: rc = launch_heads(p->geom, ptrs, stream); break;
-            case PH_POOL_CLS: rc = launch_pool_cls(p->geom, ptrs, stream); break;
-            case PH_POOL_AVG_FWD: rc = launch_pool_avg_fwd(p->geom, ptrs, stream); break;
-            case PH_POOL_AVG_BWD: rc = launch_pool_avg_bwd(p->geom, ptrs, stream); break;
-            case PH_BN_FWD: rc = launch_bn_shared_fwd(p->geom, ptrs, stream); break;
-            case PH_BN_BWD: rc = launch_bn_shared_bwd(p->geom, ptrs, stream); break;
-            case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: rc = launch_frame_attn(p, ph.kind, ptrs, stream); break;
-            case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: rc = launch_general_attn(p, ph.kind, ptrs, stream); break;
-            case PH_RNN_POOL_FWD: case PH_RNN_CELL_FWD: case PH_RNN_CELL_BWD: case PH_RNN_POOL_BWD: rc = launch_rnn(p, ph, ptrs, stream); break;
-            case PH_TEMCONV_FWD: case PH_TEMCONV_BWD: case PH_TEMCONV_WGRAD: rc = launch_temconv(p, ph.kind, ptrs, stream); break;
-            case PH_GRAD_NORM: rc = launch_grad_norm(p->geom, ptrs.g, ptrs.ws, stream); break;
-            case PH_SGD: rc = launch_sgd(p->geom, params_rw, ptrs.g, momentum, ptrs.ws, stream); break;
-            default: rc = -1;
-        }
+        const int rc = launch_phase(p, (int)(&ph - p->phases.data()), ptrs, params_rw, momentum, stream, side);
         if (rc == -5) return TA3N_ERR_INVALID;      // (launch_gemm has set the message: an experiments-only launch list on the default library)
         if (rc != 0) return fail(TA3N_ERR_HIP, "kernel launch failed in phase kind " + std::to_string(ph.kind) + ": " +
                                                    hipGetErrorString(hipGetLastError()));
@@ -457,26 +462,7 @@ int ta3n_time_phases(ta3n_plan *p, const float *x, float *params, float *grads, 
         const int r = (ph.kind == PH_SGD || ph.kind == PH_GRAD_NORM) ? 1 : reps;
         HIP_TRY(hipEventRecord(ev[2 * i], s));
         for (int k = 0; k < r; ++k) {
-            int lrc = 0;
-            switch (ph.kind) {
-                case PH_GEMM: lrc = launch_gemm(ph, static_cast<const Task *>(p->d_tasks), static_cast<const Seg *>(p->d_segs), ptrs, p->geom.o_hyper, p->geom.o_zeros, p->geom.o_ws16, s, nullptr, static_cast<const Wait *>(p->d_waits), p->geom.pair_delta, p->phase_kinds.empty() ? 0 : p->phase_kinds[i]); break;
-                case PH_POOL_FWD: lrc = launch_pool_fwd(p->geom, ptrs, s); break;
-                case PH_LOSS: lrc = launch_loss(p->geom, ptrs, s); break;
-                case PH_POOL_BWD: lrc = launch_pool_bwd(p->geom, ptrs, s); break;
-                case PH_HEADS: lrc = launch_heads(p->geom, ptrs, s); break;
-                case PH_POOL_CLS: lrc = launch_pool_cls(p->geom, ptrs, s); break;
-                case PH_POOL_AVG_FWD: lrc = launch_pool_avg_fwd(p->geom, ptrs, s); break;
-                case PH_POOL_AVG_BWD: lrc = launch_pool_avg_bwd(p->geom, ptrs, s); break;
-                case PH_BN_FWD: lrc = launch_bn_shared_fwd(p->geom, ptrs, s); break;
-                case PH_BN_BWD: lrc = launch_bn_shared_bwd(p->geom, ptrs, s); break;
-                case PH_FRAME_ATTN_FWD: case PH_FRAME_ATTN_BWD: lrc = launch_frame_attn(p, ph.kind, ptrs, s); break;
-                case PH_GENERAL_ATTN_FWD: case PH_GENERAL_ATTN_BWD: lrc = launch_general_attn(p, ph.kind, ptrs, s); break;
-                case PH_RNN_POOL_FWD: case PH_RNN_CELL_FWD: case PH_RNN_CELL_BWD: case PH_RNN_POOL_BWD: lrc = launch_rnn(p, ph, ptrs, s); break;
-                case PH_TEMCONV_FWD: case PH_TEMCONV_BWD: case PH_TEMCONV_WGRAD: lrc = launch_temconv(p, ph.kind, ptrs, s); break;
-                case PH_GRAD_NORM: lrc = launch_grad_norm(p->geom, grads, ws, s); break;
-                case PH_SGD: lrc = launch_sgd(p->geom, params, grads, momentum, ws, s); break;
-                default: lrc = -1;
-            }
+            const int lrc = launch_phase(p, i, ptrs, params, momentum, s, nullptr);
             if (lrc != 0) {
                 for (auto &e : ev) (void)hipEventDestroy(e);
                 if (lrc == -5) return TA3N_ERR_INVALID;      // (launch_gemm has set the message: an experiments-only launch list on the default library)

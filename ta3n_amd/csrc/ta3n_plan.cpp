@@ -542,15 +542,15 @@ struct AvgpoolDa {
     }
 };
 
-// "" when the configuration is built on TA3N_AGG_TEMCONV, otherwise the refusal, naming what is not built there
-std::string temconv_refusal(const ta3n_config &c) {
+// What neither TA3N_AGG_RNN nor TA3N_AGG_TEMCONV is built with: "" when the configuration has none of it, otherwise the refusal, which
+// begins with `head` (the aggregation) and names the option
+std::string new_aggregation_refusal(const ta3n_config &c, const std::string &head) {
     const std::pair<uint32_t, const char *> flags[] = {
         {TA3N_FLAG_BF16_MFMA, "TA3N_FLAG_BF16_MFMA"}, {TA3N_FLAG_BF16_STORE, "TA3N_FLAG_BF16_STORE"}, {TA3N_FLAG_F32_SPLIT, "TA3N_FLAG_F32_SPLIT"},
         {TA3N_FLAG_MCD, "TA3N_FLAG_MCD (ens_DA MCD)"}, {TA3N_FLAG_BN_SHARED, "TA3N_FLAG_BN_SHARED (use_bn)"},
         {TA3N_FLAG_TRANS_ATTN, "TA3N_FLAG_TRANS_ATTN (use_attn TransAttn)"}, {TA3N_FLAG_ATTN_ENTROPY, "TA3N_FLAG_ATTN_ENTROPY (add_loss_DA attentive_entropy)"},
         {TA3N_FLAG_TARGET_ENTROPY, "TA3N_FLAG_TARGET_ENTROPY (add_loss_DA target_entropy)"}, {TA3N_FLAG_FRAME_ATTN, "TA3N_FLAG_FRAME_ATTN (use_attn_frame)"},
         {TA3N_FLAG_GENERAL_ATTN, "TA3N_FLAG_GENERAL_ATTN (use_attn general)"}, {TA3N_FLAG_UNSHARED, "TA3N_FLAG_UNSHARED (share_params N)"}};
-    const std::string head = "TA3N_AGG_TEMCONV (frame_aggregation temconv) with ";
     for (const auto &f : flags)
         if (c.flags & f.first) return head + f.second + " is not built";
     if (c.shared_fc_layers > 1) return head + "shared_fc_layers (--add_fc) " + std::to_string(c.shared_fc_layers) + " is not built";
@@ -563,24 +563,15 @@ std::string temconv_refusal(const ta3n_config &c) {
     return "";
 }
 
+// "" when the configuration is built on TA3N_AGG_TEMCONV, otherwise the refusal, naming what is not built there
+std::string temconv_refusal(const ta3n_config &c) {
+    return new_aggregation_refusal(c, "TA3N_AGG_TEMCONV (frame_aggregation temconv) with ");
+}
+
 // "" when the configuration is built on TA3N_AGG_RNN, otherwise the refusal, naming what is not built there
 std::string rnn_refusal(const ta3n_config &c) {
-    const std::pair<uint32_t, const char *> flags[] = {
-        {TA3N_FLAG_BF16_MFMA, "TA3N_FLAG_BF16_MFMA"}, {TA3N_FLAG_BF16_STORE, "TA3N_FLAG_BF16_STORE"}, {TA3N_FLAG_F32_SPLIT, "TA3N_FLAG_F32_SPLIT"},
-        {TA3N_FLAG_MCD, "TA3N_FLAG_MCD (ens_DA MCD)"}, {TA3N_FLAG_BN_SHARED, "TA3N_FLAG_BN_SHARED (use_bn)"},
-        {TA3N_FLAG_TRANS_ATTN, "TA3N_FLAG_TRANS_ATTN (use_attn TransAttn)"}, {TA3N_FLAG_ATTN_ENTROPY, "TA3N_FLAG_ATTN_ENTROPY (add_loss_DA attentive_entropy)"},
-        {TA3N_FLAG_TARGET_ENTROPY, "TA3N_FLAG_TARGET_ENTROPY (add_loss_DA target_entropy)"}, {TA3N_FLAG_FRAME_ATTN, "TA3N_FLAG_FRAME_ATTN (use_attn_frame)"},
-        {TA3N_FLAG_GENERAL_ATTN, "TA3N_FLAG_GENERAL_ATTN (use_attn general)"}, {TA3N_FLAG_UNSHARED, "TA3N_FLAG_UNSHARED (share_params N)"}};
-    const std::string head = "TA3N_AGG_RNN (frame_aggregation rnn) with ";
-    for (const auto &f : flags)
-        if (c.flags & f.first) return head + f.second + " is not built";
-    if (c.shared_fc_layers > 1) return head + "shared_fc_layers (--add_fc) " + std::to_string(c.shared_fc_layers) + " is not built";
-    if (c.chain) return head + "chain is not built";
-    if (c.split_k) return head + "split_k is not built";
-    if (c.wgrads_late) return head + "wgrads_late is not built";
-    for (int i = 0; i < 16; ++i)
-        if (c.phase_tiles[i]) return head + "phase_tiles is not built";
-    if (c.layout_flags) return head + "layout_flags is not built";
+    const std::string e = new_aggregation_refusal(c, "TA3N_AGG_RNN (frame_aggregation rnn) with ");
+    if (!e.empty()) return e;
     if (c.rnn_cell != 0 && c.rnn_cell != 1) return "rnn_cell must be 0 (LSTM) or 1 (GRU), not " + std::to_string(c.rnn_cell);
     if (c.n_ts < 0) return "n_ts must not be negative (0 means 5), not " + std::to_string(c.n_ts);
     return "";

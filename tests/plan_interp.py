@@ -4,8 +4,12 @@ Executes the SAME descriptor lists the HIP kernels consume (Seg / Task / Phase
 PODs exported by ta3n_debug_arrays) with numpy, so the whole wiring of the
 train step - operand offsets, K-segments, GradReverse scales, epilogues, fan-out,
 workspace layout - is validated against the oracle on a machine without a GPU.
-The pointwise phases (pool fwd/bwd, loss, grad-norm, SGD) are executed from
-their specification in the kernel headers.  Nothing here is used by the product.
+The pointwise phases (pool fwd/bwd, loss, grad-norm, SGD, BatchNorm, frame and general
+attention, the recurrent and the temporal-convolution aggregator) are executed from
+their specification in the kernel headers.  One class runs every launch kind of
+ta3n_types.h (Interp.LAUNCH); a plan may mix the families.  Parameters and regions that
+exist only under a flag or an aggregation have no Geom field: like the kernels, their
+phases find them by name when they run.  Nothing here is used by the product.
 """
 import ctypes as C
 
@@ -19,7 +23,8 @@ EPI_COLSUM = 1 << 12
 EPI_SGD = 1 << 11
 EPI_SPLITK = 1 << 15
 (PH_GEMM, PH_POOL_FWD, PH_LOSS, PH_POOL_BWD, PH_GRAD_NORM, PH_SGD, PH_HEADS, PH_POOL_CLS, PH_POOL_AVG_FWD, PH_POOL_AVG_BWD,
- PH_BN_FWD, PH_BN_BWD) = range(12)
+ PH_BN_FWD, PH_BN_BWD, PH_FRAME_ATTN_FWD, PH_FRAME_ATTN_BWD, PH_GENERAL_ATTN_FWD, PH_GENERAL_ATTN_BWD,
+ PH_RNN_POOL_FWD, PH_RNN_CELL_FWD, PH_RNN_CELL_BWD, PH_RNN_POOL_BWD, PH_TEMCONV_FWD, PH_TEMCONV_BWD, PH_TEMCONV_WGRAD) = range(23)      # ta3n_types.h: PhaseKind
 HEADS_RPW = 16
 
 
@@ -116,6 +121,10 @@ def keep_mask(seed, idx, p):
     return (u >= np.float32(p)).astype(np.float64)
 
 
+def sigmoid(x):
+    return 1.0 / (1.0 + np.exp(-x))
+
+
 class Interp:
     def __init__(self, plan, dtype=np.float64):
         assert struct_sizes_ok(), "ctypes mirrors out of date with ta3n_types.h"
@@ -132,6 +141,10 @@ class Interp:
         self.labels = np.zeros(g.B, np.int64)
         self.hy = None
         self.side = None          # scalars of the update that rides in a pipelined step's first launch: dict(lr, momentum, weight_decay, clip)
+        self._split_parts = {}    # EPI_SPLITK: the partial tile the first of a pair of tasks left, by the pair's key
+        if plan.cfg.aggregation == _lib.AGG_RNN:      # the cell (0 LSTM, 1 GRU), its steps (0 means 5) and the pooling slots, as given to the plan
+            self.lstm, self.n_ts = plan.cfg.rnn_cell == 0, plan.cfg.n_ts or 5
+            self.len_ts, self.frames = _lib.rnn_slots(g.T, self.n_ts)
 
     # ---- helpers ----
     def set_params(self, state):
@@ -204,104 +217,103 @@ class Interp:
 
     def run_task(self, ph, ti):
         BM, BN = 32 * ph.wm * max(ph.rm, 1), 32 * ph.wn * max(ph.rn, 1)
-        if True:
-            t = self.tasks[ti]
-            if t.epi & EPI_SGD:          # optimiser side job of a pipelined step's first launch: update of params [4 pad0, 4 pad1)
-                if self.side is None:
-                    return
-                g, sd = self.g, self.side
-                total = np.sqrt(self.ws[g.o_sumsq:g.o_sumsq + g.n_sumsq].sum())
-                coef = min(sd["clip"] / (total + 1e-6), 1.0) if sd["clip"] > 0 else 1.0
-                lo, hi = 4 * t.pad[0], 4 * t.pad[1]
-                d = self.G[lo:hi] * coef + sd["weight_decay"] * self.P[lo:hi]
-                self.M[lo:hi] = sd["momentum"] * self.M[lo:hi] + d
-                d = d + sd["momentum"] * self.M[lo:hi]
-                self.P[lo:hi] -= sd["lr"] * d
+        t = self.tasks[ti]
+        if t.epi & EPI_SGD:          # optimiser side job of a pipelined step's first launch: update of params [4 pad0, 4 pad1)
+            if self.side is None:
                 return
-            if t.epi & EPI_COLSUM:       # exact column sums of a table of per-workgroup partials
-                src, rows, ld = t.pad[0], t.pad[1], t.pad[2]
-                n = np.arange(t.n0, t.n_valid)
-                v = self.ws[src + np.arange(rows)[:, None] * ld + n[None, :]].sum(0)
-                self.buf(t.c_base)[t.c_off + n] = v
-                if t.epi & EPI_SUMSQ:
-                    self.ws[t.pad[3]] = float((v * v).sum())
-                return
-            if t.seg_count == 0:
-                return
-            if t.epi & EPI_SUMROWS8:
-                dst, src, rows = t.pad[0], t.pad[1], t.pad[2]
-                self.ws[dst:dst + 8] = self.ws[src:src + 8 * rows].reshape(rows, 8).sum(0)
-            nr = min(BM, t.m_valid - t.m0); nc = min(BN, t.n_valid - t.n0)
-            assert nr > 0 and nc > 0
-            acc = np.zeros((nr, nc), self.dtype)
-            rowsum = np.zeros(nr, self.dtype)
-            for si in range(t.seg_begin, t.seg_begin + t.seg_count):
-                s = self.segs[si]
-                if ph.bf16 & 16:
-                    # the Seg addresses bf16 twins in units of two elements.  A twin holds round_bf16(original) - which is what
-                    # the operand read below computes from the original - so the model reads the original; that the
-                    # twin is up to date when the kernel reads it is what the GPU test checks against this model.
-                    def untwin(off):
-                        g = self.g
-                        if off >= g.o_x16:
-                            return BASE_X, (off - g.o_x16) * 2
-                        assert not (g.o_p16 <= off < g.o_x16)      # parameter twins use BASE_P16
-                        assert off >= g.o_ws16
-                        return BASE_WS, (off - g.o_ws16) * 2
-                    # (parameter twins are addressed relative to their own region: base BASE_P16, offset in pairs of elements)
-                    ab, ao = (BASE_P, s.a_off * 2) if s.a_base == BASE_P16 else untwin(s.a_off)
-                    bb, bo = (BASE_P, s.b_off * 2) if s.b_base == BASE_P16 else untwin(s.b_off)
-                    assert s.a_base in (BASE_WS, BASE_P16) and s.b_base in (BASE_WS, BASE_P16)
-                    A = self.operand(ab, ao, s.a_ld, s.a_kmajor, t.m0, nr, s.klen)
-                    Bm = self.operand(bb, bo, s.b_ld, s.b_kmajor, t.n0, nc, s.klen)
-                    if not (ph.bf16 & 32):      # (pair twins, bit 32: hi + lo planes = the original to 16 mantissa bits; modelled as exact)
-                        A, Bm = round_bf16(A), round_bf16(Bm)
-                    rowsum += A.sum(1)          # the bias gradient of a twin-reading tile sums the rounded values
-                    acc += A @ Bm.T
-                    acc *= self.scale(s.scale_kind)
-                    continue
-                A = self.operand(s.a_base, s.a_off, s.a_ld, s.a_kmajor, t.m0, nr, s.klen)
-                rowsum += A.sum(1)
-                Bm = self.operand(s.b_base, s.b_off, s.b_ld, s.b_kmajor, t.n0, nc, s.klen)
-                if ph.bf16 and not (ph.bf16 & 32):      # TA3N_FLAG_BF16_MFMA: operands rounded to bf16, products and sums in the wide
-                    # type (TA3N_FLAG_F32_SPLIT, bit 32, is fp32-grade: modelled as exact products like the fp32 MFMA)
-                    acc += round_bf16(A) @ round_bf16(Bm).T
-                else:
-                    acc += A @ Bm.T
-                acc *= self.scale(s.scale_kind)
-            if t.epi & EPI_SPLITK:       # two tasks per tile, each over part of the K segments: the first to run leaves its partial, the second finishes
-                part = self.__dict__.setdefault("_split_parts", {})
-                key = int(t.pad[0])
-                if key not in part:
-                    part[key] = acc
-                    return
-                acc = acc + part.pop(key)
-            v = acc
-            m = np.arange(t.m0, t.m0 + nr)[:, None]
-            n = np.arange(t.n0, t.n0 + nc)[None, :]
-            if t.epi & EPI_BIAS:
-                v = v + self.buf(t.bias_base)[t.bias_off + n]
-            v = v * self.scale(t.alpha_kind)
-            if t.epi & EPI_ADD:
-                v = v + self.buf(t.add_base)[t.add_off + m * t.add_ld + n]
-            if t.epi & EPI_RELU:
-                v = np.maximum(v, 0)
-            if t.epi & EPI_MASK:
-                v = np.where(self.buf(t.aux_base)[t.aux_off + m * t.aux_ld + n] > 0, v, 0)
-            if (t.epi & (EPI_DROP_I | EPI_DROP_V)) and self.hy["train"]:
-                seed = self.hy["seed_i"] if t.epi & EPI_DROP_I else self.hy["seed_v"]
-                p = self.hy["p_drop_i"] if t.epi & EPI_DROP_I else self.hy["p_drop_v"]
-                # element id m * drop_ld + n + pad2 in uint32 (ta3n_types.h; pad2: the stream offset of a stacked shared layer, --add_fc)
-                v = v * keep_mask(seed, (m * t.drop_ld + n + (int(t.pad2) & 0xFFFFFFFF)) & 0xFFFFFFFF, p)
-            v = v * self.scale(t.gamma_kind)
-            self.buf(t.c_base)[t.c_off + m * t.c_ld + n] = v
-            if t.epi & EPI_ROWSUM_A:
-                self.buf(t.bias_base)[t.bias_off + np.arange(t.m0, t.m0 + nr)] = rowsum
+            g, sd = self.g, self.side
+            total = np.sqrt(self.ws[g.o_sumsq:g.o_sumsq + g.n_sumsq].sum())
+            coef = min(sd["clip"] / (total + 1e-6), 1.0) if sd["clip"] > 0 else 1.0
+            lo, hi = 4 * t.pad[0], 4 * t.pad[1]
+            d = self.G[lo:hi] * coef + sd["weight_decay"] * self.P[lo:hi]
+            self.M[lo:hi] = sd["momentum"] * self.M[lo:hi] + d
+            d = d + sd["momentum"] * self.M[lo:hi]
+            self.P[lo:hi] -= sd["lr"] * d
+            return
+        if t.epi & EPI_COLSUM:       # exact column sums of a table of per-workgroup partials
+            src, rows, ld = t.pad[0], t.pad[1], t.pad[2]
+            n = np.arange(t.n0, t.n_valid)
+            v = self.ws[src + np.arange(rows)[:, None] * ld + n[None, :]].sum(0)
+            self.buf(t.c_base)[t.c_off + n] = v
             if t.epi & EPI_SUMSQ:
-                self.ws[t.pad[3]] = float((v * v).sum()) + (float((rowsum * rowsum).sum()) if t.epi & EPI_ROWSUM_A else 0.0)
-            for f in range(t.fan_count):
-                mk = self.ws[t.fan_mask_off[f] + m * t.fan_ld + n]
-                self.ws[t.fan_out_off[f] + m * t.fan_ld + n] = np.where(mk > 0, v, 0)
+                self.ws[t.pad[3]] = float((v * v).sum())
+            return
+        if t.seg_count == 0:
+            return
+        if t.epi & EPI_SUMROWS8:
+            dst, src, rows = t.pad[0], t.pad[1], t.pad[2]
+            self.ws[dst:dst + 8] = self.ws[src:src + 8 * rows].reshape(rows, 8).sum(0)
+        nr = min(BM, t.m_valid - t.m0); nc = min(BN, t.n_valid - t.n0)
+        assert nr > 0 and nc > 0
+        acc = np.zeros((nr, nc), self.dtype)
+        rowsum = np.zeros(nr, self.dtype)
+        for si in range(t.seg_begin, t.seg_begin + t.seg_count):
+            s = self.segs[si]
+            if ph.bf16 & 16:
+                # the Seg addresses bf16 twins in units of two elements.  A twin holds round_bf16(original) - which is what
+                # the operand read below computes from the original - so the model reads the original; that the
+                # twin is up to date when the kernel reads it is what the GPU test checks against this model.
+                def untwin(off):
+                    g = self.g
+                    if off >= g.o_x16:
+                        return BASE_X, (off - g.o_x16) * 2
+                    assert not (g.o_p16 <= off < g.o_x16)      # parameter twins use BASE_P16
+                    assert off >= g.o_ws16
+                    return BASE_WS, (off - g.o_ws16) * 2
+                # (parameter twins are addressed relative to their own region: base BASE_P16, offset in pairs of elements)
+                ab, ao = (BASE_P, s.a_off * 2) if s.a_base == BASE_P16 else untwin(s.a_off)
+                bb, bo = (BASE_P, s.b_off * 2) if s.b_base == BASE_P16 else untwin(s.b_off)
+                assert s.a_base in (BASE_WS, BASE_P16) and s.b_base in (BASE_WS, BASE_P16)
+                A = self.operand(ab, ao, s.a_ld, s.a_kmajor, t.m0, nr, s.klen)
+                Bm = self.operand(bb, bo, s.b_ld, s.b_kmajor, t.n0, nc, s.klen)
+                if not (ph.bf16 & 32):      # (pair twins, bit 32: hi + lo planes = the original to 16 mantissa bits; modelled as exact)
+                    A, Bm = round_bf16(A), round_bf16(Bm)
+                rowsum += A.sum(1)          # the bias gradient of a twin-reading tile sums the rounded values
+                acc += A @ Bm.T
+                acc *= self.scale(s.scale_kind)
+                continue
+            A = self.operand(s.a_base, s.a_off, s.a_ld, s.a_kmajor, t.m0, nr, s.klen)
+            rowsum += A.sum(1)
+            Bm = self.operand(s.b_base, s.b_off, s.b_ld, s.b_kmajor, t.n0, nc, s.klen)
+            if ph.bf16 and not (ph.bf16 & 32):      # TA3N_FLAG_BF16_MFMA: operands rounded to bf16, products and sums in the wide
+                # type (TA3N_FLAG_F32_SPLIT, bit 32, is fp32-grade: modelled as exact products like the fp32 MFMA)
+                acc += round_bf16(A) @ round_bf16(Bm).T
+            else:
+                acc += A @ Bm.T
+            acc *= self.scale(s.scale_kind)
+        if t.epi & EPI_SPLITK:       # two tasks per tile, each over part of the K segments: the first to run leaves its partial, the second finishes
+            part = self._split_parts
+            key = int(t.pad[0])
+            if key not in part:
+                part[key] = acc
+                return
+            acc = acc + part.pop(key)
+        v = acc
+        m = np.arange(t.m0, t.m0 + nr)[:, None]
+        n = np.arange(t.n0, t.n0 + nc)[None, :]
+        if t.epi & EPI_BIAS:
+            v = v + self.buf(t.bias_base)[t.bias_off + n]
+        v = v * self.scale(t.alpha_kind)
+        if t.epi & EPI_ADD:
+            v = v + self.buf(t.add_base)[t.add_off + m * t.add_ld + n]
+        if t.epi & EPI_RELU:
+            v = np.maximum(v, 0)
+        if t.epi & EPI_MASK:
+            v = np.where(self.buf(t.aux_base)[t.aux_off + m * t.aux_ld + n] > 0, v, 0)
+        if (t.epi & (EPI_DROP_I | EPI_DROP_V)) and self.hy["train"]:
+            seed = self.hy["seed_i"] if t.epi & EPI_DROP_I else self.hy["seed_v"]
+            p = self.hy["p_drop_i"] if t.epi & EPI_DROP_I else self.hy["p_drop_v"]
+            # element id m * drop_ld + n + pad2 in uint32 (ta3n_types.h; pad2: the stream offset of a stacked shared layer, --add_fc)
+            v = v * keep_mask(seed, (m * t.drop_ld + n + (int(t.pad2) & 0xFFFFFFFF)) & 0xFFFFFFFF, p)
+        v = v * self.scale(t.gamma_kind)
+        self.buf(t.c_base)[t.c_off + m * t.c_ld + n] = v
+        if t.epi & EPI_ROWSUM_A:
+            self.buf(t.bias_base)[t.bias_off + np.arange(t.m0, t.m0 + nr)] = rowsum
+        if t.epi & EPI_SUMSQ:
+            self.ws[t.pad[3]] = float((v * v).sum()) + (float((rowsum * rowsum).sum()) if t.epi & EPI_ROWSUM_A else 0.0)
+        for f in range(t.fan_count):
+            mk = self.ws[t.fan_mask_off[f] + m * t.fan_ld + n]
+            self.ws[t.fan_out_off[f] + m * t.fan_ld + n] = np.where(mk > 0, v, 0)
 
     @staticmethod
     def soft2(z):
@@ -315,18 +327,68 @@ class Interp:
         n = int(np.prod(shape))
         return self.ws[off:off + n].reshape(shape)
 
-    def run_pool_fwd(self):
+    def reg(self, name, shape):
+        """View of a workspace region the Geom has no field for, found by name as the kernels' host code finds it."""
+        return self.r(self.plan.region(name)[0], shape)
+
+    def param(self, name):
+        """Offset in P / G of a parameter the Geom has no field for."""
+        return next(off for n, off, _, _ in self.plan.params if n == name)
+
+    def w2(self, j):
+        """(W2_j [2, NB], b2_j [2]): the relation domain classifier of scale j."""
+        g = self.g
+        return self.P[g.p_W2_0 + j * g.p_W2_stride:][:2 * g.NB].reshape(2, g.NB), self.P[g.p_b2_0 + j * g.p_b2_stride:][:2]
+
+    def store_pooled(self, V):
+        """V and Vd = dropout_v(V) of the pooled feature [B, width] to their regions.  Returns the mask Vd = V * mask: keep / (1 - p)
+        on the element ids b * width + k of seed_v's stream, ones outside training or at p = 0."""
         g, h = self.g, self.hy
-        B, NR, NB, NT = g.B, g.n_rel, g.NB, g.n_tuples
-        Hr = self.r(g.o_Hr, (B, NR, NB)); Zr = self.r(g.o_Zr, (B, NT, NB))
-        R = self.r(g.o_R, (B, NR, NB)); Pr = self.r(g.o_Pr, (B, NR, 2)); attn = self.r(g.o_attn, (B, NR))
+        B, width = V.shape
+        mk = np.ones((B, width), self.dtype)
+        if h["train"] and h["p_drop_v"] > 0:
+            idx = np.arange(B)[:, None] * width + np.arange(width)[None, :]
+            mk = keep_mask(h["seed_v"], idx, h["p_drop_v"]) * self.scale(5)
+        self.r(g.o_V, (B, width))[:] = V
+        self.r(g.o_Vd, (B, width))[:] = V * mk
+        return mk
+
+    def grad_at_pooled(self, width):
+        """gVt [B, width], plus the caller's gradient at the pooled feature under TA3N_FLAG_FEATURE_GRADS."""
+        g = self.g
+        gv = self.r(g.o_gVt, (g.B, width))
+        return gv + self.r(g.o_gV_ext, (g.B, width)) if g.o_gV_ext > 0 else gv
+
+    def store_frame_grad(self, gF1):
+        """The aggregator's gradient at the frames [B, T, F]: to gZ1 directly (through F1's ReLU and dropout_i scale) where no frame
+        discriminator is live, otherwise to gRa, the additive base of the launch that adds the discriminator's share."""
+        g = self.g
+        shape = (g.B, g.T, g.F)
+        if g.o_gHf < 0:
+            self.r(g.o_gZ1, shape)[:] = np.where(self.r(g.o_F1, shape) > 0, gF1.reshape(shape) * self.scale(4), 0.0)
+        else:
+            self.r(g.o_gRa, shape)[:] = gF1.reshape(shape)
+
+    def relation_sums(self):
+        """Pr_j = Hr_j W2_j^T + b2_j and R_j = the sum of scale j's tuples of Zr, written to their regions; returns (R, Pr)."""
+        g = self.g
+        B, NR, NB = g.B, g.n_rel, g.NB
+        Hr = self.r(g.o_Hr, (B, NR, NB)); Zr = self.r(g.o_Zr, (B, g.n_tuples, NB))
+        R = self.r(g.o_R, (B, NR, NB)); Pr = self.r(g.o_Pr, (B, NR, 2))
+        for j in range(NR):
+            W2, b2 = self.w2(j)
+            Pr[:, j, :] = Hr[:, j, :] @ W2.T + b2
+            R[:, j, :] = Zr[:, self.tf[j]:self.tf[j + 1], :].sum(1)
+        return R, Pr
+
+    def run_pool_fwd(self):
+        g = self.g
+        B, NR, NB = g.B, g.n_rel, g.NB
+        R, Pr = self.relation_sums()
+        attn = self.r(g.o_attn, (B, NR))
         attn_on = bool(g.flags & _lib.FLAG_TRANS_ATTN)
         V = np.zeros((B, NB), self.dtype)
         for j in range(NR):
-            W2 = self.P[g.p_W2_0 + j * g.p_W2_stride:][:2 * NB].reshape(2, NB)
-            b2 = self.P[g.p_b2_0 + j * g.p_b2_stride:][:2]
-            Pr[:, j, :] = Hr[:, j, :] @ W2.T + b2
-            R[:, j, :] = Zr[:, self.tf[j]:self.tf[j + 1], :].sum(1)
             if attn_on:
                 _, _, H = self.soft2(Pr[:, j, :])
                 w = 1 - H
@@ -335,12 +397,7 @@ class Interp:
             else:
                 attn[:, j] = R[:, j, 0]
                 V += R[:, j, :]
-        self.r(g.o_V, (B, NB))[:] = V
-        Vd = V
-        if h["train"] and h["p_drop_v"] > 0:
-            idx = np.arange(B)[:, None] * NB + np.arange(NB)[None, :]
-            Vd = V * keep_mask(h["seed_v"], idx, h["p_drop_v"]) * self.scale(5)
-        self.r(g.o_Vd, (B, NB))[:] = Vd
+        self.store_pooled(V)
 
     def run_pool_cls(self):
         """TA3N_AGG_AVGPOOL: mean over segments, dropout_v, classifier, CE on the valid source rows and the way back to gZ1
@@ -349,14 +406,10 @@ class Interp:
         B, T, F, Cn = g.B, g.T, g.F, g.C
         F1 = self.r(g.o_F1, (B, T, F))
         V = F1.mean(1)
-        mk = np.ones((B, F), self.dtype)
-        if h["train"] and h["p_drop_v"] > 0:
-            idx = np.arange(B)[:, None] * F + np.arange(F)[None, :]
-            mk = keep_mask(h["seed_v"], idx, h["p_drop_v"]) * self.scale(5)
-        Vd = V * mk
+        mk = self.store_pooled(V)
         Wcv = self.P[g.p_Wcv:g.p_Wcv + Cn * F].reshape(Cn, F); bcv = self.P[g.p_bcv:g.p_bcv + Cn]
-        Y = Vd @ Wcv.T + bcv
-        self.r(g.o_V, (B, F))[:] = V; self.r(g.o_Vd, (B, F))[:] = Vd; self.r(g.o_Y, (B, Cn))[:] = Y
+        Y = (V * mk) @ Wcv.T + bcv
+        self.r(g.o_Y, (B, Cn))[:] = Y
         b = np.arange(B)
         on = (b < g.Bs) & (b < h["valid_source"])
         m = Y.max(1, keepdims=True); lp = Y - m - np.log(np.exp(Y - m).sum(1, keepdims=True)); p = np.exp(lp)
@@ -370,29 +423,14 @@ class Interp:
 
     def run_pool_avg_fwd(self):
         """TA3N_AGG_AVGPOOL, general: V = mean over the segments, Vd = dropout_v(V) (ta3n_pointwise.hip: pool_avg_fwd_kernel)."""
-        g, h = self.g, self.hy
-        B, T, F = g.B, g.T, g.F
-        V = self.r(g.o_F1, (B, T, F)).mean(1)
-        mk = np.ones((B, F), self.dtype)
-        if h["train"] and h["p_drop_v"] > 0:
-            idx = np.arange(B)[:, None] * F + np.arange(F)[None, :]
-            mk = keep_mask(h["seed_v"], idx, h["p_drop_v"]) * self.scale(5)
-        self.r(g.o_V, (B, F))[:] = V
-        self.r(g.o_Vd, (B, F))[:] = V * mk
+        g = self.g
+        self.store_pooled(self.r(g.o_F1, (g.B, g.T, g.F)).mean(1))
         self.ws[g.o_losses:g.o_losses + 8] = 0
 
     def run_pool_avg_bwd(self):
-        """gVt / T spread over the segments: gZ1 directly (no frame discriminator) or the additive base of its launch."""
+        """gVt / T spread over the segments."""
         g = self.g
-        B, T, F = g.B, g.T, g.F
-        gv = self.r(g.o_gVt, (B, F))
-        if g.o_gV_ext > 0:       # TA3N_FLAG_FEATURE_GRADS: the caller's gradient at V
-            gv = gv + self.r(g.o_gV_ext, (B, F))
-        base = np.repeat(gv / T, T, axis=0)
-        if g.o_gHf < 0:
-            self.r(g.o_gZ1, (B * T, F))[:] = np.where(self.r(g.o_F1, (B * T, F)) > 0, base * self.scale(4), 0.0)
-        else:
-            self.r(g.o_gRa, (B * T, F))[:] = base
+        self.store_frame_grad(np.repeat(self.grad_at_pooled(g.F) / g.T, g.T, axis=0))
 
     def run_loss(self):
         g, h = self.g, self.hy
@@ -433,6 +471,16 @@ class Interp:
         gPf, l_frm = rows(Pf, T, _lib.FLAG_ADV_FRAME, h["inv_n_frm"])
         self.r(g.o_gPr, (B * NR, 2))[:] = gPr; self.r(g.o_gPf, (B * T, 2))[:] = gPf
         self.ws[g.o_losses:g.o_losses + 6] = [l_cls + l_rel + l_vid + l_frm + h["gamma"] * l_ent, l_cls, l_rel, l_vid, l_frm, l_ent]
+        if g.flags & _lib.FLAG_TARGET_LABELS:
+            # main.py:442-446: the class cross-entropy runs over the valid rows of both halves; the target rows' share joins the source
+            # rows' above (inv_n_cls = 1 / (n_s + n_t) from the caller)
+            rows = g.Bs + np.arange(min(h["valid_target"], g.Bt))
+            z = Y[rows]
+            m = z.max(1, keepdims=True); lp = z - m - np.log(np.exp(z - m).sum(1, keepdims=True))
+            onehot = np.zeros_like(z); onehot[np.arange(len(rows)), self.labels[rows]] = 1
+            self.r(g.o_gY, (B, Cn))[rows] += (np.exp(lp) - onehot) * h["inv_n_cls"]
+            l = float(-lp[np.arange(len(rows)), self.labels[rows]].sum() * h["inv_n_cls"])
+            self.ws[g.o_losses] += l; self.ws[g.o_losses + 1] += l
 
     def _bn_rows(self, dom):
         g = self.g
@@ -491,14 +539,12 @@ class Interp:
     def run_pool_bwd(self):
         g = self.g
         B, NR, NB = g.B, g.n_rel, g.NB
-        gVt = self.r(g.o_gVt, (B, NB)); R = self.r(g.o_R, (B, NR, NB)); Pr = self.r(g.o_Pr, (B, NR, 2))
-        if g.o_gV_ext > 0:       # TA3N_FLAG_FEATURE_GRADS: the caller's gradient at the pooled feature joins here
-            gVt = gVt + self.r(g.o_gV_ext, (B, NB))
+        gVt = self.grad_at_pooled(NB); R = self.r(g.o_R, (B, NR, NB)); Pr = self.r(g.o_Pr, (B, NR, 2))
         gPr = self.r(g.o_gPr, (B, NR, 2)); gattn = self.r(g.o_gattn, (B, NR)); Hr = self.r(g.o_Hr, (B, NR, NB))
         gPrT = self.r(g.o_gPrT, (B, NR, 2)); gRa = self.r(g.o_gRa, (B, NR, NB)); gHr = self.r(g.o_gHr, (B, NR, NB))
         attn_on = bool(g.flags & _lib.FLAG_TRANS_ATTN)
         for j in range(NR):
-            W2 = self.P[g.p_W2_0 + j * g.p_W2_stride:][:2 * NB].reshape(2, NB)
+            W2, _ = self.w2(j)
             gp = gPr[:, j, :].copy(); w1 = np.ones(B, self.dtype)
             if attn_on:
                 dot = (R[:, j, :] * gVt).sum(1) + gattn[:, j]
@@ -565,19 +611,199 @@ class Interp:
         d = d + h["momentum"] * self.M[:n]
         self.P[:n] -= h["lr"] * d
 
+    # ---- TA3N_FLAG_FRAME_ATTN (ta3n_pointwise.hip: frame_attn_fwd_kernel / frame_attn_bwd_kernel) ----
+    def run_frame_attn_fwd(self):
+        g = self.g
+        BT, F = g.B * g.T, g.F
+        _, _, H = self.soft2(self.r(g.o_Pf, (BT, 2)))
+        w = 1 - H
+        self.reg("attn_frame", (BT,))[:] = w
+        self.reg("F1a", (BT, F))[:] = (1 + w)[:, None] * self.r(g.o_F1, (BT, F))
+
+    def run_frame_attn_bwd(self):
+        g = self.g
+        BT, F = g.B * g.T, g.F
+        p, lp, H = self.soft2(self.r(g.o_Pf, (BT, 2)))
+        gin = self.reg("gF1a", (BT, F)).copy()
+        d = (gin * self.r(g.o_F1, (BT, F))).sum(1)
+        self.reg("gPfT", (BT, 2))[:] = self.r(g.o_gPf, (BT, 2)) + d[:, None] * p * (lp + H[:, None])
+        # (1 + w) gF1a goes to a region of its own, or into gRa where that is large enough
+        base = self.reg("gF1s", (BT, F)) if "gF1s" in self.plan.regions else self.r(g.o_gRa, (BT, F))
+        base[:] = (1 + (1 - H))[:, None] * gin
+
+    # ---- TA3N_FLAG_GENERAL_ATTN (ta3n_pointwise.hip: general_attn_fwd_kernel / general_attn_bwd_kernel) ----
+    def wa2(self):
+        """(weight [NB], bias) of the attention layer's second Linear."""
+        return self.P[self.param("attn_layer.2.weight"):][:self.g.NB], self.P[self.param("attn_layer.2.bias")]
+
+    def run_general_attn_fwd(self):
+        """Pr and R as pool_fwd; A = tanh(U) in place; w = softmax_j(<A_j, wa2> + ba2); V = sum_j (1 + w_j) R_j; Vd; losses cleared."""
+        g = self.g
+        B, NR, NB = g.B, g.n_rel, g.NB
+        R, _ = self.relation_sums()
+        Ua = self.reg("Ua", (B, NR, NB))
+        Ua[:] = np.tanh(Ua)
+        wa2, ba2 = self.wa2()
+        s = Ua @ wa2 + ba2
+        e = np.exp(s - s.max(1, keepdims=True))
+        w = e / e.sum(1, keepdims=True)
+        self.r(g.o_attn, (B, NR))[:] = w
+        self.store_pooled(((1 + w)[:, :, None] * R).sum(1))
+        self.ws[g.o_losses:g.o_losses + 8] = 0
+
+    def run_general_attn_bwd(self):
+        """d_j = <R_j, gv> + g_attn; gs = w (d - sum_k w_k d_k); gUa = gs wa2 (1 - A^2); gRa = (1 + w) gv; gPrT = gPr; gHr from gPr."""
+        g = self.g
+        B, NR, NB = g.B, g.n_rel, g.NB
+        gv = self.grad_at_pooled(NB)
+        R = self.r(g.o_R, (B, NR, NB)); w = self.r(g.o_attn, (B, NR)); A = self.reg("Ua", (B, NR, NB))
+        d = (R * gv[:, None, :]).sum(2) + self.r(g.o_gattn, (B, NR))
+        gs = w * (d - (w * d).sum(1, keepdims=True))
+        self.reg("gs", (B, NR))[:] = gs
+        wa2, _ = self.wa2()
+        self.reg("gUa", (B, NR, NB))[:] = gs[:, :, None] * wa2[None, None, :] * (1 - A * A)
+        self.r(g.o_gRa, (B, NR, NB))[:] = (1 + w)[:, :, None] * gv[:, None, :]
+        gPr = self.r(g.o_gPr, (B, NR, 2)); Hr = self.r(g.o_Hr, (B, NR, NB))
+        self.r(g.o_gPrT, (B, NR, 2))[:] = gPr
+        gHr = self.r(g.o_gHr, (B, NR, NB))
+        for j in range(NR):
+            gHr[:, j, :] = np.where(Hr[:, j, :] > 0, gPr[:, j, :] @ self.w2(j)[0], 0)
+
+    # ---- TA3N_AGG_RNN (ta3n_rnn.hip): slot max-pooling, one LSTM / GRU cell step, and both ways back ----
+    def rnn_regions(self):
+        g, n, G = self.g, self.n_ts, 4 if self.lstm else 3
+        B, F = g.B, g.F
+        return dict(Xp=self.reg("rnn_Xp", (n, B, F)), Gx=self.reg("rnn_Gx", (n, B, G, F)), Gh=self.reg("rnn_Gh", (n, B, G, F)),
+                    act=self.reg("rnn_gates", (n, B, G, F)), c=self.reg("rnn_c", (n + 1, B, F)), h=self.reg("rnn_h", (n + 1, B, F)),
+                    gGx=self.reg("rnn_gGx", (n, B, G, F)), gGh=self.reg("rnn_gGh", (n, B, G, F)), gc=self.reg("rnn_gc", (n, B, F)),
+                    gh=self.reg("rnn_gh", (B, F)), ghd=self.reg("rnn_ghd", (B, F)), gXp=self.reg("rnn_gXp", (n, B, F)))
+
+    def run_rnn_pool_fwd(self):
+        g, t = self.g, self.rnn_regions()
+        F1 = self.r(g.o_F1, (g.B, g.T, g.F))
+        for j in range(self.n_ts):
+            t["Xp"][j] = F1[:, self.frames[j * self.len_ts:(j + 1) * self.len_ts], :].max(1)
+        t["h"][0] = 0
+        if self.lstm:
+            t["c"][0] = 0
+
+    def run_rnn_cell_fwd(self, s):
+        g, t = self.g, self.rnn_regions()
+        x, r, act = t["Gx"][s], t["Gh"][s], t["act"][s]
+        if self.lstm:
+            pre = x + r
+            act[:, 0], act[:, 1], act[:, 2], act[:, 3] = sigmoid(pre[:, 0]), sigmoid(pre[:, 1]), np.tanh(pre[:, 2]), sigmoid(pre[:, 3])
+            t["c"][s + 1] = act[:, 1] * t["c"][s] + act[:, 0] * act[:, 2]
+            t["h"][s + 1] = act[:, 3] * np.tanh(t["c"][s + 1])
+        else:
+            act[:, 0], act[:, 1] = sigmoid(x[:, 0] + r[:, 0]), sigmoid(x[:, 1] + r[:, 1])
+            act[:, 2] = np.tanh(x[:, 2] + act[:, 0] * r[:, 2])
+            t["h"][s + 1] = (1 - act[:, 1]) * act[:, 2] + act[:, 1] * t["h"][s]
+        if s == self.n_ts - 1:
+            self.store_pooled(t["h"][s + 1])
+            self.ws[g.o_losses:g.o_losses + 8] = 0
+
+    def run_rnn_cell_bwd(self, s):
+        t = self.rnn_regions()
+        last = s == self.n_ts - 1
+        gh = self.grad_at_pooled(self.g.F).copy() if last else t["gh"].copy()
+        act, gGx, gGh = t["act"][s], t["gGx"][s], t["gGh"][s]
+        if self.lstm:
+            i, f, gg, o = act[:, 0], act[:, 1], act[:, 2], act[:, 3]
+            tc = np.tanh(t["c"][s + 1])
+            gc = gh * o * (1 - tc * tc) + (0 if last else t["gc"][s + 1])
+            gGx[:, 0] = gc * gg * i * (1 - i); gGx[:, 1] = gc * t["c"][s] * f * (1 - f)
+            gGx[:, 2] = gc * i * (1 - gg * gg); gGx[:, 3] = gh * tc * o * (1 - o)
+            gGh[:] = gGx
+            t["gc"][s] = gc * f
+            t["ghd"][:] = 0
+        else:
+            r, z, n = act[:, 0], act[:, 1], act[:, 2]
+            dn = gh * (1 - z) * (1 - n * n)
+            gGx[:, 2] = dn; gGh[:, 2] = dn * r
+            gGx[:, 1] = gGh[:, 1] = gh * (t["h"][s] - n) * z * (1 - z)
+            gGx[:, 0] = gGh[:, 0] = dn * t["Gh"][s][:, 2] * r * (1 - r)
+            t["ghd"][:] = gh * z
+
+    def run_rnn_pool_bwd(self):
+        """The lowest frame index among equal candidates takes the window's gradient; frames in no window get zero."""
+        g, t = self.g, self.rnn_regions()
+        B, T, F = g.B, g.T, g.F
+        F1 = self.r(g.o_F1, (B, T, F))
+        out = np.zeros((B, T, F), self.dtype)
+        for j in range(self.n_ts):
+            fr = np.asarray(self.frames[j * self.len_ts:(j + 1) * self.len_ts])
+            first = F1[:, fr, :].argmax(1)                      # numpy's argmax returns the first maximum
+            b, k = np.meshgrid(np.arange(B), np.arange(F), indexing="ij")
+            np.add.at(out, (b, fr[first], k), t["gXp"][j])
+        self.store_frame_grad(out)
+
+    # ---- TA3N_AGG_TEMCONV (ta3n_temconv.hip): the 3-tap filter over the segments + ReLU + mean, its way back, the parameter gradients ----
+    def temconv_z(self):
+        """(F1 padded with one zero row on either side [B, T + 2, F], Z [B, T, F], the taps w [3])."""
+        g = self.g
+        pad = np.zeros((g.B, g.T + 2, g.F), self.dtype)
+        pad[:, 1:-1] = self.r(g.o_F1, (g.B, g.T, g.F))
+        w, c = self.P[self.param("tcl_3_1.conv2d.weight"):][:3], self.P[self.param("tcl_3_1.conv2d.bias")]
+        return pad, w[0] * pad[:, :-2] + w[1] * pad[:, 1:-1] + w[2] * pad[:, 2:] + c, w
+
+    def run_temconv_fwd(self):
+        g = self.g
+        self.store_pooled(np.maximum(self.temconv_z()[1], 0).mean(1))
+        self.ws[g.o_losses:g.o_losses + 8] = 0
+
+    def run_temconv_bwd(self):
+        g = self.g
+        B, T, F = g.B, g.T, g.F
+        pad, Z, w = self.temconv_z()
+        gR = np.where(Z > 0, self.grad_at_pooled(F)[:, None, :] / T, 0.0)
+        gRp = np.zeros((B, T + 2, F), self.dtype)
+        gRp[:, 1:-1] = gR
+        self.store_frame_grad(w[0] * gRp[:, 2:] + w[1] * gRp[:, 1:-1] + w[2] * gRp[:, :-2])      # gF1[t] = w0 gR[t+1] + w1 gR[t] + w2 gR[t-1]
+        part = self.reg("tc_part", (B, 4))
+        for j in range(3):
+            part[:, j] = (gR * pad[:, j:j + T]).sum((1, 2))
+        part[:, 3] = gR.sum((1, 2))
+
+    def run_temconv_wgrad(self):
+        g = self.g
+        d = self.reg("tc_part", (g.B, 4)).sum(0)
+        p_w = self.param("tcl_3_1.conv2d.weight")
+        self.G[p_w:p_w + 3] = d[:3]
+        self.G[self.param("tcl_3_1.conv2d.bias")] = d[3]
+        self.ws[g.o_sumsq + g.n_sumsq - 1] = (d * d).sum()
+
+    # kind -> what runs it, as f(interpreter, phase, fused_norm): the one place a launch kind is wired to its specification
+    LAUNCH = {
+        PH_GEMM: lambda it, ph, fused_norm: it.run_gemm(ph),
+        PH_POOL_FWD: lambda it, ph, fused_norm: it.run_pool_fwd(),
+        PH_LOSS: lambda it, ph, fused_norm: it.run_loss(),
+        PH_POOL_BWD: lambda it, ph, fused_norm: it.run_pool_bwd(),
+        PH_GRAD_NORM: lambda it, ph, fused_norm: None,      # (run_sgd forms the norm itself)
+        PH_SGD: lambda it, ph, fused_norm: it.run_sgd(fused_norm),
+        PH_HEADS: lambda it, ph, fused_norm: it.run_heads(),
+        PH_POOL_CLS: lambda it, ph, fused_norm: it.run_pool_cls(),
+        PH_POOL_AVG_FWD: lambda it, ph, fused_norm: it.run_pool_avg_fwd(),
+        PH_POOL_AVG_BWD: lambda it, ph, fused_norm: it.run_pool_avg_bwd(),
+        PH_BN_FWD: lambda it, ph, fused_norm: it.run_bn_fwd(),
+        PH_BN_BWD: lambda it, ph, fused_norm: it.run_bn_bwd(),
+        PH_FRAME_ATTN_FWD: lambda it, ph, fused_norm: it.run_frame_attn_fwd(),
+        PH_FRAME_ATTN_BWD: lambda it, ph, fused_norm: it.run_frame_attn_bwd(),
+        PH_GENERAL_ATTN_FWD: lambda it, ph, fused_norm: it.run_general_attn_fwd(),
+        PH_GENERAL_ATTN_BWD: lambda it, ph, fused_norm: it.run_general_attn_bwd(),
+        PH_RNN_POOL_FWD: lambda it, ph, fused_norm: it.run_rnn_pool_fwd(),
+        PH_RNN_CELL_FWD: lambda it, ph, fused_norm: it.run_rnn_cell_fwd(ph.task_begin),      # a cell phase's step is its task_begin
+        PH_RNN_CELL_BWD: lambda it, ph, fused_norm: it.run_rnn_cell_bwd(ph.task_begin),
+        PH_RNN_POOL_BWD: lambda it, ph, fused_norm: it.run_rnn_pool_bwd(),
+        PH_TEMCONV_FWD: lambda it, ph, fused_norm: it.run_temconv_fwd(),
+        PH_TEMCONV_BWD: lambda it, ph, fused_norm: it.run_temconv_bwd(),
+        PH_TEMCONV_WGRAD: lambda it, ph, fused_norm: it.run_temconv_wgrad(),
+    }
+
     def run_group(self, group, fused_norm=False):
         for ph in self.phases:
             if ph.group != group:
                 continue
-            if ph.kind == PH_GEMM: self.run_gemm(ph)
-            elif ph.kind == PH_POOL_FWD: self.run_pool_fwd()
-            elif ph.kind == PH_LOSS: self.run_loss()
-            elif ph.kind == PH_POOL_BWD: self.run_pool_bwd()
-            elif ph.kind == PH_HEADS: self.run_heads()
-            elif ph.kind == PH_POOL_CLS: self.run_pool_cls()
-            elif ph.kind == PH_POOL_AVG_FWD: self.run_pool_avg_fwd()
-            elif ph.kind == PH_POOL_AVG_BWD: self.run_pool_avg_bwd()
-            elif ph.kind == PH_BN_FWD: self.run_bn_fwd()
-            elif ph.kind == PH_BN_BWD: self.run_bn_bwd()
-            elif ph.kind == PH_GRAD_NORM: pass
-            elif ph.kind == PH_SGD: self.run_sgd(fused_norm)
+            if ph.kind not in self.LAUNCH:
+                raise NotImplementedError(f"phase kind {ph.kind} (group {group}) has no entry in Interp.LAUNCH")
+            self.LAUNCH[ph.kind](self, ph, fused_norm)

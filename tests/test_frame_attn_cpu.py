@@ -1,5 +1,5 @@
 """--use_attn_frame TransAttn (models.py:368-377, 612-614: every frame feature scaled by 1 + (1 - H(frame-discriminator softmax))
-in front of the TRN, the weights not detached) on the CPU: the new plans executed with numpy (tests/plan_interp_frame_attn.py)
+in front of the TRN, the weights not detached) on the CPU: the new plans executed with numpy (tests/plan_interp.py)
 against fixtures the reference produced (tests/golden/make_golden_frame_attn.py), the launch order, the plans without the flag
 left as they were, and the option handling at the plan, TrainEngine, VideoModel, train_ddp.py and main.py levels."""
 import os
@@ -9,8 +9,7 @@ import pytest
 import torch
 
 from golden_util import Golden, case_config, step_schedule
-from plan_interp import plan_arrays
-from plan_interp_frame_attn import PH_FRAME_ATTN_BWD, PH_FRAME_ATTN_FWD, FrameAttnInterp
+from plan_interp import PH_FRAME_ATTN_BWD, PH_FRAME_ATTN_FWD, Interp, plan_arrays
 from ta3n_amd import _lib
 from ta3n_amd.engine import flags_from_options, frame_attn_refusal
 from ta3n_amd.synthetic import synth_batch, synth_state
@@ -45,7 +44,7 @@ def test_plan_reproduces_reference(name, extra):
     T = c["T"]
     plan = _plan(c, faf_flags(c) | extra)
     assert not plan.has_fused_step
-    it = FrameAttnInterp(plan)
+    it = Interp(plan)
     shapes = {n: s for n, _, s, _ in plan.params}
     it.set_params(synth_state(shapes, seed=c["wseed"], scale=c["wscale"]))
     live = {n for n, _, _, lv in plan.params if lv}
@@ -93,7 +92,7 @@ def test_padded_rows_contribute_no_gradient():
     c = case_config(g)
     T = c["T"]
     plan = _plan(c, FAF)
-    it = FrameAttnInterp(plan)
+    it = Interp(plan)
     it.set_params(synth_state({n: s for n, _, s, _ in plan.params}, seed=c["wseed"], scale=c["wscale"]))
     st = step_schedule(c)[-1]
     assert (st["n_src"], st["n_tgt"]) == (5, 3)

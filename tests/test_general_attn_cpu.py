@@ -1,5 +1,5 @@
 """--use_attn general (models.py:320-325, 359-366, 379-388: the relation features weighted by the softmax over the relations of a
-learned layer's scores) on the CPU: the new plans executed with numpy (tests/plan_interp_general_attn.py) against fixtures the
+learned layer's scores) on the CPU: the new plans executed with numpy (tests/plan_interp.py) against fixtures the
 reference produced (tests/golden/make_golden_general_attn.py), the launch order, the plans without the flag left as they were, and
 the option handling at the plan, TrainEngine, VideoModel, train_ddp.py and main.py levels."""
 import json
@@ -11,8 +11,7 @@ import pytest
 import torch
 
 from golden_util import Golden, case_config, step_schedule
-from plan_interp import plan_arrays
-from plan_interp_general_attn import PH_GENERAL_ATTN_BWD, PH_GENERAL_ATTN_FWD, GeneralAttnInterp
+from plan_interp import PH_GENERAL_ATTN_BWD, PH_GENERAL_ATTN_FWD, Interp, plan_arrays
 from ta3n_amd import _lib
 from ta3n_amd.engine import flags_from_options, general_attn_refusal
 from ta3n_amd.synthetic import synth_batch, synth_state
@@ -60,7 +59,7 @@ def test_plan_reproduces_reference(name, extra):
     T = c["T"]
     plan = _plan(c, ga_flags(c) | extra)
     assert not plan.has_fused_step
-    it = GeneralAttnInterp(plan)
+    it = Interp(plan)
     shapes = {n: s for n, _, s, _ in plan.params}
     it.set_params(synth_state(shapes, seed=c["wseed"], scale=c["wscale"]))
     live = {n for n, _, _, lv in plan.params if lv}
@@ -127,7 +126,7 @@ def test_padded_rows_contribute_no_gradient():
     g = Golden("tiny_ga_T5")
     c = case_config(g)
     plan = _plan(c, GA)
-    it = GeneralAttnInterp(plan)
+    it = Interp(plan)
     it.set_params(synth_state({n: s for n, _, s, _ in plan.params}, seed=c["wseed"], scale=c["wscale"]))
     st = step_schedule(c)[-1]
     assert (st["n_src"], st["n_tgt"]) == (5, 3)

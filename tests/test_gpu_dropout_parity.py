@@ -320,7 +320,7 @@ def test_add_fc_2_layers_draw_the_offset_streams(fused, capsys):
 def test_frame_attention_lists(capsys):
     """--use_attn_frame TransAttn (tiny_faf_T5; the option's unfused lists), p 0.5 / 0.5: pattern check on F1 (the un-attended frame
     features) and Vd, gradients against the float64 interpreter with the two frame-attention phases."""
-    from plan_interp_frame_attn import FrameAttnInterp
+    from plan_interp import Interp
     c = case_config(Golden("tiny_faf_T5"))
     Bs, Bt, T, D, Fc, Cn, p_i, p_v = c["Bs"], c["Bt"], c["T"], c["D"], c["fc_dim"], c["C"], 0.5, 0.5
     flags = flags_from_options(("Y", "Y", "Y"), "attentive_entropy", "TransAttn", "RevGrad", "uSv", use_attn_frame="TransAttn")
@@ -341,7 +341,7 @@ def test_frame_attention_lists(capsys):
                         torch.cat(mk["keep_v"]), p_v, "frame attention")
     with capsys.disabled():
         print(f"\n[dropout parity] frame attention: excluded share {share:.2%}")
-    _against_interpreter(eng, FrameAttnInterp(eng.plan), state, xs, xt, ys, _interp_hyper(Bs, Bt, T, p_i, p_v, 0), False, "frame attention", capsys)
+    _against_interpreter(eng, Interp(eng.plan), state, xs, xt, ys, _interp_hyper(Bs, Bt, T, p_i, p_v, 0), False, "frame attention", capsys)
 
 
 def test_module_path_forward_uses_the_drawn_seeds():

@@ -539,3 +539,27 @@ def test_unfused_lists_read_twins_on_cpu(monkeypatch):
     monkeypatch.setenv("TA3N_UNFUSED_TWINS", "1")
     mcd = Interp(_lib.Plan(c["Bs"], c["Bt"], T, c["D"], c["fc_dim"], c["C"], flags | _lib.FLAG_MCD))      # (no fused step: the unfused lists are all there is)
     assert len([ph for ph in mcd.phases if ph.group in (0, 2) and ph.kind == 0 and (ph.bf16 & 16)]) >= 5
+
+
+def test_interpreter_names_every_phase_kind_of_the_header():
+    """The interpreter's PH_* names and numbers are exactly the PhaseKind enum of ta3n_types.h, and its table runs each of them."""
+    import os
+    import re
+
+    import plan_interp
+    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ta3n_amd", "csrc", "ta3n_types.h")
+    body = re.search(r"enum PhaseKind : int32_t \{(.*?)\};", open(header).read(), re.S).group(1)
+    enum = {name: int(value) for name, value in re.findall(r"^\s*(PH_\w+) = (\d+),", body, re.M)}
+    assert len(enum) == 23 and sorted(enum.values()) == list(range(23))
+    assert {k: v for k, v in vars(plan_interp).items() if k.startswith("PH_")} == enum
+    assert set(Interp.LAUNCH) == set(enum.values())
+
+
+def test_interpreter_refuses_a_phase_kind_it_does_not_know():
+    """A kind outside the table is an error that names the kind and the group, never a launch skipped in silence."""
+    from types import SimpleNamespace
+    it = Interp(_lib.Plan(6, 4, 5, 512, 64, 12, ALL_FLAGS))
+    it.phases = [SimpleNamespace(kind=23, group=1, task_begin=0, task_count=0)]
+    with pytest.raises(NotImplementedError, match=r"phase kind 23 \(group 1\)"):
+        it.run_group(1)
+    it.run_group(0)      # (no phase of another group is looked at)

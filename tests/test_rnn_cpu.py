@@ -10,12 +10,11 @@ import torch
 
 import rnn_reference as rr
 from golden_util import GOLDEN_DIR, step_schedule
-from plan_interp import PH_GEMM, PH_POOL_AVG_BWD, PH_POOL_AVG_FWD, plan_arrays
-from plan_interp_rnn import PH_RNN_CELL_BWD, PH_RNN_CELL_FWD, PH_RNN_POOL_BWD, PH_RNN_POOL_FWD, RnnInterp
+from plan_interp import (PH_GEMM, PH_POOL_AVG_BWD, PH_POOL_AVG_FWD, PH_RNN_CELL_BWD, PH_RNN_CELL_FWD, PH_RNN_POOL_BWD, PH_RNN_POOL_FWD, Interp,
+                         plan_arrays)
 from ta3n_amd import _lib, tolerances as tol
 from ta3n_amd.models import VideoModel
 from test_plan_cpu import make_hyper
-from test_unshared_cpu import SvInterp
 
 INTERP_FIXTURES = [n for n in rr.FIXTURES if n != "tiny_rnn_gru_sv_wcls"]
 
@@ -44,17 +43,13 @@ def test_slot_table_is_the_reference_pooling():
             _lib.rnn_slots(*bad)
 
 
-class _SvRnnInterp(RnnInterp, SvInterp):
-    pass
-
-
 @pytest.mark.parametrize("fused", [False, True])
 @pytest.mark.parametrize("name", INTERP_FIXTURES)
 def test_plan_reproduces_reference_on_cpu(name, fused):
     g, c = rr.setup(name)
     T, B, Bs = c["T"], c["Bs"] + c["Bt"], c["Bs"]
     plan = rr.make_plan(c)
-    it = _SvRnnInterp(plan, c["rnn_cell"], c["n_ts"])
+    it = Interp(plan)
     shapes = {n: s for n, _, s, _ in plan.params}
     it.set_params(rr.state_of(shapes, c))
     live = {n for n, _, _, lv in plan.params if lv}

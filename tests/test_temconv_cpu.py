@@ -10,19 +10,13 @@ import torch
 
 import temconv_reference as tr
 from golden_util import GOLDEN_DIR, step_schedule
-from plan_interp import PH_POOL_AVG_BWD, PH_POOL_AVG_FWD, plan_arrays
-from plan_interp_temconv import PH_TEMCONV_BWD, PH_TEMCONV_FWD, PH_TEMCONV_WGRAD, TemconvInterp
+from plan_interp import PH_POOL_AVG_BWD, PH_POOL_AVG_FWD, PH_TEMCONV_BWD, PH_TEMCONV_FWD, PH_TEMCONV_WGRAD, Interp, plan_arrays
 from ta3n_amd import _lib, tolerances as tol
 from ta3n_amd.models import VideoModel
 from test_plan_cpu import make_hyper
-from test_unshared_cpu import SvInterp
 
 INTERP_FIXTURES = [n for n in tr.FIXTURES if n != "tiny_tc_sv_wcls"]
 DEAD = ("tcl_5_1.", "tcl_3_2.", "tcl_5_2.", "bn_1_S.", "bn_1_T.", "bn_2_S.", "bn_2_T.", "conv_fusion.")
-
-
-class _SvTemconvInterp(TemconvInterp, SvInterp):
-    pass
 
 
 def _like(ref_key, g, a):
@@ -37,7 +31,7 @@ def test_plan_reproduces_reference_on_cpu(name, fused):
     g, c = tr.setup(name)
     T, B, Bs = c["T"], c["Bs"] + c["Bt"], c["Bs"]
     plan = tr.make_plan(c)
-    it = _SvTemconvInterp(plan)
+    it = Interp(plan)
     shapes = {n: s for n, _, s, _ in plan.params}
     it.set_params(tr.state_of(shapes, c))
     live = [n for n, _, _, lv in plan.params if lv]
@@ -83,7 +77,7 @@ def test_fused_norm_counts_the_temconv_gradients():
     """The fused optimiser's norm is the sum of the "sumsq" slots: the last one holds the four tcl_3_1 gradients' sum of squares."""
     g, c = tr.setup("tiny_tc_T5")
     plan = tr.make_plan(c)
-    it = _SvTemconvInterp(plan)
+    it = Interp(plan)
     it.set_params(tr.state_of({n: s for n, _, s, _ in plan.params}, c))
     st = step_schedule(c)[0]
     xs, xt, labels = tr.step_batch(c, st)

@@ -42,25 +42,6 @@ def _plan(c, flags, **kw):
     return _lib.Plan(c["Bs"], c["Bt"], c["T"], c["D"], c["fc_dim"], c["C"], flags, **kw)
 
 
-class SvInterp(Interp):
-    """The loss launch under TA3N_FLAG_TARGET_LABELS (main.py:442-446): the class cross-entropy over the valid rows of both halves -
-    plan_interp's run_loss takes the source rows; the target rows' share is added here (inv_n_cls = 1 / (n_s + n_t) from the caller)."""
-
-    def run_loss(self):
-        super().run_loss()
-        g, h = self.g, self.hy
-        if not (g.flags & _lib.FLAG_TARGET_LABELS):
-            return
-        Y = self.r(g.o_Y, (g.B, g.C))
-        rows = g.Bs + np.arange(min(h["valid_target"], g.Bt))
-        z = Y[rows]
-        m = z.max(1, keepdims=True); lp = z - m - np.log(np.exp(z - m).sum(1, keepdims=True))
-        onehot = np.zeros_like(z); onehot[np.arange(len(rows)), self.labels[rows]] = 1
-        self.r(g.o_gY, (g.B, g.C))[rows] += (np.exp(lp) - onehot) * h["inv_n_cls"]
-        l = float(-lp[np.arange(len(rows)), self.labels[rows]].sum() * h["inv_n_cls"])
-        self.ws[g.o_losses] += l; self.ws[g.o_losses + 1] += l
-
-
 def _load_step(it, g, c, st):
     xs, xt, ys, yt = synth_batch(c["C"], c["T"], c["D"], c["Bs"], c["Bt"], seed=st["xseed"])
     xs[st["n_src"]:] = 0; xt[st["n_tgt"]:] = 0
@@ -84,7 +65,7 @@ def test_plan_reproduces_reference(name):
     T = c["T"]
     plan = _plan(c, sp_flags(g, c))
     assert not plan.has_fused_step and _lib.lib().ta3n_has_pipelined_step(plan.handle) == 0
-    it = SvInterp(plan)
+    it = Interp(plan)
     shapes = {n: s for n, _, s, _ in plan.params}
     it.set_params(synth_state(shapes, seed=c["wseed"], scale=c["wscale"]))
     live = {n for n, _, _, lv in plan.params if lv}
@@ -324,7 +305,7 @@ def test_bf16_plan_on_cpu(store):
     g = Golden("tiny_sp_T5")
     c = case_config(g)
     plan = _plan(c, sp_flags(g, c) | _lib.FLAG_BF16_MFMA | (_lib.FLAG_BF16_STORE if store else 0))
-    it = SvInterp(plan)
+    it = Interp(plan)
     it.set_params(synth_state({n: s for n, _, s, _ in plan.params}, seed=c["wseed"], scale=c["wscale"]))
     _load_step(it, g, c, step_schedule(c)[0])
     it.run_group(0)
@@ -343,7 +324,7 @@ def test_dropout_masks_stay_keyed_by_the_global_row():
     plan = _plan(c, sp_flags(g, c))
     res = []
     for p in (0.0, 0.5):
-        it = SvInterp(plan)
+        it = Interp(plan)
         it.set_params(synth_state({n: s for n, _, s, _ in plan.params}, seed=c["wseed"], scale=c["wscale"]))
         _load_step(it, g, c, step_schedule(c)[0])
         it.hy.update(p_drop_i=p, p_drop_v=p, seed_i=11, seed_v=12)
