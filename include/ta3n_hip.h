@@ -151,6 +151,22 @@ typedef enum {
  * places the n videos in the TARGET half of x (rows [batch_source * T, (batch_source + n) * T)) and their labels in region "labels"[0, n);
  * ta3n_eval_metrics then scores rows [batch_source, batch_source + n) of "Y", n <= min(batch_source, batch_target). */
 #define TA3N_FLAG_UNSHARED       (1u << 16)
+/* A score-only plan: the eval-mode forward up to the class logits and nothing else - what main.validate (main.py:707-735) and test_models.py
+ * (:155-198) need from the model.  The parameter layout is that of the same configuration WITHOUT the bit - names, order, offsets,
+ * ta3n_param_floats, ta3n_live_param_floats - so a training plan's params buffer is passed as it is.  All batch_source + batch_target rows
+ * are alike; the sum is the plan's capacity.  One launch list (group 0; ta3n_forward and ta3n_time_phases run it), made of launch kinds the
+ * training plans have: trn-m: the shared-FC product (no dropout epilogue), the tuple products and - with TA3N_FLAG_TRANS_ATTN only - the relation
+ * discriminators' first layer "Hr"; avgpool: the shared-FC product and the averaging; rnn: slot pooling, the Gx product, per step the Gh
+ * product and the cell; temconv: the shared-FC product and the filter.  No frame or video discriminator, no dropout, no gradient, partial-sum,
+ * twin or optimiser region: ta3n_workspace_floats is smaller than the training plan's.  ta3n_score runs the list and the score kernel behind it.
+ * The scalars ta3n_init_workspace leaves are eval mode; results never depend on beta, dropout rates or seeds, and ta3n_set_hyper refuses such
+ * a plan, as does every entry point that takes gradients, momentum or a loss.
+ * Accepted beside the bit - they decide the layout and, TA3N_FLAG_TRANS_ATTN, the attention: TA3N_FLAG_ADV_*, _ATTN_ENTROPY, _TRANS_ATTN (trn-m),
+ * _MCD (classifier 1 is scored, as test_models.py does), _FEATURE_GRADS, _TARGET_LABELS, _TARGET_ENTROPY - wherever the configuration without
+ * the bit is built: its checks run first, with their messages.  Then refused by name, "TA3N_FLAG_SCORE_ONLY with ... is not built":
+ * TA3N_FLAG_BN_SHARED, _BF16_MFMA, _BF16_STORE, _F32_SPLIT (fp32 only), _FRAME_ATTN, _GENERAL_ATTN, _UNSHARED, _CLASS_WEIGHTS,
+ * shared_fc_layers > 1, chain, split_k, wgrads_late, phase_tiles, layout_flags, and on trn-m a num_bottleneck other than 64, 128, 256 or 512. */
+#define TA3N_FLAG_SCORE_ONLY     (1u << 17)
 
 /* ta3n_config.aggregation */
 #define TA3N_AGG_TRN_M    0   /* 'trn-m': multi-scale TRN - the TA3N path (TRNmodule.py:27-86) */
@@ -396,6 +412,21 @@ int ta3n_train_step(ta3n_plan *plan, const float *x, const float *params, float 
  * rows (labels in ws["labels"]) to ws["metrics"][0..3] and their (label, argmax) pairs to the int32 [C][C]
  * matrix ws["confusion"]; reset != 0 clears both first.  No host synchronisation per batch. */
 int ta3n_eval_metrics(ta3n_plan *plan, float *ws, int n_videos, int reset, void *stream);
+
+/* Scores n_videos videos on a TA3N_FLAG_SCORE_ONLY plan: the plan's launch list (group 0) and ONE more launch, the score kernel - one wave
+ * per video from the aggregated feature to probabilities, ranks and metrics.  x holds rows [n_videos * T][D] (the buffer has the plan's
+ * capacity; rows at and past n_videos * T may hold anything and influence nothing), the labels sit in ws["labels"][0, n_videos).
+ * trn-m: R_j = sum of scale j's tuple activations, w_j = 1 - H(softmax(W2_j Hr_j + b2_j)) with TA3N_FLAG_TRANS_ATTN and 0 without,
+ * V = sum_j (1 + w_j) R_j (models.py:351-357, 379-388); the other aggregations: V as their last launch left it.  Then Y = Wcv V + bcv,
+ * prob = softmax(Y), ce = -log_softmax(Y)[label], rank = classes ahead of the label in torch.topk order (ties: the lower class index is
+ * ahead), pred = argmax under the same rule - the rules of ta3n_eval_metrics.
+ * Written per video (rows [0, n_videos)): regions "Y" [cap][C], "prob" [cap][C], "rank" and "pred" (int32 [cap]), "ce" [cap], "V" [cap][NB or
+ * F], and on trn-m "attn" [cap][T-1] = w_j.  Accumulated across calls, cleared first when reset != 0: "metrics" = {CE sum, top-1 hits,
+ * top-5 hits, videos} and the int32 [C][C] "confusion" (rows = label, cols = pred).  The workgroup that finishes last adds the per-video
+ * values in video order (the int32 "score_ticket" counts the finished workgroups and is zero again when the launch ends): no float atomics, the
+ * same call twice gives the same bits.  Enqueue only.
+ * TA3N_ERR_INVALID: a plan without the flag, n_videos outside [0, batch_source + batch_target]. */
+int ta3n_score(ta3n_plan *plan, const float *x, const float *params, float *ws, int n_videos, int reset, void *stream);
 
 /* clip_grad_norm_ + Nesterov SGD with weight decay (main.py:578-583) on the
  * flat live prefix; ws["grad_norm"] receives the pre-clip global norm. */

@@ -34,6 +34,7 @@ FLAG_TARGET_LABELS = 1 << 13   # --use_target Sv: the class CE over the valid ro
 FLAG_TARGET_ENTROPY = 1 << 14  # --add_loss_DA target_entropy: gamma * mean entropy of the valid target rows' class softmax; exclusive with FLAG_ATTN_ENTROPY
 FLAG_GENERAL_ATTN = 1 << 15   # use_attn general: relation weights = softmax over the relations of a learned layer's scores (parameters attn_layer.0 / .2; regions Ua, gUa, gs); unfused entry points, single rank
 FLAG_UNSHARED = 1 << 16       # share_params N: the target rows' own first frame layer and video classifier (parameters fc_*_target); unfused entry points, single rank
+FLAG_SCORE_ONLY = 1 << 17     # a score-only plan: the eval-mode forward to the class logits on the training plan's parameter layout, scored by ta3n_score (ta3n_amd.scoring.Scorer)
 AGG_TRN_M, AGG_AVGPOOL, AGG_RNN = 0, 1, 2      # AGG_RNN: slot max-pooling + one LSTM / GRU layer (rnn_cell, n_ts)
 AGG_TEMCONV = 4                                 # the 3-tap filter tcl_3_1 over the segments + ReLU + mean (3 would be the reference's 'trn', which it cannot run)
 RNN_CELLS = {"LSTM": 0, "GRU": 1}
@@ -43,7 +44,7 @@ SYMBOLS = [
     "ta3n_num_relation_tuples", "ta3n_relation_table", "ta3n_segment_indices", "ta3n_rnn_slots", "ta3n_gather_segments", "ta3n_plan_create",
     "ta3n_plan_destroy", "ta3n_num_params", "ta3n_param_info", "ta3n_param_floats", "ta3n_live_param_floats",
     "ta3n_workspace_floats", "ta3n_ws_offset", "ta3n_ws_size", "ta3n_plan_describe", "ta3n_set_hyper",
-    "ta3n_init_workspace", "ta3n_forward", "ta3n_loss", "ta3n_backward", "ta3n_has_fused_step", "ta3n_train_step", "ta3n_eval_metrics",
+    "ta3n_init_workspace", "ta3n_forward", "ta3n_loss", "ta3n_backward", "ta3n_has_fused_step", "ta3n_train_step", "ta3n_eval_metrics", "ta3n_score",
     "ta3n_sgd_step", "ta3n_sgd_step_fused", "ta3n_sgd_range", "ta3n_train_step_join", "ta3n_train_step_range", "ta3n_refresh_bf16", "ta3n_sgd_step_next", "ta3n_gather_segments_into", "ta3n_has_pipelined_step", "ta3n_train_step_after_update", "ta3n_num_phases",
     "ta3n_adam_scalars", "ta3n_adam_range", "ta3n_adam_step_next", "ta3n_train_steps_adam",
     "ta3n_debug_arrays", "ta3n_debug_struct_sizes", "ta3n_time_phases", "ta3n_time_update_launches", "ta3n_last_error", "ta3n_version",
@@ -151,6 +152,7 @@ def lib() -> C.CDLL:
     L.ta3n_loss.argtypes = [vp, vp, vp]
     L.ta3n_backward.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ta3n_eval_metrics.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    L.ta3n_score.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
     L.ta3n_has_fused_step.argtypes = [vp]
     L.ta3n_train_step.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ta3n_sgd_step.argtypes = [vp, vp, vp, vp, vp, vp]

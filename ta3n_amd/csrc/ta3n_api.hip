@@ -34,6 +34,11 @@ const char *const LAYOUT_PLAN_TEXT = ": this plan lies on another plan's paramet
                                      "the ranges of ta3n_live_range, update them with ta3n_sgd_live";
 #define REFUSE_LAYOUT_PLAN(p, fn) \
     do { if ((p)->cfg.layout_flags) return fail(TA3N_ERR_INVALID, std::string(fn) + LAYOUT_PLAN_TEXT); } while (0)
+// A score-only plan (TA3N_FLAG_SCORE_ONLY) holds the forward to the class logits and nothing a loss, a gradient or an optimiser touches
+const char *const SCORE_PLAN_TEXT = ": this plan was created with TA3N_FLAG_SCORE_ONLY - it holds the forward to the class logits only "
+                                    "(ta3n_forward, ta3n_score, ta3n_time_phases), no loss, gradient or optimiser region";
+#define REFUSE_SCORE_PLAN(p, fn) \
+    do { if ((p)->cfg.flags & TA3N_FLAG_SCORE_ONLY) return fail(TA3N_ERR_INVALID, std::string(fn) + SCORE_PLAN_TEXT); } while (0)
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
@@ -374,7 +379,7 @@ int ta3n_init_workspace(ta3n_plan *p, float *ws, void *stream) {
     if (rc != TA3N_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(ws, 0, (size_t)p->ws_floats * sizeof(float), s));
-    if (launch_fill(ws + p->geom.o_ones, 1.0f, (int64_t)p->geom.B * p->geom.T * 4, s) != 0)
+    if (p->geom.o_ones >= 0 && launch_fill(ws + p->geom.o_ones, 1.0f, (int64_t)p->geom.B * p->geom.T * 4, s) != 0)      // (a score-only plan has no ones block)
         return fail(TA3N_ERR_HIP, "fill launch failed");
     HIP_TRY(hipMemcpyAsync(ws + p->geom.o_tuple_first, p->tuple_first.data(), p->tuple_first.size() * sizeof(int32_t),
                            hipMemcpyHostToDevice, s));
@@ -384,6 +389,7 @@ int ta3n_init_workspace(ta3n_plan *p, float *ws, void *stream) {
 
 int ta3n_set_hyper(ta3n_plan *p, float *ws, const ta3n_hyper *h, void *stream) {
     if (!p || !ws || !h) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_set_hyper");
     int rc = ensure_uploaded(p);
     if (rc != TA3N_OK) return rc;
     // by kernel argument: the values are captured when the launch is enqueued, so the host may run any number of steps
@@ -404,6 +410,7 @@ int ta3n_forward(ta3n_plan *p, const float *x, const float *params, float *ws, v
 
 int ta3n_loss(ta3n_plan *p, float *ws, void *stream) {
     if (!p || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_loss");
     int rc = ensure_uploaded(p);
     if (rc != TA3N_OK) return rc;
     Ptrs ptrs = make_ptrs(p, nullptr, nullptr, nullptr, ws);
@@ -413,6 +420,7 @@ int ta3n_loss(ta3n_plan *p, float *ws, void *stream) {
 // ---- ens_DA MCD: the loss assembly around the second classifier and the second, reversed pass (include/ta3n_hip.h) ----
 int ta3n_mcd_source_loss(ta3n_plan *p, float *ws, float *scratch, float *out, void *stream) {
     if (!p || !ws || !scratch || !out) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_mcd_source_loss");
     if (!(p->cfg.flags & TA3N_FLAG_MCD) || p->geom.o_Y2 <= 0) return fail(TA3N_ERR_INVALID, "the plan was not created with TA3N_FLAG_MCD");
     if (launch_mcd_source_loss(p->geom, ws, scratch, out, static_cast<hipStream_t>(stream)) != 0) return fail(TA3N_ERR_HIP, "MCD source-loss launch failed");
     return TA3N_OK;
@@ -420,6 +428,7 @@ int ta3n_mcd_source_loss(ta3n_plan *p, float *ws, float *scratch, float *out, vo
 
 int ta3n_mcd_second_loss(ta3n_plan *p, float *ws, float *ws2, int global_target, float *scratch, float *out, void *stream) {
     if (!p || !ws || !ws2 || !scratch || !out || ws == ws2) return fail(TA3N_ERR_INVALID, "null argument (or one workspace for both passes)");
+    REFUSE_SCORE_PLAN(p, "ta3n_mcd_second_loss");
     if (!(p->cfg.flags & TA3N_FLAG_MCD) || p->geom.o_Y2 <= 0) return fail(TA3N_ERR_INVALID, "the plan was not created with TA3N_FLAG_MCD");
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the second pass has no ta3n_loss of its own: every gradient entry its backward reads starts from zero
@@ -434,6 +443,7 @@ int ta3n_mcd_second_loss(ta3n_plan *p, float *ws, float *ws2, int global_target,
 
 int ta3n_backward(ta3n_plan *p, const float *x, const float *params, float *grads, float *ws, void *stream) {
     if (!p || !x || !params || !grads || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_backward");
     if (!aligned16(x) || !aligned16(params) || !aligned16(grads) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     int rc = ensure_uploaded(p);
@@ -447,7 +457,8 @@ int ta3n_backward(ta3n_plan *p, const float *x, const float *params, float *grad
 // between two events (the phases are idempotent); optimiser phases once.
 int ta3n_time_phases(ta3n_plan *p, const float *x, float *params, float *grads, float *momentum, float *ws,
                      void *stream, int reps, float *ms_out, int32_t *kind_out, int32_t *group_out, int cap) {
-    if (!p || !x || !params || !grads || !momentum || !ws || !ms_out) return fail(TA3N_ERR_INVALID, "null argument");
+    if (!p || !x || !params || !ws || !ms_out) return fail(TA3N_ERR_INVALID, "null argument");
+    if ((!grads || !momentum) && !(p->cfg.flags & TA3N_FLAG_SCORE_ONLY)) return fail(TA3N_ERR_INVALID, "null argument");      // (no launch of a score-only plan takes them)
     int rc = ensure_uploaded(p);
     if (rc != TA3N_OK) return rc;
     if (reps < 1) reps = 1;
@@ -497,6 +508,7 @@ static SgdSide update_side(const Geom &g, float *params, float *momentum, float 
 int ta3n_time_update_launches(ta3n_plan *p, const float *x, float *params, float *grads, float *momentum, float *ws, int fused_norm,
                               float lr, float momentum_coef, float weight_decay, float clip, void *stream, int reps, float *ms_out2) {
     if (!p || !x || !params || !grads || !momentum || !ws || !ms_out2) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_time_update_launches");
     if (ta3n_has_pipelined_step(p) != 1) return fail(TA3N_ERR_INVALID, "no pipelined step for this configuration");
     int rc = ensure_uploaded(p);
     if (rc != TA3N_OK) return rc;
@@ -579,12 +591,28 @@ int ta3n_gather_segments_bf16_into(ta3n_plan *p, const void *store16, const int6
 
 int ta3n_eval_metrics(ta3n_plan *p, float *ws, int n_videos, int reset, void *stream) {
     if (!p || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_eval_metrics");
     if (n_videos < 0 || n_videos > p->geom.Bs) return fail(TA3N_ERR_INVALID, "n_videos must be in [0, batch_source]");
     if ((p->geom.flags & TA3N_FLAG_UNSHARED) && n_videos > p->geom.Bt)
         return fail(TA3N_ERR_INVALID, "TA3N_FLAG_UNSHARED: n_videos must be in [0, min(batch_source, batch_target)] (the videos are scored in the target half)");
     if (p->geom.C > 64) return fail(TA3N_ERR_INVALID, "num_class > 64 not supported");
     if (launch_eval_metrics(p->geom, ws, n_videos, reset, static_cast<hipStream_t>(stream)) != 0)
         return fail(TA3N_ERR_HIP, std::string("metrics launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return TA3N_OK;
+}
+
+int ta3n_score(ta3n_plan *p, const float *x, const float *params, float *ws, int n_videos, int reset, void *stream) {
+    if (!p || !x || !params || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    if (!(p->cfg.flags & TA3N_FLAG_SCORE_ONLY) || p->score.o_prob < 0) return fail(TA3N_ERR_INVALID, "ta3n_score: the plan was not created with TA3N_FLAG_SCORE_ONLY");
+    if (n_videos < 0 || n_videos > p->geom.B) return fail(TA3N_ERR_INVALID, "ta3n_score: n_videos must be in [0, batch_source + batch_target]");
+    if (!aligned16(x) || !aligned16(params) || !aligned16(ws)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    int rc = ensure_uploaded(p);
+    if (rc != TA3N_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Ptrs ptrs = make_ptrs(p, x, params, nullptr, ws);
+    if ((rc = run_group(p, 0, ptrs, nullptr, nullptr, s)) != TA3N_OK) return rc;
+    if (launch_score(p->geom, ptrs, p->score, n_videos, reset, s) != 0)
+        return fail(TA3N_ERR_HIP, std::string("score launch failed: ") + hipGetErrorString(hipGetLastError()));
     return TA3N_OK;
 }
 
@@ -602,6 +630,7 @@ int ta3n_train_step(ta3n_plan *p, const float *x, const float *params, float *gr
 int ta3n_train_step_range(ta3n_plan *p, const float *x, const float *params, float *grads, float *ws, int first_launch,
                           int n_launches, void *stream) {
     if (!p || !x || !params || !grads || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_train_step_range");
     if (!aligned16(x) || !aligned16(params) || !aligned16(grads) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
@@ -625,6 +654,7 @@ int ta3n_train_step_after_update(ta3n_plan *p, const float *x, float *params, fl
                                  int fused_norm, float lr, float momentum_coef, float weight_decay, float clip,
                                  const ta3n_hyper *next, void *stream) {
     if (!p || !x || !params || !grads || !momentum || !ws || !next) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_train_step_after_update");
     if (!aligned16(x) || !aligned16(params) || !aligned16(grads) || !aligned16(momentum) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (ta3n_has_pipelined_step(p) != 1) return fail(TA3N_ERR_INVALID, "no pipelined step for this configuration");
@@ -725,6 +755,7 @@ static int enqueue_pipelined_step(ta3n_plan *p, const Ptrs &ptrs, float *params,
 static int check_steps_job(ta3n_plan *p, const float *x, float *params, float *grads, float *momentum, float *ws, const ta3n_hyper *hypers,
                            int fused_norm, const ta3n_feed *source, const ta3n_feed *target, ta3n_comm *comm) {
     if (!p || !x || !params || !grads || !momentum || !ws || !hypers) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_train_steps");
     if (!aligned16(x) || !aligned16(params) || !aligned16(grads) || !aligned16(momentum) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (ta3n_has_pipelined_step(p) != 1) return fail(TA3N_ERR_INVALID, "no pipelined step for this configuration");
@@ -824,6 +855,7 @@ int ta3n_shard_ranges(const ta3n_plan *p, int rank, int world, int64_t *own4, in
 
 int ta3n_shard_sumsq(ta3n_plan *p, const float *grads, float *ws, int rank, int world, void *stream) {
     if (!p || !grads || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_shard_sumsq");
     Shards s;
     int rc = shard_layout(p, world, s);
     if (rc != TA3N_OK) return rc;
@@ -838,6 +870,7 @@ int ta3n_shard_sumsq(ta3n_plan *p, const float *grads, float *ws, int rank, int 
 int ta3n_sgd_shard(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, int rank, int world, float lr, float momentum_coef,
                    float weight_decay, float clip, const ta3n_hyper *next, void *stream) {
     if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_sgd_shard");
     Shards s;
     int rc = shard_layout(p, world, s);
     if (rc != TA3N_OK) return rc;
@@ -863,6 +896,7 @@ int ta3n_sgd_shard(ta3n_plan *p, float *params, float *grads, float *momentum, f
 
 int ta3n_shard_reduce_scatter(ta3n_plan *p, ta3n_comm *c, float *grads, void *scratch_bf16, void *stream) {
     if (!p || !c || !grads) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_shard_reduce_scatter");
     Shards s;
     int rc = shard_layout(p, comm_world_size(c), s);
     if (rc != TA3N_OK) return rc;
@@ -875,6 +909,7 @@ int ta3n_shard_reduce_scatter(ta3n_plan *p, ta3n_comm *c, float *grads, void *sc
 int ta3n_sharded_update(ta3n_plan *p, ta3n_comm *c, float *params, float *grads, float *momentum, float *ws, float lr, float momentum_coef,
                         float weight_decay, float clip, const ta3n_hyper *next, void *stream) {
     if (!p || !c || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_sharded_update");
     const int rank = comm_rank(c), world = comm_world_size(c);
     Shards s;
     int rc = shard_layout(p, world, s);
@@ -956,6 +991,7 @@ int ta3n_train_steps_fused_update(ta3n_plan *p, const float *x, float *params, f
                                   float momentum_coef, float weight_decay, float clip, const ta3n_hyper *hypers, int n_steps,
                                   const ta3n_feed *source, const ta3n_feed *target, void *stream) {
     if (!p || !x || !params || !params_alt || !grads || !momentum || !ws || !hypers) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_train_steps_fused_update");
     if (n_steps < 0) return fail(TA3N_ERR_INVALID, "n_steps must be >= 0");
     if (!aligned16(x) || !aligned16(params) || !aligned16(params_alt) || !aligned16(grads) || !aligned16(momentum) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
@@ -1017,6 +1053,7 @@ int ta3n_refresh_bf16(ta3n_plan *p, const float *x, const float *params, float *
 int ta3n_sgd_range(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, int64_t begin, int64_t end, int fused_norm,
                    float lr, float momentum_coef, float weight_decay, float clip, void *stream) {
     if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_sgd_range");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (begin < 0 || end > p->live_floats || begin > end || (begin & 3) || (end & 3))
         return fail(TA3N_ERR_INVALID, "range must be 4-float aligned and inside the live parameter prefix");
@@ -1036,6 +1073,7 @@ int ta3n_sgd_range(ta3n_plan *p, float *params, float *grads, float *momentum, f
 int ta3n_sgd_step_next(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, int fused_norm, float lr,
                        float momentum_coef, float weight_decay, float clip, const ta3n_hyper *next, void *stream) {
     if (!p || !params || !grads || !momentum || !ws || !next) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_sgd_step_next");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     REFUSE_LAYOUT_PLAN(p, "ta3n_sgd_step_next");
     if (fused_norm && ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
@@ -1053,6 +1091,7 @@ int ta3n_sgd_step_next(ta3n_plan *p, float *params, float *grads, float *momentu
 
 int ta3n_train_step_join(ta3n_plan *p, const float *x, const float *params, float *grads, float *ws, void *stream, void *join_event) {
     if (!p || !x || !params || !grads || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_train_step_join");
     if (!aligned16(x) || !aligned16(params) || !aligned16(grads) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (ta3n_has_fused_step(p) != 1)
@@ -1066,6 +1105,7 @@ int ta3n_train_step_join(ta3n_plan *p, const float *x, const float *params, floa
 
 int ta3n_sgd_step_fused(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, void *stream) {
     if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_sgd_step_fused");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     REFUSE_LAYOUT_PLAN(p, "ta3n_sgd_step_fused");
     if (ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration: use ta3n_sgd_step");
@@ -1078,6 +1118,7 @@ int ta3n_sgd_step_fused(ta3n_plan *p, float *params, float *grads, float *moment
 
 int ta3n_sgd_step(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, void *stream) {
     if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_sgd_step");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     REFUSE_LAYOUT_PLAN(p, "ta3n_sgd_step");
     int rc = ensure_uploaded(p);
@@ -1098,6 +1139,7 @@ int ta3n_live_range(const ta3n_plan *p, int i, int64_t *begin, int64_t *end) {
 int ta3n_sgd_live(ta3n_plan *p, float *params, float *grads, float *momentum, float *ws, int fused_norm, float lr, float momentum_coef,
                   float weight_decay, float clip, void *stream) {
     if (!p || !params || !grads || !momentum || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "ta3n_sgd_live");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(momentum)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (fused_norm && ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
     LiveRanges lr_tab;
@@ -1136,6 +1178,7 @@ namespace {
 int check_adam(const ta3n_plan *p, const float *params, const float *grads, const float *exp_avg, const float *exp_avg_sq, const float *ws,
                int64_t step, float eps, int fused_norm) {
     if (!p || !params || !grads || !exp_avg || !exp_avg_sq || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    REFUSE_SCORE_PLAN(p, "the Adam update");
     if (!aligned16(params) || !aligned16(grads) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (step < 1) return fail(TA3N_ERR_INVALID, "Adam: step counts from 1 (the number of the update being applied)");

@@ -332,6 +332,8 @@ int launch_sgd_open_feed(const Geom &g, float *params, const float *grads, float
                          bool fused_norm, float lr, float mu, float wd, float clip, const Hyper *next, const FeedJob feeds[2], hipStream_t stream);
 int launch_shard_sumsq(const Geom &g, const float *grads, float *ws, int64_t a0, int64_t a1, int64_t b0, int64_t b1, int rank, hipStream_t stream);
 int launch_eval_metrics(const Geom &g, float *ws, int n, int reset, hipStream_t stream);
+// TA3N_FLAG_SCORE_ONLY (ta3n_score.hip): classifier, softmax, rank and metrics of the first n videos, behind the plan's launch list
+int launch_score(const Geom &g, const Ptrs &ptrs, const ScoreArgs &a, int n, int reset, hipStream_t stream);
 int launch_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                            const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, int32_t *seg_out,
                            float *out_twin, hipStream_t stream, int64_t pair_delta = 0);

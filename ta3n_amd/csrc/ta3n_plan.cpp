@@ -746,6 +746,7 @@ struct TrnModel {
     int tau(int t, int pos) const { return p.tuples[(size_t)t * d.T + pos]; }
 
     void add_params();
+    void resolve_params();
     bool lay_out_workspace(std::string &err);
     void add_unfused_lists();
     void add_frame_attn_lists();
@@ -985,7 +986,11 @@ void TrnModel::add_params() {
         Wsh_t = p.poff("fc_feature_shared_target.weight"); bsh_t = p.poff("fc_feature_shared_target.bias");
         Wcv_t = p.poff("fc_classifier_video_target.weight"); bcv_t = p.poff("fc_classifier_video_target.bias");
     }
+    resolve_params();
+}
 
+// the offsets the spec builders address, from the parameter table (add_params' own, or - TA3N_FLAG_SCORE_ONLY - the training plan's)
+void TrnModel::resolve_params() {
     w = head_params(p, mcd);
     for (int j = 0; j < NR; ++j) {
         const std::string trn = "TRN.fc_fusion_scales." + std::to_string(j) + ".1", rel = "relation_domain_classifier_all." + std::to_string(j);
@@ -1488,6 +1493,127 @@ int build_plan_once(ta3n_plan &p, std::string &err) {
     return (c.flags & general) ? build_plan_avgpool_general(p, err) : build_plan_avgpool(p, err);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// TA3N_FLAG_SCORE_ONLY: the forward to the class logits and nothing else (main.validate / test_models.py score out_target of an eval-mode
+// forward, main.py:707-735).  The parameter table is the training plan's of the same configuration (`donor`, built first: its checks
+// come first, and a training plan's params buffer is passed as it is); every row of batch_source + batch_target is alike.  One launch
+// list, group 0, of launch kinds the training plans have, up to the aggregated feature:
+//   trn-m    F1 | tuple products [+ Hr_j with TA3N_FLAG_TRANS_ATTN]                (the score kernel pools: no PH_POOL_FWD)
+//   avgpool  F1 | PH_POOL_AVG_FWD          temconv  F1 | PH_TEMCONV_FWD          rnn  F1 | slot pooling | Gx | per step { Gh | cell }
+// behind which ta3n_score runs the score kernel (ta3n_score.hip): classifier, softmax, rank, metrics.  No dropout epilogue (eval mode:
+// the scalars ta3n_init_workspace leaves), no discriminator, no gradient / partial-sum / twin / optimiser region.
+std::string score_refusal(const ta3n_config &c) {
+    const std::string head = "TA3N_FLAG_SCORE_ONLY with ";
+    const std::pair<uint32_t, const char *> flags[] = {
+        {TA3N_FLAG_BN_SHARED, "TA3N_FLAG_BN_SHARED (use_bn)"}, {TA3N_FLAG_BF16_MFMA, "TA3N_FLAG_BF16_MFMA"}, {TA3N_FLAG_BF16_STORE, "TA3N_FLAG_BF16_STORE"},
+        {TA3N_FLAG_F32_SPLIT, "TA3N_FLAG_F32_SPLIT"}, {TA3N_FLAG_FRAME_ATTN, "TA3N_FLAG_FRAME_ATTN (use_attn_frame)"},
+        {TA3N_FLAG_GENERAL_ATTN, "TA3N_FLAG_GENERAL_ATTN (use_attn general)"}, {TA3N_FLAG_UNSHARED, "TA3N_FLAG_UNSHARED (share_params N)"},
+        {TA3N_FLAG_CLASS_WEIGHTS, "TA3N_FLAG_CLASS_WEIGHTS (weighted class loss)"}};
+    for (const auto &f : flags)
+        if (c.flags & f.first) return head + f.second + " is not built";
+    if (c.shared_fc_layers > 1) return head + "shared_fc_layers (--add_fc) " + std::to_string(c.shared_fc_layers) + " is not built";
+    if (c.chain) return head + "chain is not built";
+    if (c.split_k) return head + "split_k is not built";
+    if (c.wgrads_late) return head + "wgrads_late is not built";
+    for (int i = 0; i < 16; ++i)
+        if (c.phase_tiles[i]) return head + "phase_tiles is not built";
+    if (c.layout_flags) return head + "layout_flags is not built";
+    // (trn-m: the score kernel keeps a video's pooled feature lane-resident, num_bottleneck / 64 channels per lane, in the widths it is instantiated for)
+    const int q = c.num_bottleneck / 64;
+    if (c.aggregation == TA3N_AGG_TRN_M && q != 1 && q != 2 && q != 4 && q != 8)
+        return head + "num_bottleneck " + std::to_string(c.num_bottleneck) + " is not built: 64, 128, 256 or 512";
+    return "";
+}
+
+int build_plan_score(ta3n_plan &p, std::string &err) {
+    const ta3n_config cfg = p.cfg;
+    ta3n_plan donor;
+    donor.cfg = cfg;
+    donor.cfg.flags = cfg.flags & ~TA3N_FLAG_SCORE_ONLY;
+    const int rc = ta3n::build_plan(donor, err);
+    if (rc != TA3N_OK) return rc;
+    { const std::string e = score_refusal(cfg); if (!e.empty()) { err = e; return TA3N_ERR_INVALID; } }
+    p = ta3n_plan();
+    p.cfg = cfg;
+    p.params = donor.params; p.param_floats = donor.param_floats; p.live_floats = donor.live_floats; p.first_floats = donor.first_floats;
+    p.live_ranges = donor.live_ranges;
+    p.n_tuples = donor.n_tuples; p.tuples = donor.tuples; p.scale_len = donor.scale_len; p.scale_id = donor.scale_id; p.tuple_first = donor.tuple_first;
+
+    const ta3n_config &c = p.cfg;
+    const Dims d = dims_of(c);
+    const int B = d.B, BT = d.BT, D = d.D, F = d.F, C = d.C;
+    const bool trn = c.aggregation == TA3N_AGG_TRN_M, attn = trn && (c.flags & TA3N_FLAG_TRANS_ATTN);
+    const int NB = trn ? d.NB : F, NR = trn ? d.T - 1 : 0, NT = p.n_tuples;
+    TrnModel m(p, d);                  // (its builder serves every aggregation; its specs trn-m)
+    Builder &b = m.b;
+    Geom &g = p.geom;
+    init_geom(g, d, NB, c.flags);
+    g.n_tuples = NT; g.n_rel = NR;
+    g.o_F1 = (int32_t)b.add_region("F1", (int64_t)BT * F);
+    if (trn) {
+        m.resolve_params();
+        g.o_Zr = (int32_t)b.add_region("Zr", (int64_t)B * NT * NB);
+        if (attn) g.o_Hr = (int32_t)b.add_region("Hr", (int64_t)B * NR * NB);
+        g.o_attn = (int32_t)b.add_region("attn", (int64_t)B * NR);
+        g.p_W2_0 = (int32_t)m.W2[0]; g.p_b2_0 = (int32_t)m.B2[0];
+        g.p_W2_stride = NR > 1 ? (int32_t)(m.W2[1] - m.W2[0]) : 0;
+        g.p_b2_stride = NR > 1 ? (int32_t)(m.B2[1] - m.B2[0]) : 0;
+    }
+    const HeadParams w = head_params(p, false);      // (TA3N_FLAG_MCD: classifier 1 is the one scored, test_models.py)
+    g.o_V = g.o_Vd = (int32_t)b.add_region("V", (int64_t)B * NB);      // eval mode: dropout_v is the identity, the aggregator launches write one region twice
+    g.o_Y = (int32_t)b.add_region("Y", (int64_t)B * C);
+    p.score.trn = trn ? 1 : 0; p.score.width = NB;      // (the per-video results lie back to back, "attn" .. "ce": one copy takes them all)
+    p.score.o_prob = (int32_t)b.add_region("prob", (int64_t)B * C);
+    p.score.o_rank = (int32_t)b.add_region("rank", B);
+    p.score.o_pred = (int32_t)b.add_region("pred", B);
+    p.score.o_ce = (int32_t)b.add_region("ce", B);
+    AvgpoolDa a{b, g, d, w, SharedStack(), false, false, false, false};
+    if (c.aggregation == TA3N_AGG_RNN) {
+        RnnArgs &r = p.rnn;
+        r = donor.rnn;                 // cell, n_ts, len_ts and the slot table
+        const int GF = (r.cell ? 3 : 4) * F;
+        const int64_t rows = (int64_t)r.n_ts * B;
+        r.o_Xp = (int32_t)b.add_region("rnn_Xp", rows * F);
+        r.o_Gx = (int32_t)b.add_region("rnn_Gx", rows * GF);
+        r.o_Gh = (int32_t)b.add_region("rnn_Gh", rows * GF);
+        r.o_gates = (int32_t)b.add_region("rnn_gates", rows * GF);
+        r.o_c = (int32_t)b.add_region("rnn_c", (rows + B) * F);
+        r.o_h = (int32_t)b.add_region("rnn_h", (rows + B) * F);
+        r.o_gGx = r.o_gGh = r.o_gc = r.o_gh = r.o_ghd = r.o_gXp = -1;
+        a.rnn = &p.rnn;
+        a.Wih = p.poff("rnn.weight_ih_l0"); a.Whh = p.poff("rnn.weight_hh_l0");
+        a.bih = p.poff("rnn.bias_ih_l0"); a.bhh = p.poff("rnn.bias_hh_l0");
+    }
+    if (c.aggregation == TA3N_AGG_TEMCONV)
+        p.temconv = {(int32_t)p.poff("tcl_3_1.conv2d.weight"), (int32_t)p.poff("tcl_3_1.conv2d.bias"), -1, -1};
+    p.score.o_ticket = (int32_t)b.add_region("score_ticket", 1);
+    g.o_zeros = (int32_t)b.add_region("zeros", 64);   // never written: source of out-of-range operand elements
+    g.o_ones = -1;                                    // (the column sums of the weight gradients read it: no such launch here)
+    g.o_losses = (int32_t)b.add_region("losses", 8);  // (cleared by the aggregator launches, read by nobody)
+    g.o_hyper = (int32_t)b.add_region("hyper", 32);
+    g.o_labels = (int32_t)b.add_region("labels", B);
+    g.o_tuple_first = (int32_t)b.add_region("tuple_first", NR + 1);
+    g.o_metrics = (int32_t)b.add_region("metrics", 8);
+    g.o_confusion = (int32_t)b.add_region("confusion", (int64_t)C * C);
+    g.live_floats = (int32_t)p.live_floats;
+    g.p_Wcv = (int32_t)w.Wcv; g.p_bcv = (int32_t)w.bcv;
+
+    // the shared frame FC without its dropout epilogue (models.py:565-575 in eval mode)
+    b.add_gemm_phase(0, spec_linear(BT, F, D, BASE_X, 0, D, w.Wsh, w.bsh, g.o_F1, F, true));
+    if (trn) {
+        std::vector<GemmSpec> s;
+        for (int t = 0; t < NT; ++t) s.push_back(m.spec_Z(t));
+        b.add_gemm_phase(0, s);
+        if (attn) {
+            std::vector<GemmSpec> h;
+            for (int j = 0; j < NR; ++j) h.push_back(m.spec_Hr(j));
+            b.add_gemm_phase(0, h);
+        }
+    } else if (a.rnn) a.rnn_forward(0);
+    else b.add_simple_phase(c.aggregation == TA3N_AGG_TEMCONV ? PH_TEMCONV_FWD : PH_POOL_AVG_FWD, 0);
+    return finish_plan(p, b, err);
+}
+
 }  // namespace
 
 // models.py:397-409.  Python's round(T / n_ts) is half-to-even on the float quotient; T <= 64 and n_ts <= 128 make every quotient with
@@ -1512,6 +1638,7 @@ extern "C" int ta3n_rnn_slots(int num_segments, int n_ts, int32_t *len_ts, int32
 // plan is laid out (add_bf16_twins): build, look, and rebuild without the blocking where it cannot be used.
 int ta3n::build_plan(ta3n_plan &p, std::string &err) {
     const ta3n_config cfg = p.cfg;
+    if (cfg.flags & TA3N_FLAG_SCORE_ONLY) return build_plan_score(p, err);
     // ta3n_config.layout_flags: build the donor first and place this plan's parameters where the donor has them
     std::vector<ParamInfo> layout;
     int64_t donor_live = 0;

@@ -141,6 +141,17 @@ struct RnnArgs {
     uint8_t frames[RNN_MAX_SLOTS];   // slot j * len_ts + i reads this frame
 };
 
+// TA3N_FLAG_SCORE_ONLY: what the score kernel (ta3n_score.hip) takes by value beside Geom.  Per-video regions have one row per video of the
+// plan's capacity B.
+struct ScoreArgs {
+    int32_t trn;                     // 1: the trn-m front end (V pooled from "Zr" in the kernel); 0: V is read from region "V"
+    int32_t width;                   // floats per row of V: NB (trn-m) or F
+    int32_t o_prob;                  // [B][C] softmax(Y)
+    int32_t o_rank, o_pred;          // int32 [B]: classes ahead of the label in torch.topk order / argmax
+    int32_t o_ce;                    // [B] -log_softmax(Y)[label]
+    int32_t o_ticket;                // int32: workgroups of the running launch that have finished (zero between launches)
+};
+
 // work split of the fused heads kernel (ta3n_heads.hip); the plan builder sizes its partial-sum regions from these
 constexpr int HEADS_RPW = 16;   // frame rows per row group of a frame workgroup (Geom.heads_rpw rows per workgroup, a multiple of this)
 
