@@ -325,7 +325,7 @@ int ta3n_segment_indices(int num_frames, int num_segments, int new_length, int64
 int ta3n_rnn_slots(int num_segments, int n_ts, int32_t *len_ts, int32_t *frames);
 
 /* TSNDataSet.__getitem__ for a whole batch on the device (dataset.py:118-144 with the test-mode sampler
- * dataset.py:103-116 - the only one main.py uses, main.py:171-197 - and new_length 1): the dataset lives in HBM
+ * dataset.py:103-116 - the one main.py uses, main.py:171-197; the others: ta3n_gather_segments_sampled - and new_length 1): the dataset lives in HBM
  * as one packed fp32 store [total_frames, feature_dim] (ta3n_amd/feature_store.py writes it from the reference's
  * one-.t7-file-per-frame layout); video i owns rows [first_row[i], first_row[i] + num_frames[i]).  For each of the
  * n_videos ids the segment indices are computed in float64 exactly like the reference's Python and the selected
@@ -336,6 +336,41 @@ int ta3n_gather_segments(const float *store, const int64_t *first_row, const int
                          const int32_t *labels, const int32_t *video_ids, int n_videos, int num_segments,
                          int feature_dim, float *out, int32_t *labels_out, int32_t *segment_ids_out,
                          void *stream);
+
+/* The segment samplers of TSNDataSet (dataset.py:76-116) for new_length 1; every gather takes one.  A clip has nf frames, T segments:
+ *   TA3N_SAMPLER_TEST  _get_test_indices (dataset.py:103-116): offset int(tick / 2.0 + tick * x), tick = nf / T in float64; a clip
+ *                      shorter than T repeats its last frame.  What every entry point without sampler arguments computes.
+ *   TA3N_SAMPLER_VAL   _get_val_indices (dataset.py:92-101): the same arithmetic where nf >= T, frame 1 for every segment otherwise.
+ *   TA3N_SAMPLER_TRAIN _sample_indices (dataset.py:76-90), TSN's temporal jitter: avg = nf / T (integer); segment x takes offset
+ *                      x * avg + r with r uniform in [0, avg); avg == 0: frame 1 for every segment.  (The reference's sorted draw
+ *                      for avg == 0 and nf > T cannot occur with new_length 1 or 2.)
+ * Sampler key.  r is a function of (seed, step, slot, x) and of nothing else - not of the video id, the grid, first_video, or of
+ * whether a launch of its own or the step-opening launch assembles the rows.  slot is the position of the video in its gather call
+ * (in its batch half, for a ta3n_feed): a list that names a video twice gives it two draws.  With
+ *   mix32(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16        (uint32 arithmetic; the dropout stream's)
+ *   h = mix32(mix32(mix32(mix32(seed ^ 0x9E3779B9) ^ step) ^ slot) ^ x)
+ * r = (uint64(h) * avg) >> 32, the high half of the 64-bit product: within avg / 2^32 of uniform, where a modulo would favour the
+ * low residues.  ta3n_sample_segments is the host side of the same source the kernels compile: the 1-based frame ids out[T] that a
+ * gather with the same (sampler, seed, step) selects for the video in position slot.  TA3N_ERR_INVALID for an unknown sampler or
+ * num_frames < 1. */
+#define TA3N_SAMPLER_TEST 0
+#define TA3N_SAMPLER_VAL 1
+#define TA3N_SAMPLER_TRAIN 2
+int ta3n_sample_segments(int sampler, int num_frames, int num_segments, uint32_t seed, uint32_t step, uint32_t slot,
+                         int64_t *out /* 1-based, [T] */);
+
+/* ta3n_gather_segments with a sampler (sampler 0: the same launch, the same bits). */
+int ta3n_gather_segments_sampled(const float *store, const int64_t *first_row, const int32_t *num_frames,
+                                 const int32_t *labels, const int32_t *video_ids, int n_videos, int num_segments,
+                                 int feature_dim, float *out, int32_t *labels_out, int32_t *segment_ids_out,
+                                 void *stream, int sampler, uint32_t seed, uint32_t step);
+
+/* The stand-alone gather from a bf16 packed store (raw bf16 [total_frames, feature_dim], feature_dim % 8 == 0) into fp32 out: every
+ * selected row widened exactly (bf16 bits << 16), as ta3n_gather_segments_bf16_into widens into x. */
+int ta3n_gather_segments_bf16(const void *store16, const int64_t *first_row, const int32_t *num_frames,
+                              const int32_t *labels, const int32_t *video_ids, int n_videos, int num_segments,
+                              int feature_dim, float *out, int32_t *labels_out, int32_t *segment_ids_out,
+                              void *stream, int sampler, uint32_t seed, uint32_t step);
 
 /* ---- plan ---------------------------------------------------------------------- */
 
@@ -455,6 +490,15 @@ int ta3n_gather_segments_bf16_into(ta3n_plan *plan, const void *store16, const i
                                    const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x,
                                    float *ws, int32_t *labels_out, void *stream);
 
+/* The two above with a sampler (TA3N_SAMPLER_*; the slot of the key counts from video_ids[0], whatever first_video is); they are
+ * these with 0, 0, 0. */
+int ta3n_gather_segments_sampled_into(ta3n_plan *plan, const float *store, const int64_t *first_row, const int32_t *num_frames,
+                                      const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x,
+                                      float *ws, int32_t *labels_out, void *stream, int sampler, uint32_t seed, uint32_t step);
+int ta3n_gather_segments_bf16_sampled_into(ta3n_plan *plan, const void *store16, const int64_t *first_row, const int32_t *num_frames,
+                                           const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x,
+                                           float *ws, int32_t *labels_out, void *stream, int sampler, uint32_t seed, uint32_t step);
+
 /* The whole-prefix update of step n with its scalars passed by value, which also leaves `next` - the per-step
  * scalars of step n+1 - in the workspace: a loop that postpones each update to the start of the next step saves
  * the separate ta3n_set_hyper upload (one host-to-device copy per step).  Arithmetic of ta3n_sgd_step[_fused]. */
@@ -493,6 +537,9 @@ typedef struct {
     const int32_t *num_frames;  /* device [n_videos] */
     const int32_t *labels;      /* device [n_videos]; required for the source feed (written to ws["labels"]) */
     const int32_t *video_ids;   /* device [n_steps][ids_per_step] */
+    int32_t sampler;            /* TA3N_SAMPLER_*; all three zero: the test-mode sampler */
+    uint32_t seed;              /* sampler key: the feed's seed ... */
+    uint32_t step0;             /* ... and the step of the call's step 0: step k draws with step = step0 + k (mod 2^32), slot = position in the half */
 } ta3n_feed;
 typedef struct ta3n_comm ta3n_comm;
 int ta3n_train_steps(ta3n_plan *plan, const float *x, float *params, float *grads, float *momentum, float *ws, int fused_norm,

@@ -57,7 +57,10 @@ SYMBOLS = [
     "ta3n_set_heads_waves", "ta3n_get_heads_waves",
     "ta3n_num_live_ranges", "ta3n_live_range", "ta3n_sgd_live",
     "ta3n_shard_ranges", "ta3n_shard_sumsq", "ta3n_sgd_shard", "ta3n_shard_reduce_scatter", "ta3n_sharded_update", "ta3n_train_steps_sharded",
+    "ta3n_sample_segments", "ta3n_gather_segments_sampled", "ta3n_gather_segments_bf16", "ta3n_gather_segments_sampled_into",
+    "ta3n_gather_segments_bf16_sampled_into",
 ]
+SAMPLERS = {"test": 0, "val": 1, "train": 2}      # TA3N_SAMPLER_* (TSNDataSet._get_test_indices / _get_val_indices / _sample_indices)
 
 
 class Config(C.Structure):
@@ -83,7 +86,8 @@ class Hyper(C.Structure):
 class Feed(C.Structure):
     """ta3n_feed (include/ta3n_hip.h): device-side batch assembly of a multi-step call."""
     _fields_ = [("store", C.c_void_p), ("bf16", C.c_int32), ("ids_per_step", C.c_int32), ("first_row", C.c_void_p),
-                ("num_frames", C.c_void_p), ("labels", C.c_void_p), ("video_ids", C.c_void_p)]
+                ("num_frames", C.c_void_p), ("labels", C.c_void_p), ("video_ids", C.c_void_p),
+                ("sampler", C.c_int32), ("seed", C.c_uint32), ("step0", C.c_uint32)]      # all zero: the test-mode sampler
 
 
 class StepsJob(C.Structure):
@@ -132,6 +136,10 @@ def lib() -> C.CDLL:
     L.ta3n_segment_indices.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(i64)]
     L.ta3n_rnn_slots.argtypes = [C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)]
     L.ta3n_gather_segments.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    key = [C.c_int, C.c_uint32, C.c_uint32]      # sampler, seed, step
+    L.ta3n_sample_segments.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64)]
+    L.ta3n_gather_segments_sampled.argtypes = L.ta3n_gather_segments.argtypes + key
+    L.ta3n_gather_segments_bf16.argtypes = L.ta3n_gather_segments.argtypes + key
     L.ta3n_plan_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     L.ta3n_plan_destroy.argtypes = [vp]
     L.ta3n_plan_destroy.restype = None
@@ -181,6 +189,8 @@ def lib() -> C.CDLL:
                                                 C.POINTER(Feed), C.POINTER(Feed), vp]
     L.ta3n_gather_segments_into.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.ta3n_gather_segments_bf16_into.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.ta3n_gather_segments_sampled_into.argtypes = L.ta3n_gather_segments_into.argtypes + key
+    L.ta3n_gather_segments_bf16_sampled_into.argtypes = L.ta3n_gather_segments_into.argtypes + key
     L.ta3n_sgd_step_next.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp]
     L.ta3n_num_phases.argtypes = [vp, C.c_int]
     f32, f64 = C.c_float, C.c_double
@@ -259,6 +269,25 @@ def segment_indices(num_frames: int, num_segments: int, new_length: int = 1) -> 
     L = lib()
     out = (C.c_int64 * num_segments)()
     check(L.ta3n_segment_indices(num_frames, num_segments, new_length, out), "ta3n_segment_indices")
+    return list(out)
+
+
+def sampler_code(sampler) -> int:
+    """TA3N_SAMPLER_* of a sampler's name ("test" / "val" / "train"; a code passes through)."""
+    if isinstance(sampler, str) and sampler in SAMPLERS:
+        return SAMPLERS[sampler]
+    if not isinstance(sampler, (str, bool)) and sampler in SAMPLERS.values():
+        return int(sampler)
+    raise ValueError(f"sampler must be one of 'test', 'val', 'train', not {sampler!r}")
+
+
+def sample_segments(sampler, num_frames: int, num_segments: int, seed: int = 0, step: int = 0, slot: int = 0) -> List[int]:
+    """The 1-based frame ids a device gather with (sampler, seed, step) selects for the video in position `slot` of its call
+    (ta3n_sample_segments: the host side of the kernels' own rule, new_length 1)."""
+    L = lib()
+    out = (C.c_int64 * num_segments)()
+    check(L.ta3n_sample_segments(sampler_code(sampler), num_frames, num_segments, seed & 0xFFFFFFFF, step & 0xFFFFFFFF, slot & 0xFFFFFFFF, out),
+          "ta3n_sample_segments")
     return list(out)
 
 

@@ -543,15 +543,56 @@ int ta3n_time_update_launches(ta3n_plan *p, const float *x, float *params, float
     return TA3N_OK;
 }
 
-int ta3n_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
-                         const int32_t *video_ids, int n_videos, int num_segments, int feature_dim, float *out,
-                         int32_t *labels_out, int32_t *segment_ids_out, void *stream) {
+static bool known_sampler(int sampler) { return sampler >= TA3N_SAMPLER_TEST && sampler <= TA3N_SAMPLER_TRAIN; }
+
+int ta3n_gather_segments_sampled(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
+                                 const int32_t *video_ids, int n_videos, int num_segments, int feature_dim, float *out,
+                                 int32_t *labels_out, int32_t *segment_ids_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
     if (!store || !first_row || !num_frames || !video_ids || !out) return fail(TA3N_ERR_INVALID, "null argument");
     if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
     if (n_videos < 0 || num_segments <= 0 || feature_dim <= 0) return fail(TA3N_ERR_INVALID, "bad sizes");
+    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
     if ((feature_dim & 3) == 0 && (!aligned16(store) || !aligned16(out))) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (launch_gather_segments(store, first_row, num_frames, labels, video_ids, n_videos, num_segments, feature_dim, out, labels_out,
-                               segment_ids_out, nullptr, static_cast<hipStream_t>(stream)) != 0)
+                               segment_ids_out, nullptr, static_cast<hipStream_t>(stream), 0, sampler, seed, step) != 0)
+        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return TA3N_OK;
+}
+
+int ta3n_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
+                         const int32_t *video_ids, int n_videos, int num_segments, int feature_dim, float *out,
+                         int32_t *labels_out, int32_t *segment_ids_out, void *stream) {
+    return ta3n_gather_segments_sampled(store, first_row, num_frames, labels, video_ids, n_videos, num_segments, feature_dim, out, labels_out,
+                                        segment_ids_out, stream, TA3N_SAMPLER_TEST, 0, 0);
+}
+
+int ta3n_gather_segments_bf16(const void *store16, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
+                              const int32_t *video_ids, int n_videos, int num_segments, int feature_dim, float *out,
+                              int32_t *labels_out, int32_t *segment_ids_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
+    if (!store16 || !first_row || !num_frames || !video_ids || !out) return fail(TA3N_ERR_INVALID, "null argument");
+    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
+    if (n_videos < 0 || num_segments <= 0 || feature_dim <= 0) return fail(TA3N_ERR_INVALID, "bad sizes");
+    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
+    if ((feature_dim & 7) != 0 || !aligned16(store16) || !aligned16(out)) return fail(TA3N_ERR_INVALID, "feature_dim % 8 and 16-byte alignment required");
+    if (launch_gather_segments_bf16(store16, first_row, num_frames, labels, video_ids, n_videos, num_segments, feature_dim, out, labels_out,
+                                    nullptr, static_cast<hipStream_t>(stream), 0, sampler, seed, step, segment_ids_out) != 0)
+        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return TA3N_OK;
+}
+
+int ta3n_gather_segments_sampled_into(ta3n_plan *p, const float *store, const int64_t *first_row, const int32_t *num_frames,
+                                      const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
+                                      int32_t *labels_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
+    if (!p || !store || !first_row || !num_frames || !video_ids || !x || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
+    const Geom &g = p->geom;
+    if (n_videos < 0 || first_video < 0 || first_video + n_videos > g.B) return fail(TA3N_ERR_INVALID, "videos outside the batch");
+    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
+    if ((g.D & 3) != 0 || !aligned16(store) || !aligned16(x) || !aligned16(ws)) return fail(TA3N_ERR_INVALID, "feature_dim % 4 and 16-byte alignment required");
+    const size_t row0 = (size_t)first_video * g.T;
+    float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
+    if (launch_gather_segments(store, first_row, num_frames, labels, video_ids, n_videos, g.T, g.D, x + row0 * g.D, labels_out, nullptr,
+                               twin, static_cast<hipStream_t>(stream), g.pair_delta, sampler, seed, step) != 0)
         return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
     return TA3N_OK;
 }
@@ -559,15 +600,24 @@ int ta3n_gather_segments(const float *store, const int64_t *first_row, const int
 int ta3n_gather_segments_into(ta3n_plan *p, const float *store, const int64_t *first_row, const int32_t *num_frames,
                               const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
                               int32_t *labels_out, void *stream) {
-    if (!p || !store || !first_row || !num_frames || !video_ids || !x || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    return ta3n_gather_segments_sampled_into(p, store, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out, stream,
+                                             TA3N_SAMPLER_TEST, 0, 0);
+}
+
+int ta3n_gather_segments_bf16_sampled_into(ta3n_plan *p, const void *store16, const int64_t *first_row, const int32_t *num_frames,
+                                           const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
+                                           int32_t *labels_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
+    if (!p || !store16 || !first_row || !num_frames || !video_ids || !ws) return fail(TA3N_ERR_INVALID, "null argument");
     if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
     const Geom &g = p->geom;
     if (n_videos < 0 || first_video < 0 || first_video + n_videos > g.B) return fail(TA3N_ERR_INVALID, "videos outside the batch");
-    if ((g.D & 3) != 0 || !aligned16(store) || !aligned16(x) || !aligned16(ws)) return fail(TA3N_ERR_INVALID, "feature_dim % 4 and 16-byte alignment required");
+    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
+    if ((g.D & 7) != 0 || !aligned16(store16) || (x && !aligned16(x)) || !aligned16(ws)) return fail(TA3N_ERR_INVALID, "feature_dim % 8 and 16-byte alignment required");
+    if (!x && g.o_x16 < 0) return fail(TA3N_ERR_INVALID, "a plan without bf16 twins needs the fp32 input rows (x)");
     const size_t row0 = (size_t)first_video * g.T;
     float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
-    if (launch_gather_segments(store, first_row, num_frames, labels, video_ids, n_videos, g.T, g.D, x + row0 * g.D, labels_out, nullptr,
-                               twin, static_cast<hipStream_t>(stream), g.pair_delta) != 0)
+    if (launch_gather_segments_bf16(store16, first_row, num_frames, labels, video_ids, n_videos, g.T, g.D, x ? x + row0 * g.D : nullptr, labels_out,
+                                    twin, static_cast<hipStream_t>(stream), g.pair_delta, sampler, seed, step) != 0)
         return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
     return TA3N_OK;
 }
@@ -575,18 +625,8 @@ int ta3n_gather_segments_into(ta3n_plan *p, const float *store, const int64_t *f
 int ta3n_gather_segments_bf16_into(ta3n_plan *p, const void *store16, const int64_t *first_row, const int32_t *num_frames,
                                    const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
                                    int32_t *labels_out, void *stream) {
-    if (!p || !store16 || !first_row || !num_frames || !video_ids || !ws) return fail(TA3N_ERR_INVALID, "null argument");
-    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
-    const Geom &g = p->geom;
-    if (n_videos < 0 || first_video < 0 || first_video + n_videos > g.B) return fail(TA3N_ERR_INVALID, "videos outside the batch");
-    if ((g.D & 7) != 0 || !aligned16(store16) || (x && !aligned16(x)) || !aligned16(ws)) return fail(TA3N_ERR_INVALID, "feature_dim % 8 and 16-byte alignment required");
-    if (!x && g.o_x16 < 0) return fail(TA3N_ERR_INVALID, "a plan without bf16 twins needs the fp32 input rows (x)");
-    const size_t row0 = (size_t)first_video * g.T;
-    float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
-    if (launch_gather_segments_bf16(store16, first_row, num_frames, labels, video_ids, n_videos, g.T, g.D, x ? x + row0 * g.D : nullptr, labels_out,
-                                    twin, static_cast<hipStream_t>(stream), g.pair_delta) != 0)
-        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return TA3N_OK;
+    return ta3n_gather_segments_bf16_sampled_into(p, store16, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out,
+                                                  stream, TA3N_SAMPLER_TEST, 0, 0);
 }
 
 int ta3n_eval_metrics(ta3n_plan *p, float *ws, int n_videos, int reset, void *stream) {
@@ -688,6 +728,7 @@ static int feed_step(ta3n_plan *p, const ta3n_feed *f, int step, int first_video
     if (!f->store || !f->first_row || !f->num_frames || !f->video_ids) return fail(TA3N_ERR_INVALID, "ta3n_feed: null table");
     if (f->ids_per_step < 0 || f->ids_per_step > cap) return fail(TA3N_ERR_INVALID, "ta3n_feed: ids_per_step exceeds the batch half");
     if (labels_out && !f->labels) return fail(TA3N_ERR_INVALID, "ta3n_feed: the feed needs labels (the source feed; the target feed under TA3N_FLAG_TARGET_LABELS)");
+    if (!known_sampler(f->sampler)) return fail(TA3N_ERR_INVALID, "ta3n_feed: sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
     const int32_t *ids = f->video_ids + (size_t)step * f->ids_per_step;
     const size_t row0 = (size_t)first_video * g.T;
     float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
@@ -695,10 +736,12 @@ static int feed_step(ta3n_plan *p, const ta3n_feed *f, int step, int first_video
     if (f->bf16) {
         if (!twin && !x) return fail(TA3N_ERR_INVALID, "ta3n_feed: a plan without bf16 twins needs the fp32 input rows");
         rc = launch_gather_segments_bf16(f->store, f->first_row, f->num_frames, f->labels, ids, f->ids_per_step, g.T, g.D,
-                                         twin ? nullptr : x + row0 * g.D, labels_out, twin, s, g.pair_delta);
+                                         twin ? nullptr : x + row0 * g.D, labels_out, twin, s, g.pair_delta, f->sampler, f->seed,
+                                         f->step0 + (uint32_t)step);
     } else {
         rc = launch_gather_segments(static_cast<const float *>(f->store), f->first_row, f->num_frames, f->labels, ids, f->ids_per_step,
-                                    g.T, g.D, x + row0 * g.D, labels_out, nullptr, twin, s, g.pair_delta);
+                                    g.T, g.D, x + row0 * g.D, labels_out, nullptr, twin, s, g.pair_delta, f->sampler, f->seed,
+                                    f->step0 + (uint32_t)step);
     }
     return rc == 0 ? TA3N_OK : fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
 }
@@ -709,6 +752,7 @@ static int feed_job(ta3n_plan *p, const ta3n_feed *f, int step, int first_video,
     if (!f->store || !f->first_row || !f->num_frames || !f->video_ids) return fail(TA3N_ERR_INVALID, "ta3n_feed: null table");
     if (f->ids_per_step < 0 || f->ids_per_step > cap) return fail(TA3N_ERR_INVALID, "ta3n_feed: ids_per_step exceeds the batch half");
     if (labels_out && !f->labels) return fail(TA3N_ERR_INVALID, "ta3n_feed: the feed needs labels (the source feed; the target feed under TA3N_FLAG_TARGET_LABELS)");
+    if (!known_sampler(f->sampler)) return fail(TA3N_ERR_INVALID, "ta3n_feed: sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
     const size_t row0 = (size_t)first_video * g.T;
     float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
     if (f->bf16 && !twin && !x) return fail(TA3N_ERR_INVALID, "ta3n_feed: a plan without bf16 twins needs the fp32 input rows");
@@ -717,6 +761,7 @@ static int feed_job(ta3n_plan *p, const ta3n_feed *f, int step, int first_video,
     job->n_videos = f->ids_per_step; job->bf16 = f->bf16 ? 1 : 0;
     job->out = (f->bf16 && twin) ? nullptr : x + row0 * g.D;      // (a bf16 store feeding twins writes no fp32 rows: feed_step)
     job->twin = twin; job->labels_out = labels_out;
+    job->sampler = f->sampler; job->seed = f->seed; job->step = f->step0 + (uint32_t)step;      // (the draw's key: feed_step's)
     return TA3N_OK;
 }
 

@@ -56,7 +56,7 @@ __device__ __forceinline__ float hyper_scale(const Hyper *__restrict__ hy, int k
 // pass instead of storing a mask (nn.Dropout, reference models.py:131-132,
 // 574-575, 679-680; bit-matching torch's Philox/MT streams is not possible nor
 // required - SURVEY.md 7 "Dropout").
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {      // (host too: ta3n_sample_segments draws with the device's own code)
     x ^= x >> 16; x *= 0x7feb352dU;
     x ^= x >> 15; x *= 0x846ca68bU;
     x ^= x >> 16;
@@ -327,6 +327,8 @@ struct FeedJob {
     float *out, *twin;
     int32_t *labels_out;
     int32_t n_videos, bf16;
+    int32_t sampler;             // TA3N_SAMPLER_*; seed and step key the train sampler's draw (sample_offset)
+    uint32_t seed, step;
 };
 int launch_sgd_open_feed(const Geom &g, float *params, const float *grads, float *momentum, float *ws, int64_t begin, int64_t end,
                          bool fused_norm, float lr, float mu, float wd, float clip, const Hyper *next, const FeedJob feeds[2], hipStream_t stream);
@@ -336,11 +338,12 @@ int launch_eval_metrics(const Geom &g, float *ws, int n, int reset, hipStream_t 
 int launch_score(const Geom &g, const Ptrs &ptrs, const ScoreArgs &a, int n, int reset, hipStream_t stream);
 int launch_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                            const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, int32_t *seg_out,
-                           float *out_twin, hipStream_t stream, int64_t pair_delta = 0);
+                           float *out_twin, hipStream_t stream, int64_t pair_delta = 0, int sampler = 0, uint32_t seed = 0, uint32_t step = 0);
 
 int launch_gather_segments_bf16(const void *store16, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                                 const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, float *out_twin,
-                                hipStream_t stream, int64_t pair_delta = 0);
+                                hipStream_t stream, int64_t pair_delta = 0, int sampler = 0, uint32_t seed = 0, uint32_t step = 0,
+                                int32_t *seg_out = nullptr);
 
 
 }  // namespace ta3n

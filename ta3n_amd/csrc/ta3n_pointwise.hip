@@ -668,20 +668,43 @@ __global__ __launch_bounds__(256) void pool_avg_bwd_kernel(Geom g, Ptrs ptrs, in
 // TSNDataSet.__getitem__ for a whole batch on the device (reference dataset.py:103-116, 128-144, new_length 1):
 // one workgroup per output row (video v, segment x).  The segment index is computed in float64 exactly as the
 // reference's Python does (tick = n / T; int(tick / 2.0 + tick * x)); clips shorter than T repeat their last frame.
-__device__ __forceinline__ int segment_offset(int nf, int T, int x) {
+__host__ __device__ __forceinline__ int segment_offset(int nf, int T, int x) {
     if (nf < T) return x < nf ? x : nf - 1;
     const double tick = (double)nf / (double)T;             // dataset.py:103-116, float64 like the reference's Python
     return (int)(tick / 2.0 + tick * (double)x);
+}
+// The three samplers of TSNDataSet (dataset.py:76-116, new_length 1) as ONE rule for the kernels and for ta3n_sample_segments on the host:
+// the 0-based frame offset of segment x of a clip of nf frames.  TEST is segment_offset, untouched.  VAL (dataset.py:92-101) is the same
+// float64 arithmetic where nf >= T and frame 0 for every segment of a shorter clip (test mode repeats the LAST frame there).  TRAIN
+// (dataset.py:76-90, TSN's temporal jitter): avg = nf / T; segment x draws uniformly from its own stretch [x avg, (x + 1) avg), frame 0
+// where avg == 0.  The reference's middle branch - a sorted draw when avg == 0 and nf > T - cannot be reached with new_length 1 or 2
+// (avg == 0 means nf - new_length + 1 < T, so nf <= T); only the host TSNDataSet carries it.  The draw is a counter-based hash of
+// (seed, step, slot, x) and of nothing else (include/ta3n_hip.h "sampler key"): slot is the video's position in its gather call or
+// batch half - not its id, not its row in the batch, not the workgroup that copies it.  The hash reaches [0, avg) through the high half
+// of the 64-bit product (off by at most avg / 2^32 from uniform; a modulo would favour the low residues).
+__host__ __device__ __forceinline__ uint32_t sampler_draw(uint32_t seed, uint32_t step, uint32_t slot, uint32_t x, uint32_t avg) {
+    uint32_t h = mix32(seed ^ 0x9E3779B9U);
+    h = mix32(h ^ step);
+    h = mix32(h ^ slot);
+    h = mix32(h ^ x);
+    return (uint32_t)(((uint64_t)h * (uint64_t)avg) >> 32);
+}
+__host__ __device__ __forceinline__ int sample_offset(int sampler, int nf, int T, int x, uint32_t seed, uint32_t step, uint32_t slot) {
+    if (sampler == TA3N_SAMPLER_TEST) return segment_offset(nf, T, x);
+    if (sampler == TA3N_SAMPLER_VAL) return nf >= T ? segment_offset(nf, T, x) : 0;
+    const int avg = nf / T;
+    return avg > 0 ? x * avg + (int)sampler_draw(seed, step, slot, (uint32_t)x, (uint32_t)avg) : 0;
 }
 __device__ __forceinline__ void gather_row_f32(int row, const float *__restrict__ store, const int64_t *__restrict__ first_row,
                                                const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
                                                const int32_t *__restrict__ video_ids, int T, int D,
                                                float *__restrict__ out, int32_t *__restrict__ labels_out,
-                                               int32_t *__restrict__ seg_out, uint2 *__restrict__ out16, int64_t pair_delta) {
+                                               int32_t *__restrict__ seg_out, uint2 *__restrict__ out16, int64_t pair_delta,
+                                               int sampler, uint32_t seed, uint32_t step) {
     const int v = row / T, x = row - v * T;
     const int vid = video_ids[v];
     const int nf = num_frames[vid];
-    const int off = segment_offset(nf, T, x);
+    const int off = sample_offset(sampler, nf, T, x, seed, step, (uint32_t)v);      // (v: the slot - rows count from the call's first video)
     if (threadIdx.x == 0) {
         if (seg_out) seg_out[row] = off + 1;                    // the reference's ids are 1-based (img_00001.t7)
         if (labels_out && x == 0) labels_out[v] = labels[vid];
@@ -709,8 +732,10 @@ __global__ __launch_bounds__(256) void gather_segments_kernel(const float *__res
                                                               const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
                                                               const int32_t *__restrict__ video_ids, int T, int D,
                                                               float *__restrict__ out, int32_t *__restrict__ labels_out,
-                                                              int32_t *__restrict__ seg_out, uint2 *__restrict__ out16, int64_t pair_delta) {
-    gather_row_f32((int)blockIdx.x, store, first_row, num_frames, labels, video_ids, T, D, out, labels_out, seg_out, out16, pair_delta);
+                                                              int32_t *__restrict__ seg_out, uint2 *__restrict__ out16, int64_t pair_delta,
+                                                              int sampler, uint32_t seed, uint32_t step) {
+    gather_row_f32((int)blockIdx.x, store, first_row, num_frames, labels, video_ids, T, D, out, labels_out, seg_out, out16, pair_delta,
+                   sampler, seed, step);
 }
 
 // The same batch assembly from a bf16 packed store ("fp16/bf16 memory-mapped blob"): a quarter of the
@@ -720,12 +745,16 @@ __device__ __forceinline__ void gather_row_bf16(int row, const uint4 *__restrict
                                                 const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
                                                 const int32_t *__restrict__ video_ids, int T, int D,
                                                 float4 *__restrict__ out, int32_t *__restrict__ labels_out,
-                                                uint4 *__restrict__ out16, int64_t pair_delta) {
+                                                int32_t *__restrict__ seg_out, uint4 *__restrict__ out16, int64_t pair_delta,
+                                                int sampler, uint32_t seed, uint32_t step) {
     const int v = row / T, x = row - v * T;
     const int vid = video_ids[v];
     const int nf = num_frames[vid];
-    const int off = segment_offset(nf, T, x);
-    if (threadIdx.x == 0 && labels_out && x == 0) labels_out[v] = labels[vid];
+    const int off = sample_offset(sampler, nf, T, x, seed, step, (uint32_t)v);
+    if (threadIdx.x == 0) {
+        if (seg_out) seg_out[row] = off + 1;
+        if (labels_out && x == 0) labels_out[v] = labels[vid];
+    }
     const uint4 *__restrict__ src = store + (size_t)(first_row[vid] + off) * (D / 8);
     for (int i = threadIdx.x; i < D / 8; i += 256) {
         const uint4 q = src[i];
@@ -745,8 +774,10 @@ __global__ __launch_bounds__(256) void gather_segments_bf16_kernel(const uint4 *
                                                                    const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
                                                                    const int32_t *__restrict__ video_ids, int T, int D,
                                                                    float4 *__restrict__ out, int32_t *__restrict__ labels_out,
-                                                                   uint4 *__restrict__ out16, int64_t pair_delta) {
-    gather_row_bf16((int)blockIdx.x, store, first_row, num_frames, labels, video_ids, T, D, out, labels_out, out16, pair_delta);
+                                                                   int32_t *__restrict__ seg_out, uint4 *__restrict__ out16, int64_t pair_delta,
+                                                                   int sampler, uint32_t seed, uint32_t step) {
+    gather_row_bf16((int)blockIdx.x, store, first_row, num_frames, labels, video_ids, T, D, out, labels_out, seg_out, out16, pair_delta,
+                    sampler, seed, step);
 }
 
 // Validation metrics of main.validate / test_models.py (reference main.py:707-735, 809-822; test_models.py:155-198)
@@ -859,6 +890,8 @@ struct FeedHalf {
     int32_t *labels_out;         // nullptr: the target half without TA3N_FLAG_TARGET_LABELS
     float *twin;                 // bf16 twin rows of this half (nullptr: the plan keeps none)
     int32_t rows, bf16;          // ids_per_step * T; the store holds bf16
+    int32_t sampler;             // TA3N_SAMPLER_* and the key of its draw (sample_offset)
+    uint32_t seed, step;
 };
 struct FeedPair {
     FeedHalf half[2];
@@ -880,10 +913,11 @@ __global__ __launch_bounds__(256) void sgd_open_feed_kernel(Geom g, float *__res
     const FeedHalf &f = fp.half[h];
     if (f.bf16)
         gather_row_bf16(row, static_cast<const uint4 *>(f.store), f.first_row, f.num_frames, f.labels, f.video_ids, fp.T, fp.D,
-                        reinterpret_cast<float4 *>(f.out), f.labels_out, reinterpret_cast<uint4 *>(f.twin), f.twin ? fp.pair_delta : 0);
+                        reinterpret_cast<float4 *>(f.out), f.labels_out, nullptr, reinterpret_cast<uint4 *>(f.twin), f.twin ? fp.pair_delta : 0,
+                        f.sampler, f.seed, f.step);
     else
         gather_row_f32(row, static_cast<const float *>(f.store), f.first_row, f.num_frames, f.labels, f.video_ids, fp.T, fp.D,
-                       f.out, f.labels_out, nullptr, reinterpret_cast<uint2 *>(f.twin), f.twin ? fp.pair_delta : 0);
+                       f.out, f.labels_out, nullptr, reinterpret_cast<uint2 *>(f.twin), f.twin ? fp.pair_delta : 0, f.sampler, f.seed, f.step);
 }
 
 // Closes a fused-update step (gemm_tiles with SgdSide::p_new: every gradient tile already applied the Nesterov step to its own
@@ -1459,20 +1493,20 @@ int launch_sgd(const Geom &g, float *params, const float *grads, float *momentum
 
 int launch_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                            const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, int32_t *seg_out,
-                           float *out_twin, hipStream_t stream, int64_t pair_delta) {
+                           float *out_twin, hipStream_t stream, int64_t pair_delta, int sampler, uint32_t seed, uint32_t step) {
     if (n_videos <= 0) return 0;
     hipLaunchKernelGGL(gather_segments_kernel, dim3(n_videos * T), dim3(256), 0, stream, store, first_row, num_frames, labels, video_ids,
-                       T, D, out, labels_out, seg_out, reinterpret_cast<uint2 *>(out_twin), out_twin ? pair_delta : 0);
+                       T, D, out, labels_out, seg_out, reinterpret_cast<uint2 *>(out_twin), out_twin ? pair_delta : 0, sampler, seed, step);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int launch_gather_segments_bf16(const void *store16, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                                 const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, float *out_twin,
-                                hipStream_t stream, int64_t pair_delta) {
+                                hipStream_t stream, int64_t pair_delta, int sampler, uint32_t seed, uint32_t step, int32_t *seg_out) {
     if (n_videos <= 0) return 0;
     hipLaunchKernelGGL(gather_segments_bf16_kernel, dim3(n_videos * T), dim3(256), 0, stream, static_cast<const uint4 *>(store16), first_row,
-                       num_frames, labels, video_ids, T, D, reinterpret_cast<float4 *>(out), labels_out, reinterpret_cast<uint4 *>(out_twin),
-                       out_twin ? pair_delta : 0);
+                       num_frames, labels, video_ids, T, D, reinterpret_cast<float4 *>(out), labels_out, seg_out,
+                       reinterpret_cast<uint4 *>(out_twin), out_twin ? pair_delta : 0, sampler, seed, step);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1534,6 +1568,7 @@ int launch_sgd_open_feed(const Geom &g, float *params, const float *grads, float
         FeedHalf &f = fp.half[h];
         f.store = j.store; f.first_row = j.first_row; f.num_frames = j.num_frames; f.labels = j.labels; f.video_ids = j.video_ids;
         f.out = j.out; f.labels_out = j.labels_out; f.twin = j.twin; f.rows = j.n_videos > 0 ? j.n_videos * g.T : 0; f.bf16 = j.bf16;
+        f.sampler = j.sampler; f.seed = j.seed; f.step = j.step;
     }
     const int rows = fp.half[0].rows + fp.half[1].rows;
     hipLaunchKernelGGL(sgd_open_feed_kernel, dim3(blocks + rows), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1, ns.off, ns.n,
@@ -1580,3 +1615,10 @@ int launch_fill(float *dst, float value, int64_t n, hipStream_t stream) {
 }
 
 }  // namespace ta3n
+
+// The host side of sample_offset: the frames a gather with the same (sampler, seed, step) copies for the video in position `slot`.
+extern "C" int ta3n_sample_segments(int sampler, int num_frames, int num_segments, uint32_t seed, uint32_t step, uint32_t slot, int64_t *out) {
+    if (sampler < TA3N_SAMPLER_TEST || sampler > TA3N_SAMPLER_TRAIN || num_frames < 1 || num_segments <= 0 || !out) return TA3N_ERR_INVALID;
+    for (int x = 0; x < num_segments; ++x) out[x] = (int64_t)sample_offset(sampler, num_frames, num_segments, x, seed, step, slot) + 1;
+    return TA3N_OK;
+}

@@ -1222,15 +1222,19 @@ class TrainEngine:
         return self._labels[self.Bs:] if self.target_labels else None
 
     def _gather_step(self, feeds, k: int) -> None:
-        """Step k's batch halves assembled on the device from the feeds (for a step that goes out on its own, not inside a multi-step call)."""
+        """Step k's batch halves assembled on the device from the feeds (for a step that goes out on its own, not inside a multi-step call).
+        A store with a sampler (FeatureStore.sampled) draws with the absolute index of the step that is about to run (step_count)."""
         if feeds is None:
             return
         for (store, ids), first in zip(feeds, (0, self.Bs)):
             if store is not None:
-                store.gather_into(self, ids[k], first, labels_out=self._feed_labels_out(first))
+                sampler = getattr(store, "sampler", 0)
+                key = dict(sampler=sampler, seed=getattr(store, "seed", 0), step=self.step_count) if sampler else {}
+                store.gather_into(self, ids[k], first, labels_out=self._feed_labels_out(first), **key)
 
     def _feeds(self, feeds, k0: int):
-        """ta3n_feed structs (and the id tables that must outlive the enqueued gathers) of a multi-step call."""
+        """ta3n_feed structs (and the id tables that must outlive the enqueued gathers) of a multi-step call whose first step is step
+        number step_count (k0: its position in the tables).  A store with a sampler keys each step's draw by that absolute number."""
         fd, keep = [None, None], []
         if feeds is not None:
             for i, (store, ids) in enumerate(feeds):
@@ -1242,6 +1246,8 @@ class TrainEngine:
                 f.store = store.store.data_ptr(); f.bf16 = int(store.bf16); f.ids_per_step = ids.shape[1]
                 f.first_row = store.first_row.data_ptr(); f.num_frames = store.num_frames.data_ptr()
                 f.labels = store.labels.data_ptr(); f.video_ids = ids.data_ptr()
+                f.sampler, f.seed = getattr(store, "sampler", 0), getattr(store, "seed", 0) & 0xFFFFFFFF
+                f.step0 = self.step_count & 0xFFFFFFFF if f.sampler else 0
                 fd[i] = f
         return fd, keep
 

@@ -11,14 +11,18 @@ dataset_preparation/video2feature.py:206-217) and `TSNDataSet.__getitem__` (data
     <prefix>.idx.npy  int64 [n_videos, 3] = (first_row, num_frames, label)
 
 (UCF-HMDB_full: ~3.2 k videos x ~100 frames x 8 KiB = 2.5 GB - a sliver of the 288 GB of HBM), loaded to
-the GPU once, and a batch is one kernel: `ta3n_gather_segments` computes the reference's test-mode segment
-indices (dataset.py:103-116, float64, bit-exact) and copies the selected rows straight into the train
-step's input buffer.  List parsing and the list repeat/truncate rule (dataset.py:69-74) stay on the host.
+the GPU once, and a batch is one kernel: `ta3n_gather_segments*` computes the segment indices of one of the
+reference's three samplers - test mode (dataset.py:103-116, float64, bit-exact; the default), val mode
+(dataset.py:92-101) or the train mode's temporal jitter (dataset.py:76-90: a uniform draw inside each segment's
+stretch, from a counter-based hash of (seed, step, position in the batch) - include/ta3n_hip.h "sampler key") -
+and copies the selected rows straight into the train step's input buffer.  List parsing and the list
+repeat/truncate rule (dataset.py:69-74) stay on the host.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import copy
 from typing import Optional, Tuple
 
 import numpy as np
@@ -55,7 +59,8 @@ def pack(list_file: str, prefix: str, image_tmpl: str = "img_{:05d}.t7", root_pa
 
 class FeatureStore:
     """A packed dataset on one GPU.  `gather` is TSNDataSet.__getitem__ + DataLoader collation for a batch of
-    video ids, on the device."""
+    video ids, on the device.  sampler / seed: what TrainEngine.train_steps(feeds=...) draws the frames with (`sampled`)."""
+    sampler, seed = 0, 0      # TA3N_SAMPLER_TEST: the reference's test-mode frames
 
     def __init__(self, prefix: str, feature_dim: int, device: Optional[torch.device] = None):
         if not torch.cuda.is_available():
@@ -95,22 +100,22 @@ class FeatureStore:
     def __len__(self) -> int:
         return self.n_videos
 
+    def sampled(self, sampler, seed: int = 0) -> "FeatureStore":
+        """A view of this store (every tensor shared) that carries `.sampler` (TA3N_SAMPLER_* of "test" / "val" / "train") and `.seed`:
+        passed in train_steps(feeds=((store, ids), ...)) in place of the store, step k of the engine then draws its frames with
+        (sampler, seed, step k) - the same frames however the schedule is enqueued."""
+        view = copy.copy(self)
+        view.sampler, view.seed = _lib.sampler_code(sampler), int(seed) & 0xFFFFFFFF
+        return view
+
     def gather(self, video_ids: torch.Tensor, num_segments: int, out: Optional[torch.Tensor] = None,
-               labels_out: Optional[torch.Tensor] = None, segment_ids_out: Optional[torch.Tensor] = None):
-        """video_ids: int32 tensor on this device -> (features [n, T, D] written into `out`, int32 labels [n])."""
+               labels_out: Optional[torch.Tensor] = None, segment_ids_out: Optional[torch.Tensor] = None,
+               sampler="test", seed: int = 0, step: int = 0):
+        """video_ids: int32 tensor on this device -> (features [n, T, D] written into `out`, int32 labels [n]).  sampler: "test", "val"
+        or "train"; (seed, step) key the train sampler's draw, the video in position s of video_ids is its slot s."""
+        key = (_lib.sampler_code(sampler), int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF)
         ids = video_ids.to(device=self.device, dtype=torch.int32).contiguous()
         n, T, D = ids.numel(), num_segments, self.feature_dim
-        if self.bf16:        # (validation / host-side use: widen the selected rows with torch; the train step uses gather_into)
-            seg = torch.tensor([[s - 1 for s in _lib.segment_indices(int(nf), T)] for nf in self.num_frames[ids.long()].tolist()],
-                               device=self.device, dtype=torch.long)
-            rows = self.first_row[ids.long()].unsqueeze(1) + seg
-            feats = self.store[rows.reshape(-1)].view(torch.bfloat16).to(torch.float32).view(n, T, D)
-            lab = self.labels[ids.long()]
-            if out is not None:
-                out.view(-1)[: n * T * D].copy_(feats.reshape(-1))
-            if labels_out is not None:
-                labels_out[:n].copy_(lab)
-            return feats, lab
         if out is None:
             out = torch.empty(n * T, D, dtype=torch.float32, device=self.device)
         if labels_out is None:
@@ -118,23 +123,27 @@ class FeatureStore:
         assert out.is_contiguous() and out.numel() >= n * T * D and out.dtype == torch.float32
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(self._L.ta3n_gather_segments(p(self.store), p(self.first_row), p(self.num_frames), p(self.labels), p(ids), n, T, D,
-                                                p(out), p(labels_out), p(segment_ids_out), stream), "ta3n_gather_segments")
+        fn = "ta3n_gather_segments_bf16" if self.bf16 else "ta3n_gather_segments_sampled"      # (bf16: the rows widened by the kernel)
+        _lib.check(getattr(self._L, fn)(p(self.store), p(self.first_row), p(self.num_frames), p(self.labels), p(ids), n, T, D,
+                                        p(out), p(labels_out), p(segment_ids_out), stream, *key), fn)
         return out.view(-1)[: n * T * D].view(n, T, D), labels_out
 
-    def gather_into(self, engine, video_ids: torch.Tensor, first_video: int, labels_out: Optional[torch.Tensor] = None) -> None:
+    def gather_into(self, engine, video_ids: torch.Tensor, first_video: int, labels_out: Optional[torch.Tensor] = None,
+                    sampler="test", seed: int = 0, step: int = 0) -> None:
         """Assemble videos [first_video, first_video + n) of a TrainEngine's input batch on the device: the fp32 rows of
-        engine.X and - when the engine reads bf16 twins - the input twin, in one pass (ta3n_gather_segments_into)."""
+        engine.X and - when the engine reads bf16 twins - the input twin, in one pass (ta3n_gather_segments[_bf16]_sampled_into).
+        sampler, seed, step: as in gather; the slot counts from video_ids[0], whatever first_video is."""
+        key = (_lib.sampler_code(sampler), int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF)
         ids = video_ids.to(device=self.device, dtype=torch.int32).contiguous()
         assert engine.D == self.feature_dim
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         if self.bf16:      # the rows go into the input's bf16 twin as they are; fp32 rows only for an engine that does not read twins
-            _lib.check(self._L.ta3n_gather_segments_bf16_into(engine.plan.handle, p(self.store), p(self.first_row), p(self.num_frames),
-                                                              p(self.labels), p(ids), ids.numel(), int(first_video),
-                                                              None if engine.bf16_store else p(engine.X), p(engine.ws), p(labels_out), stream),
-                       "ta3n_gather_segments_bf16_into")
+            _lib.check(self._L.ta3n_gather_segments_bf16_sampled_into(engine.plan.handle, p(self.store), p(self.first_row), p(self.num_frames),
+                                                                      p(self.labels), p(ids), ids.numel(), int(first_video),
+                                                                      None if engine.bf16_store else p(engine.X), p(engine.ws), p(labels_out),
+                                                                      stream, *key), "ta3n_gather_segments_bf16_sampled_into")
             return
-        _lib.check(self._L.ta3n_gather_segments_into(engine.plan.handle, p(self.store), p(self.first_row), p(self.num_frames),
-                                                     p(self.labels), p(ids), ids.numel(), int(first_video), p(engine.X), p(engine.ws),
-                                                     p(labels_out), stream), "ta3n_gather_segments_into")
+        _lib.check(self._L.ta3n_gather_segments_sampled_into(engine.plan.handle, p(self.store), p(self.first_row), p(self.num_frames),
+                                                             p(self.labels), p(ids), ids.numel(), int(first_video), p(engine.X), p(engine.ws),
+                                                             p(labels_out), stream, *key), "ta3n_gather_segments_sampled_into")

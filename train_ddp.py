@@ -140,11 +140,26 @@ def validate_options(args, module_path: bool = False) -> None:
     need(len(args.beta) == 3 and len(args.place_adv) == 3, "--beta and --place_adv take three values [relation, video, frame]")
     need(len(args.batch_size) >= 2, "-b needs at least the source and target batch sizes")
     need(args.arch in ARCH_FEATURE_DIM, f"--arch {args.arch}")
+    # --segment_sampler (train_ddp.py's own, beside --feature_store): which of TSNDataSet's samplers the device batch assembly draws the
+    # training frames with; the per-frame loaders keep the reference's hard-wired test mode (main.py:171-197)
+    sampler = getattr(args, "segment_sampler", "test")
+    need(sampler in SEGMENT_SAMPLERS, f"--segment_sampler {sampler} (built: {', '.join(SEGMENT_SAMPLERS)})")
+    need(sampler == "test" or bool(getattr(args, "feature_store", None)),
+         f"--segment_sampler {sampler} without --feature_store (the device batch assembly draws the frames; built: test)")
     if args.add_loss_DA == "attentive_entropy" and args.use_attn != "none" and args.use_target != "none":
         need(args.place_adv[0] == "Y" and args.place_adv[1] == "Y",
              "attentive_entropy indexes pred_domain_all[1] (main.py:559-562): needs --place_adv Y Y *")
     if bad:
         raise SystemExit("train_ddp.py: unsupported option value(s):\n  " + "\n  ".join(bad))
+
+
+SEGMENT_SAMPLERS = ("test", "val", "train")
+
+
+def sampler_seed(domain: int, rank: int) -> int:
+    """The seed of a training store's sampler (FeatureStore.sampled): one per domain (0 source, 1 target) and rank, so that no two
+    batch halves of a job share a draw; the step number does the rest."""
+    return (0x5EED0000 + 2 * rank + domain) & 0xFFFFFFFF
 
 
 def train_list_sizes(num_source: int, num_target: int, batch_size, copy_list):
@@ -191,6 +206,10 @@ def main():
     parser.add_argument("--graph", action="store_true", help="replay a captured hipGraph (default: eager launches, faster here)")
     parser.add_argument("--feature_store", type=str, nargs="+", default=None, metavar="PREFIX",
                         help="packed feature stores (ta3n_amd.feature_store.pack): SRC TGT [VAL]; batches are assembled on the GPU")
+    parser.add_argument("--segment_sampler", choices=SEGMENT_SAMPLERS, default="test",
+                        help="with --feature_store: the sampler of the training batches - test: the reference's test-mode frames (what main.py "
+                             "trains on); val: TSNDataSet's val-mode frames; train: TSN's temporal jitter, a fresh draw inside every "
+                             "segment's stretch at every step.  Validation keeps test")
     args = parser.parse_args()
     validate_options(args)
     rank, local_rank, world = parallel.init_distributed()
@@ -230,6 +249,8 @@ def main():
         from ta3n_amd.feature_store import FeatureStore
         stores = [FeatureStore(pfx, D, dev) for pfx in args.feature_store]
         n_src, n_tgt = len(stores[0]), len(stores[1])
+        if args.segment_sampler != "test":      # the training stores draw their frames per step; the validation store keeps test mode
+            stores[:2] = [st.sampled(args.segment_sampler, sampler_seed(d, rank)) for d, st in enumerate(stores[:2])]
     elif args.synthetic:
         n_src, n_tgt = args.synthetic
     else:
@@ -343,8 +364,9 @@ def main():
                 eng.X.zero_()
                 if eng.bf16_store:
                     eng.refresh_bf16(x=True)                                            # twin of the zeroed (padding) rows
-                stores[0].gather_into(eng, xs[lo:hi].to(dev), 0, labels_out=eng._labels[:Bs])   # features + their bf16 twin
-                stores[1].gather_into(eng, xt[lo_t:hi_t].to(dev), Bs)
+                key = lambda st: dict(sampler=st.sampler, seed=st.seed, step=eng.step_count)
+                stores[0].gather_into(eng, xs[lo:hi].to(dev), 0, labels_out=eng._labels[:Bs], **key(stores[0]))   # features + their bf16 twin
+                stores[1].gather_into(eng, xt[lo_t:hi_t].to(dev), Bs, **key(stores[1]))
             else:
                 xs_r = torch.zeros(Bs, T, D); xs_r[: hi - lo] = xs[lo:hi]
                 xt_r = torch.zeros(Bt, T, D); xt_r[: hi_t - lo_t] = xt[lo_t:hi_t]
