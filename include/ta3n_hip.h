@@ -167,6 +167,35 @@ typedef enum {
  * TA3N_FLAG_BN_SHARED, _BF16_MFMA, _BF16_STORE, _F32_SPLIT (fp32 only), _FRAME_ATTN, _GENERAL_ATTN, _UNSHARED, _CLASS_WEIGHTS,
  * shared_fc_layers > 1, chain, split_k, wgrads_late, phase_tiles, layout_flags, and on trn-m a num_bottleneck other than 64, 128, 256 or 512. */
 #define TA3N_FLAG_SCORE_ONLY     (1u << 17)
+/* Training meters on the device: what main.train logs every print_freq steps (main.py:564-617: Prec@1 / Prec@5 of the source batch, the
+ * running averages of Loss, loss_c, loss_a, loss_e) without a host synchronisation per step, plus the accuracy of the domain discriminators.
+ * ONE more launch, the last of the fused step list (group 4, behind the launch that completes region "losses") and the last of the loss list
+ * (group 1): ta3n_train_step, ta3n_loss, ta3n_train_step_range, ta3n_train_steps*, the pipelined, Adam, sharded and _ddp variants and a
+ * captured graph of any of them run it without further code (the two-stream schedules keep their overlap: the launch follows the one
+ * their second collective waits for).  Every aggregation, every arithmetic.  The launch writes two regions, laid out behind every other,
+ * and nothing else; parameters, launches and every other region offset are those of the plan without the flag, bit for bit.
+ * A window is everything since the last ta3n_meters_reset (ta3n_init_workspace clears too).  Per launch:
+ *   region "meter_counts", int32[32]:
+ *     [0] steps              += 1
+ *     [1] nonfinite_steps    += 1 when losses[0] is NaN or +-Inf - and then NOTHING below is added or rewritten for that step
+ *     [2] source rows        += valid source rows (rows [0, hyper.valid_source) of "Y"; the reference's dummy rows never count)
+ *     [3] top-1 hits, [4] top-5 hits of those rows: rank = classes ahead of the label in torch.topk order, equal logits ranked by lower class
+ *         index - the rule of ta3n_eval_metrics; with fewer than six classes every row is a top-5 hit
+ *     [5] [6] [7] the same three numbers of the last finite step alone (the log line's .val)
+ *     [8 + 4 l + 2 d + {0, 1}], level l = 0 relation ("Pr"), 1 video ("Pv"), 2 frame ("Pf"), domain d = 0 source, 1 target: valid rows and rows
+ *         classified correctly; the prediction is target iff logit[1] > logit[0] (a tie, or a NaN, predicts source).  A level is counted when its
+ *         TA3N_FLAG_ADV_* bit is set and the plan has its logits row by row (no relation rows outside trn-m); otherwise its words stay zero
+ *     [20..23] scratch of the running launch, zero between launches; [24..31] unused
+ *   region "meter_sums", float64[8] (8-byte aligned inside the float workspace):
+ *     [0..5] += the six slots of region "losses" {total, cls, adv_rel, adv_vid, adv_frm, entropy}, each step with weight one, added by one
+ *         thread in slot order.  sum / (steps - nonfinite_steps) is the reference's AverageMeter .avg whenever the batches of the window are
+ *         full; the reference weights a short last batch by its size, this mean does not.  [6] [7] unused
+ * Counts are integers added by integer atomics (order-free); no float is added by an atomic: the same schedule twice gives the same bits.
+ * With TA3N_FLAG_MCD / TA3N_FLAG_FEATURE_GRADS (DAN, JAN) the meters hold what the loss kernel knows: loss_s, loss_c2 and loss_d stay the
+ * caller's, as without the flag.  Over several ranks every count and every sum is this rank's share: sum them (the loss slots carry the
+ * global 1 / n of ta3n_hyper.inv_n_*).
+ * ta3n_plan_create refuses by name, "TA3N_FLAG_TRAIN_METERS with ... is not built": TA3N_FLAG_SCORE_ONLY, chain. */
+#define TA3N_FLAG_TRAIN_METERS   (1u << 18)
 
 /* ta3n_config.aggregation */
 #define TA3N_AGG_TRN_M    0   /* 'trn-m': multi-scale TRN - the TA3N path (TRNmodule.py:27-86) */
@@ -462,6 +491,11 @@ int ta3n_eval_metrics(ta3n_plan *plan, float *ws, int n_videos, int reset, void 
  * same call twice gives the same bits.  Enqueue only.
  * TA3N_ERR_INVALID: a plan without the flag, n_videos outside [0, batch_source + batch_target]. */
 int ta3n_score(ta3n_plan *plan, const float *x, const float *params, float *ws, int n_videos, int reset, void *stream);
+
+/* Opens a new window of the training meters (TA3N_FLAG_TRAIN_METERS): enqueues the clearing of regions "meter_counts" and "meter_sums" on
+ * `stream` and nothing else.  Reading them is the caller's copy of ws[ta3n_ws_offset(plan, "meter_counts") ...] (both regions lie back to
+ * back, "meter_sums" 64 floats behind "meter_counts": one device-to-host copy).  TA3N_ERR_INVALID on a plan without the flag. */
+int ta3n_meters_reset(ta3n_plan *plan, float *ws, void *stream);
 
 /* clip_grad_norm_ + Nesterov SGD with weight decay (main.py:578-583) on the
  * flat live prefix; ws["grad_norm"] receives the pre-clip global norm. */

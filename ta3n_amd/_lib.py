@@ -35,6 +35,7 @@ FLAG_TARGET_ENTROPY = 1 << 14  # --add_loss_DA target_entropy: gamma * mean entr
 FLAG_GENERAL_ATTN = 1 << 15   # use_attn general: relation weights = softmax over the relations of a learned layer's scores (parameters attn_layer.0 / .2; regions Ua, gUa, gs); unfused entry points, single rank
 FLAG_UNSHARED = 1 << 16       # share_params N: the target rows' own first frame layer and video classifier (parameters fc_*_target); unfused entry points, single rank
 FLAG_SCORE_ONLY = 1 << 17     # a score-only plan: the eval-mode forward to the class logits on the training plan's parameter layout, scored by ta3n_score (ta3n_amd.scoring.Scorer)
+FLAG_TRAIN_METERS = 1 << 18   # training meters: one more launch per step accumulates loss sums, Prec@1/5 and domain accuracy in regions meter_counts / meter_sums
 AGG_TRN_M, AGG_AVGPOOL, AGG_RNN = 0, 1, 2      # AGG_RNN: slot max-pooling + one LSTM / GRU layer (rnn_cell, n_ts)
 AGG_TEMCONV = 4                                 # the 3-tap filter tcl_3_1 over the segments + ReLU + mean (3 would be the reference's 'trn', which it cannot run)
 RNN_CELLS = {"LSTM": 0, "GRU": 1}
@@ -59,6 +60,7 @@ SYMBOLS = [
     "ta3n_shard_ranges", "ta3n_shard_sumsq", "ta3n_sgd_shard", "ta3n_shard_reduce_scatter", "ta3n_sharded_update", "ta3n_train_steps_sharded",
     "ta3n_sample_segments", "ta3n_gather_segments_sampled", "ta3n_gather_segments_bf16", "ta3n_gather_segments_sampled_into",
     "ta3n_gather_segments_bf16_sampled_into",
+    "ta3n_meters_reset",
 ]
 SAMPLERS = {"test": 0, "val": 1, "train": 2}      # TA3N_SAMPLER_* (TSNDataSet._get_test_indices / _get_val_indices / _sample_indices)
 
@@ -161,6 +163,7 @@ def lib() -> C.CDLL:
     L.ta3n_backward.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ta3n_eval_metrics.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.ta3n_score.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
+    L.ta3n_meters_reset.argtypes = [vp, vp, vp]
     L.ta3n_has_fused_step.argtypes = [vp]
     L.ta3n_train_step.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ta3n_sgd_step.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -299,6 +302,48 @@ def rnn_slots(num_segments: int, n_ts: int) -> Tuple[int, List[int]]:
     frames = (C.c_int32 * 256)()
     check(L.ta3n_rnn_slots(num_segments, n_ts, C.byref(len_ts), frames), "ta3n_rnn_slots")
     return len_ts.value, list(frames[:len_ts.value * n_ts])
+
+
+# ---- training meters (TA3N_FLAG_TRAIN_METERS; include/ta3n_hip.h) ----
+METER_WORDS = 32          # int32 words of region "meter_counts"
+METER_SUMS = 8            # float64 words of region "meter_sums", 64 floats behind "meter_counts"
+METER_FLOATS = 64 + 2 * METER_SUMS      # floats from the start of "meter_counts" to the end of "meter_sums": one copy reads both
+METER_LEVELS = ("rel", "vid", "frm")
+METER_LOSSES = ("loss", "loss_c", "loss_adv_rel", "loss_adv_vid", "loss_adv_frm", "loss_e")
+
+
+def read_meters(plan: "Plan", ws: "torch.Tensor"):
+    """Both meter regions of a flagged plan's workspace with ONE device-to-host copy: (int64 counts [32], float64 sums [8])."""
+    o, _ = plan.region("meter_counts")
+    o2, _ = plan.region("meter_sums")
+    assert o2 == o + 64 and o2 % 2 == 0, (o, o2)
+    raw = ws[o:o + METER_FLOATS].cpu()
+    counts = raw[:METER_WORDS].view(torch.int32).to(torch.int64)
+    sums = raw[64:64 + 2 * METER_SUMS].view(torch.float64).clone()
+    return counts, sums
+
+
+def _pct(hit: int, n: int) -> float:
+    return 100.0 * hit / n if n else 0.0
+
+
+def decode_meters(counts, sums, world: int = 1) -> Dict[str, object]:
+    """The words of the two regions as the dict TrainEngine.meters() returns: per-step loss means, accuracies in percent, raw counts.
+    world > 1: the words are the SUM over that many ranks - every rank counted every step, and a rank's loss slots are its shard's share
+    of the job's mean: the step counts are divided by world (a step some rank found non-finite counts as one), the sums are the job's."""
+    c = [int(v) for v in counts]
+    s = [float(v) for v in sums]
+    finite = (c[0] - c[1]) / world
+    out: Dict[str, object] = {"steps": c[0] // world, "nonfinite_steps": -(-c[1] // world)}
+    for i, k in enumerate(METER_LOSSES):
+        out[k] = s[i] / finite if finite else 0.0
+    out.update(prec1=_pct(c[3], c[2]), prec5=_pct(c[4], c[2]), prec1_last=_pct(c[6], c[5]), prec5_last=_pct(c[7], c[5]))
+    dom = {lv: tuple(c[8 + 4 * l + 2 * d: 8 + 4 * l + 2 * d + 2] for d in (0, 1)) for l, lv in enumerate(METER_LEVELS)}
+    out["acc_domain"] = {lv: tuple(_pct(hit, n) for n, hit in dom[lv]) for lv in METER_LEVELS}
+    out["counts"] = {"source_rows": c[2], "top1": c[3], "top5": c[4], "last_source_rows": c[5], "last_top1": c[6], "last_top5": c[7],
+                     "domain": {lv: {"source": tuple(dom[lv][0]), "target": tuple(dom[lv][1])} for lv in METER_LEVELS}}      # (rows, correct)
+    out["loss_sums"] = dict(zip(METER_LOSSES, s[:6]))
+    return out
 
 
 class Plan:

@@ -157,6 +157,7 @@ int launch_phase(const ta3n_plan *p, int index, const Ptrs &ptrs, float *params_
         case PH_TEMCONV_FWD: case PH_TEMCONV_BWD: case PH_TEMCONV_WGRAD: return launch_temconv(p, ph.kind, ptrs, stream);
         case PH_GRAD_NORM: return launch_grad_norm(p->geom, ptrs.g, ptrs.ws, stream);
         case PH_SGD: return launch_sgd(p->geom, params_rw, ptrs.g, momentum, ptrs.ws, stream);
+        case PH_TRAIN_METERS: return launch_train_meters(p->geom, ptrs, p->meters, stream);
         default: return -1;
     }
 }
@@ -641,6 +642,16 @@ int ta3n_eval_metrics(ta3n_plan *p, float *ws, int n_videos, int reset, void *st
     return TA3N_OK;
 }
 
+int ta3n_meters_reset(ta3n_plan *p, float *ws, void *stream) {
+    if (!p || !ws) return fail(TA3N_ERR_INVALID, "null argument");
+    if (!(p->cfg.flags & TA3N_FLAG_TRAIN_METERS) || p->meters.o_counts < 0)
+        return fail(TA3N_ERR_INVALID, "ta3n_meters_reset: the plan was not created with TA3N_FLAG_TRAIN_METERS");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(ws + p->meters.o_counts, 0, (size_t)MT_WORDS * sizeof(int32_t), s));
+    HIP_TRY(hipMemsetAsync(ws + p->meters.o_sums, 0, (size_t)METER_SUMS * sizeof(double), s));
+    return TA3N_OK;
+}
+
 int ta3n_score(ta3n_plan *p, const float *x, const float *params, float *ws, int n_videos, int reset, void *stream) {
     if (!p || !x || !params || !ws) return fail(TA3N_ERR_INVALID, "null argument");
     if (!(p->cfg.flags & TA3N_FLAG_SCORE_ONLY) || p->score.o_prob < 0) return fail(TA3N_ERR_INVALID, "ta3n_score: the plan was not created with TA3N_FLAG_SCORE_ONLY");
@@ -983,7 +994,7 @@ int ta3n_train_steps_sharded(ta3n_plan *p, ta3n_comm *c, const float *x, float *
     hipEvent_t fork = comm_event(c, 0), join = comm_event(c, 1), fork2 = comm_event(c, 2), join2 = comm_event(c, 3);
     if (two && (!fork || !join || !fork2 || !join2)) return fail(TA3N_ERR_HIP, "hipEventCreate failed");
     const Geom &g = p->geom;
-    const int n = ta3n_num_phases(p, 4);
+    const int n = ta3n_num_phases(p, 4) - ((p->cfg.flags & TA3N_FLAG_TRAIN_METERS) ? 1 : 0);      // (the meters launch follows the step's last)
     if (n < 3) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
     // with wgrads_late the last launch also produces gradients of region B: its reduce-scatter then cannot start before that launch
     const bool early_b = two && p->cfg.wgrads_late == 0;
@@ -1014,7 +1025,7 @@ int ta3n_train_steps_sharded(ta3n_plan *p, ta3n_comm *c, const float *x, float *
             if ((rc = comm_reduce_scatter_sum(c, grads, sh.a_end, sh.b_chunk, scratch_bf16, cs)) != TA3N_OK) return rc;
             if (hipEventRecord(join, cs) != hipSuccess) return fail(TA3N_ERR_HIP, "event record failed");
         }
-        if ((rc = run_group(p, 4, ptrs, nullptr, nullptr, s, nullptr, n - 1, 1)) != TA3N_OK) return rc;
+        if ((rc = run_group(p, 4, ptrs, nullptr, nullptr, s, nullptr, n - 1, 1 << 30)) != TA3N_OK) return rc;
         if (!early_b && (rc = comm_reduce_scatter_sum(c, grads, sh.a_end, sh.b_chunk, scratch_bf16, s)) != TA3N_OK) return rc;
         if ((rc = comm_reduce_scatter_sum(c, grads, 0, sh.a_chunk, scratch_bf16, s)) != TA3N_OK) return rc;
         if (early_b && hipStreamWaitEvent(s, join, 0) != hipSuccess) return fail(TA3N_ERR_HIP, "event join failed");

@@ -214,7 +214,8 @@ int ta3n_all_reduce_sum(ta3n_comm *c, float *buf, int64_t count, void *scratch_b
 int ta3n_train_step_ddp(ta3n_plan *p, ta3n_comm *c, const float *x, const float *params, float *grads, float *ws,
                         void *scratch_bf16, void *stream, void *comm_stream) {
     if (!p || !c || !x || !params || !grads || !ws) return fail(TA3N_ERR_INVALID, "null argument");
-    const int n = ta3n_num_phases(p, 4);
+    const int meters = (p->cfg.flags & TA3N_FLAG_TRAIN_METERS) ? 1 : 0;      // (the meters launch follows the step's last)
+    const int n = ta3n_num_phases(p, 4) - meters;
     if (n < 2) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
     const int64_t n1 = p->first_floats, live = p->live_floats;
     char *s16 = static_cast<char *>(scratch_bf16);
@@ -231,7 +232,7 @@ int ta3n_train_step_ddp(ta3n_plan *p, ta3n_comm *c, const float *x, const float 
     if (hipEventRecord(c->fork, s) != hipSuccess || hipStreamWaitEvent(cs, c->fork, 0) != hipSuccess) return fail(TA3N_ERR_HIP, "event fork failed");
     rc = ta3n_all_reduce_sum(c, grads + n1, live - n1, s16 ? s16 + 2 * n1 : nullptr, comm_stream);
     if (rc != TA3N_OK) return rc;
-    rc = ta3n_train_step_range(p, x, params, grads, ws, n - 1, 1, stream);
+    rc = ta3n_train_step_range(p, x, params, grads, ws, n - 1, 1 + meters, stream);
     if (rc != TA3N_OK) return rc;
     if (hipEventRecord(c->join, s) != hipSuccess || hipStreamWaitEvent(cs, c->join, 0) != hipSuccess) return fail(TA3N_ERR_HIP, "event join failed");
     rc = ta3n_all_reduce_sum(c, grads, n1, scratch_bf16, comm_stream);

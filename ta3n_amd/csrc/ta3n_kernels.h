@@ -336,6 +336,8 @@ int launch_shard_sumsq(const Geom &g, const float *grads, float *ws, int64_t a0,
 int launch_eval_metrics(const Geom &g, float *ws, int n, int reset, hipStream_t stream);
 // TA3N_FLAG_SCORE_ONLY (ta3n_score.hip): classifier, softmax, rank and metrics of the first n videos, behind the plan's launch list
 int launch_score(const Geom &g, const Ptrs &ptrs, const ScoreArgs &a, int n, int reset, hipStream_t stream);
+// TA3N_FLAG_TRAIN_METERS (ta3n_meters.hip): one step's loss slots, source accuracy and domain accuracy added to the two meter regions
+int launch_train_meters(const Geom &g, const Ptrs &ptrs, const MetersArgs &a, hipStream_t stream);
 int launch_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                            const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, int32_t *seg_out,
                            float *out_twin, hipStream_t stream, int64_t pair_delta = 0, int sampler = 0, uint32_t seed = 0, uint32_t step = 0);

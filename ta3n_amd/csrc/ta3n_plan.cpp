@@ -347,6 +347,23 @@ int finish_plan(ta3n_plan &p, Builder &b, std::string &err) {
         p.class_w_off = b.add_region("class_w", 64);
         if (!workspace_fits(p, err)) return TA3N_ERR_INVALID;
     }
+    // TA3N_FLAG_TRAIN_METERS: one launch behind the fused step list (group 4, where the plan has one) and behind the loss list (group 1),
+    // two regions behind everything else.  Only under the flag: no other plan changes by a byte.  A level is counted when its ADV flag is
+    // set and the plan has its logits row by row (no relation rows outside trn-m: region "Pr" is a stub there).
+    if (p.cfg.flags & TA3N_FLAG_TRAIN_METERS) {
+        const Geom &g = p.geom;
+        auto rows_of = [&p](const char *name) { for (const auto &r : p.regions) if (r.name == name) return r.size / 2; return (int64_t)0; };
+        p.meters.levels = ((p.cfg.flags & TA3N_FLAG_ADV_RELATION) && g.n_rel > 0 && rows_of("Pr") == (int64_t)g.B * g.n_rel ? 1 : 0) |
+                          ((p.cfg.flags & TA3N_FLAG_ADV_VIDEO) && rows_of("Pv") == g.B ? 2 : 0) |
+                          ((p.cfg.flags & TA3N_FLAG_ADV_FRAME) && rows_of("Pf") == (int64_t)g.B * g.T ? 4 : 0);
+        p.meters.o_counts = (int32_t)b.add_region("meter_counts", MT_WORDS);
+        p.meters.o_sums = (int32_t)b.add_region("meter_sums", 2 * METER_SUMS);      // (regions start on multiples of 64 floats: 8-byte aligned)
+        if (!workspace_fits(p, err)) return TA3N_ERR_INVALID;
+        bool fused = false;
+        for (const Phase &ph : p.phases) fused = fused || ph.group == 4;
+        if (fused) b.add_simple_phase(PH_TRAIN_METERS, 4);
+        b.add_simple_phase(PH_TRAIN_METERS, 1);
+    }
     return TA3N_OK;
 }
 
@@ -1638,6 +1655,9 @@ extern "C" int ta3n_rnn_slots(int num_segments, int n_ts, int32_t *len_ts, int32
 // plan is laid out (add_bf16_twins): build, look, and rebuild without the blocking where it cannot be used.
 int ta3n::build_plan(ta3n_plan &p, std::string &err) {
     const ta3n_config cfg = p.cfg;
+    // TA3N_FLAG_TRAIN_METERS: a score-only plan has no step to meter; a chained step list is an experiments build's
+    if ((cfg.flags & TA3N_FLAG_TRAIN_METERS) && (cfg.flags & TA3N_FLAG_SCORE_ONLY)) { err = "TA3N_FLAG_TRAIN_METERS with TA3N_FLAG_SCORE_ONLY is not built"; return TA3N_ERR_INVALID; }
+    if ((cfg.flags & TA3N_FLAG_TRAIN_METERS) && cfg.chain) { err = "TA3N_FLAG_TRAIN_METERS with chain is not built"; return TA3N_ERR_INVALID; }
     if (cfg.flags & TA3N_FLAG_SCORE_ONLY) return build_plan_score(p, err);
     // ta3n_config.layout_flags: build the donor first and place this plan's parameters where the donor has them
     std::vector<ParamInfo> layout;

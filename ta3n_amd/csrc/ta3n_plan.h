@@ -53,6 +53,8 @@ struct ta3n_plan {
     ta3n::TemconvArgs temconv = {-1, -1, -1, -1};
     // TA3N_FLAG_SCORE_ONLY: the launch argument of the score kernel (o_prob < 0 on every other plan)
     ta3n::ScoreArgs score = {0, 0, -1, -1, -1, -1, -1};
+    // TA3N_FLAG_TRAIN_METERS: the launch argument of the meters kernel (o_counts < 0 on every other plan)
+    ta3n::MetersArgs meters = {-1, -1, 0};
     int64_t class_w_off = 0;    // ws offset of region "class_w" (TA3N_FLAG_CLASS_WEIGHTS; 0 without it): what the launchers put into Hyper::class_w_off
     uint64_t deny_blocking = 0;   // bit i: phase i must not use register-blocked tiles (it does not read bf16 twins; build_plan's retry)
     // device copies (created lazily by the launcher)

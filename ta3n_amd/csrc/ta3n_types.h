@@ -116,6 +116,27 @@ enum PhaseKind : int32_t {
     PH_TEMCONV_FWD = 20,     // V = mean_t relu(w0 F1[t-1] + w1 F1[t] + w2 F1[t+1] + c), Vd = dropout_v(V), loss slots = 0
     PH_TEMCONV_BWD = 21,     // gradient at V back through the mean, the ReLU and the filter (-> gZ1 or its additive base); tc_part[b] = this video's share of the four parameter gradients
     PH_TEMCONV_WGRAD = 22,   // fixed-order sum of tc_part over the videos -> gradient entries of tcl_3_1.conv2d.{weight, bias}, their sum of squares
+    // TA3N_FLAG_TRAIN_METERS (ta3n_meters.hip; offsets in ta3n_plan::meters): 23, the next number.  Only flagged plans contain it.  It is
+    // numbered by its position because tests/test_plan_cpu.py pins the explicitly numbered kinds above as exactly what the base interpreter
+    // tests/plan_interp.py runs; this one is run by its subclass tests/meters_reference.py (tests/test_train_meters_cpu.py pins its number)
+    PH_TRAIN_METERS,         // last launch of the step: loss sums, Prec@1/5 of the source rows, domain accuracy per level, accumulated in "meter_counts" / "meter_sums"
+};
+static_assert(PH_TRAIN_METERS == 23, "launch kinds keep their numbers: tests and recorded plans mirror them");
+
+// TA3N_FLAG_TRAIN_METERS: what the meters kernel (ta3n_meters.hip) takes by value beside Geom.  The int32 words of region "meter_counts":
+enum MeterSlot : int32_t {
+    MT_STEPS = 0, MT_NONFINITE = 1,
+    MT_ROWS = 2, MT_TOP1 = 3, MT_TOP5 = 4,                    // window: valid source rows, top-1 hits, top-5 hits
+    MT_LAST_ROWS = 5, MT_LAST_TOP1 = 6, MT_LAST_TOP5 = 7,     // the same three of the last finite step alone
+    MT_DOMAIN = 8,                                            // [level: relation, video, frame][domain: source, target]{valid rows, classified correctly}
+    MT_CUR = 20,                                              // in-launch scratch of the three last-step numbers (zero between launches)
+    MT_TICKET = 23,                                           // workgroups of the running launch that have finished (zero between launches)
+    MT_WORDS = 32,
+};
+constexpr int METER_SUMS = 8;        // float64 words of region "meter_sums" (the six loss slots, two spare)
+struct MetersArgs {
+    int32_t o_counts, o_sums;        // ws offsets (floats) of the two regions; o_sums is even (8-byte aligned)
+    int32_t levels;                  // bit l: adversarial level l (0 relation, 1 video, 2 frame) is counted
 };
 
 // TA3N_AGG_TEMCONV: what the three kernels of ta3n_temconv.hip take by value

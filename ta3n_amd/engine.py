@@ -188,6 +188,7 @@ class TrainEngine:
 
     # --pretrain_source is off unless the constructor turns it on (_setup_pretrain)
     pretrain_source = False
+    train_meters = False      # ... and so are the training meters (_check_options)
     plan_pre: Optional["_lib.Plan"] = None
     ws_pre: Optional[torch.Tensor] = None
 
@@ -203,13 +204,14 @@ class TrainEngine:
                  peer_exchange: Optional[bool] = None, ddp_buckets: Optional[int] = None, share_comm: bool = False,
                  add_fc: int = 1, optimizer: str = "SGD", betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8,
                  class_weights: Optional[Sequence[float]] = None, domain_weights: Optional[Sequence[float]] = None,
-                 share_params: str = "Y", pretrain_source: bool = False):
+                 share_params: str = "Y", pretrain_source: bool = False, train_meters: bool = False):
         sw = self._switches = _resolve_switches(sharded_update, peer_exchange, grad_transport, ddp_buckets, split_k, chain)
         flags, fused, features, context = self._check_options(
             sw, flags=flags, fused=fused, num_class=num_class, process_group=process_group, optimizer=optimizer, betas=betas, eps=eps,
             class_weights=class_weights, domain_weights=domain_weights, add_fc=add_fc, use_bn=use_bn, dis_DA=dis_DA, place_dis=place_dis,
             alpha=alpha, ens_DA=ens_DA, mu=mu, aggregation=aggregation, wgrads_late=wgrads_late, phase_tiles=phase_tiles,
-            f32_split=f32_split, bf16=bf16, bf16_store=bf16_store, share_params=share_params, pretrain_source=pretrain_source)
+            f32_split=f32_split, bf16=bf16, bf16_store=bf16_store, share_params=share_params, pretrain_source=pretrain_source,
+            train_meters=train_meters)
         if not torch.cuda.is_available():
             raise _lib.Ta3nError("TrainEngine needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -246,7 +248,7 @@ class TrainEngine:
 
     def _check_options(self, sw: "_Switches", *, flags, fused, num_class, process_group, optimizer, betas, eps, class_weights, domain_weights,
                        add_fc, use_bn, dis_DA, place_dis, alpha, ens_DA, mu, aggregation, wgrads_late, phase_tiles, f32_split, bf16, bf16_store,
-                       share_params="Y", pretrain_source=False):
+                       share_params="Y", pretrain_source=False, train_meters=False):
         """Refuses what is not built and composes the plan's flags from the options; touches no device and no plan.  Returns (flags,
         fused, features, context): the features that are on (rows of options.FEATURES) and the one context all of them were asked in,
         which the constructor asks again with the world size once it knows it (options.world_refusal)."""
@@ -386,6 +388,14 @@ class TrainEngine:
         self.pretrain_source = bool(pretrain_source)
         if self.pretrain_source:
             ask("pretrain")
+        # train_meters (or TA3N_FLAG_TRAIN_METERS in `flags`): the last launch of every step adds the step's loss slots, the source rows'
+        # Prec@1 / Prec@5 and the domain discriminators' accuracy to two workspace regions (meters(), reset_meters()): what main.train logs
+        # every print_freq steps (main.py:564-617), without a host synchronisation and for the steps between two log lines too
+        if train_meters:
+            flags |= _lib.FLAG_TRAIN_METERS
+        self.train_meters = bool(flags & _lib.FLAG_TRAIN_METERS)
+        if self.train_meters:
+            ask("train_meters")
         return flags, fused, features, context
 
     def _create_plan(self, sw: "_Switches", flags: int, fused: bool, *, fc_dim, tile_config, phase_tiles, xcd_aware, wgrads_late) -> None:
@@ -401,7 +411,7 @@ class TrainEngine:
                 phase_tiles[int(i)] = int(code)
         # chained launches (ta3n_config.chain): the fused trn-m step in 5 launches instead of 8; as an argument it is taken as given, as
         # TA3N_CHAIN=1 only where it is built
-        chain = sw.chain_arg if sw.chain_given else (sw.chain_env and plain and bool(fused))
+        chain = sw.chain_arg if sw.chain_given else (sw.chain_env and plain and bool(fused) and not self.train_meters)
         self._flags = int(flags)
         # (kept: the source-only plan of pretrain_source is built from the same choices, _setup_pretrain)
         self._plan_args = (self.Bs, self.Bt, self.T, self.D, fc_dim, self.C)
@@ -552,8 +562,9 @@ class TrainEngine:
         self.ws_pre: Optional[torch.Tensor] = None
         if not self.pretrain_source:
             return
-        pre_flags = self._flags & ~PRETRAIN_DROPPED_FLAGS
-        self.plan_pre = _lib.Plan(*self._plan_args, pre_flags, layout_flags=0 if pre_flags == self._flags else self._flags, **self._plan_kw)
+        own = self._flags & ~_lib.FLAG_TRAIN_METERS      # (the meters are the step's: the pass has none, and the flag moves no parameter)
+        pre_flags = own & ~PRETRAIN_DROPPED_FLAGS
+        self.plan_pre = _lib.Plan(*self._plan_args, pre_flags, layout_flags=0 if pre_flags == own else own, **self._plan_kw)
         p = self.plan_pre
         if p.param_floats != self.plan.param_floats or [q[:3] for q in p.params] != [q[:3] for q in self.plan.params]:
             raise _lib.Ta3nError("pretrain_source: the source-only plan does not lie on the step's parameter layout")
@@ -617,6 +628,7 @@ class TrainEngine:
                 f"{', general attention (use_attn general)' if self.general_attn else ''}"
                 f"{', unshared target layers (share_params N)' if self.unshared else ''}"
                 f"{', source-only pass before every step (pretrain_source)' if self.pretrain_source else ''}"
+                f"{', training meters on the device (train_meters)' if self.train_meters else ''}"
                 f"{', domain weights ({:.3g}, {:.3g})'.format(*self.domain_weights) if self.domain_weights is not None else ''}: {step}")
 
     # ---- plumbing ----
@@ -984,11 +996,12 @@ class TrainEngine:
                                                    C.c_void_p(self._comm_stream.cuda_stream)), "ta3n_train_step_ddp")
             self._bn_track()
             return
-        n = self._L.ta3n_num_phases(self.plan.handle, 4)
+        meters = 1 if self.train_meters else 0      # (the meters launch follows the step's last)
+        n = self._L.ta3n_num_phases(self.plan.handle, 4) - meters
         args = (self.plan.handle, self.X.data_ptr(), self.P.data_ptr(), self.G.data_ptr(), self.ws.data_ptr())
         _lib.check(self._L.ta3n_train_step_range(*args, 0, n - 1, self._stream()), "ta3n_train_step_range")
         w1 = parallel.all_reduce_sum_async(self.G[self._n_first: self.plan.live_floats], self.pg, self._ddp_selftest)
-        _lib.check(self._L.ta3n_train_step_range(*args, n - 1, 1, self._stream()), "ta3n_train_step_range")
+        _lib.check(self._L.ta3n_train_step_range(*args, n - 1, 1 + meters, self._stream()), "ta3n_train_step_range")
         w2 = parallel.all_reduce_sum_async(self.G[: self._n_first], self.pg, self._ddp_selftest)
         for w in (w1, w2):
             if w is not None:
@@ -1509,6 +1522,29 @@ class TrainEngine:
         if self.frame_attn:      # use_attn_frame: the frame-level weights (feat_f1 stays the un-attended feat[2], models.py:600-603)
             out["attn_frame"] = self.region("attn_frame", (B, T))
         return out
+
+    # ---- training meters (TA3N_FLAG_TRAIN_METERS) ----
+    def _need_meters(self, what: str) -> None:
+        if not self.train_meters:
+            raise _lib.Ta3nError(f"{what}: this engine was built without train_meters")
+
+    def meter_words(self):
+        """The two meter regions as they lie in the workspace, with ONE device-to-host copy: (int64 counts [32], float64 sums [8]) - what a
+        multi-rank caller sums over the ranks before decoding (_lib.decode_meters)."""
+        self._need_meters("meter_words")
+        return _lib.read_meters(self.plan, self.ws)
+
+    def meters(self) -> Dict[str, object]:
+        """The window since the last reset_meters(): steps, nonfinite_steps; loss, loss_c, loss_adv_rel, loss_adv_vid, loss_adv_frm, loss_e
+        as per-step means; prec1 / prec5 in percent over the window and prec1_last / prec5_last of the last step; acc_domain
+        {level: (source %, target %)}; the raw counts and loss sums.  This rank's share (train_ddp.py sums over the ranks).  One
+        device-to-host copy, which waits for the stream."""
+        return _lib.decode_meters(*self.meter_words())
+
+    def reset_meters(self) -> None:
+        """Opens a new window: enqueues the clearing of both regions, nothing else."""
+        self._need_meters("reset_meters")
+        _lib.check(self._L.ta3n_meters_reset(self.plan.handle, self.ws.data_ptr(), self._stream()), "ta3n_meters_reset")
 
     def losses(self) -> Dict[str, float]:
         v = self.region("losses")[:6].tolist()

@@ -153,6 +153,11 @@ FEATURES = {
         labels={"f32_split": "f32_split (f32x3)"},
         params="optimizer dis_DA ens_DA use_attn use_attn_frame share_params add_fc use_bn f32_split feeds capture fused_update multi_step world "
                "process_group ddp_selftest sharded_update peer_exchange"),
+    # TrainEngine(train_meters=True): TA3N_FLAG_TRAIN_METERS - one more launch behind the step's launch list keeps loss sums, Prec@1/5 and the
+    # domain discriminators' accuracy on the device; every aggregation, arithmetic, optimiser, schedule and world size, chained launches excepted
+    "train_meters": Row(
+        on=lambda c: True, without=("chain",), head="train_meters", tail=" (the meters launch stands behind the plain launch lists)",
+        reads=_CHAIN_AS_PASSED, params="chain"),
 }
 
 

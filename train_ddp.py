@@ -162,6 +162,22 @@ def sampler_seed(domain: int, rank: int) -> int:
     return (0x5EED0000 + 2 * rank + domain) & 0xFFFFFFFF
 
 
+def format_train_meters(m, loss_last: float, show_a: bool = True, show_e: bool = True) -> str:
+    """The accuracy and loss fields of the reference's training line (main.py:590-604) from the device's training meters (m:
+    _lib.decode_meters of the window's words, summed over the ranks; loss_last: the last step's total loss), then the domain
+    discriminators' accuracy per level (source / target, percent) and the count of non-finite steps when there were any."""
+    out = (f"Prec@1 {m['prec1_last']:.3f} ({m['prec1']:.3f})\tPrec@5 {m['prec5_last']:.3f} ({m['prec5']:.3f})\t"
+           f"Loss {loss_last:.4f} ({m['loss']:.4f})   loss_c {m['loss_c']:.4f}")
+    if show_a:
+        out += f"\tloss_a {m['loss_adv_rel'] + m['loss_adv_vid'] + m['loss_adv_frm']:.4f}"
+    if show_e:
+        out += f"\tloss_e {m['loss_e']:.4f}"
+    out += "\tacc_d " + " ".join(f"{lv} {m['acc_domain'][lv][0]:.1f}/{m['acc_domain'][lv][1]:.1f}" for lv in ("rel", "vid", "frm"))
+    if m["nonfinite_steps"] > 0:
+        out += f"\tnonfinite {m['nonfinite_steps']}"
+    return out
+
+
 def train_list_sizes(num_source: int, num_target: int, batch_size, copy_list):
     """main.py:145-153: the shorter list is repeated (--copy_list Y) so that both loaders run the same number of
     iterations.  Returns (num_source_train, num_target_train)."""
@@ -210,6 +226,10 @@ def main():
                         help="with --feature_store: the sampler of the training batches - test: the reference's test-mode frames (what main.py "
                              "trains on); val: TSNDataSet's val-mode frames; train: TSN's temporal jitter, a fresh draw inside every "
                              "segment's stretch at every step.  Validation keeps test")
+    parser.add_argument("--train_meters", action="store_true",
+                        help="keep the training meters on the device (one more small launch per step): the log line carries the reference's "
+                             "Prec@1 / Prec@5 and running loss averages over the epoch - every step counts, not only the logged one - and the "
+                             "domain discriminators' accuracy; one summary line ends the epoch")
     args = parser.parse_args()
     validate_options(args)
     rank, local_rank, world = parallel.init_distributed()
@@ -225,7 +245,7 @@ def main():
                       clip=args.clip_gradient, device=dev, bf16=(args.arithmetic == "bf16"), bf16_store=(args.arithmetic == "bf16"),
                       f32_split=(args.arithmetic == "f32x3"), aggregation=args.frame_aggregation,
                       dis_DA=args.dis_DA, place_dis=args.place_dis, alpha=max(args.alpha, 0.0), use_bn=args.use_bn,
-                      ens_DA=args.ens_DA, mu=args.mu, add_fc=args.add_fc)
+                      ens_DA=args.ens_DA, mu=args.mu, add_fc=args.add_fc, train_meters=args.train_meters)
     from ta3n_amd.models import VideoModel
     torch.manual_seed(1)
     model = VideoModel(num_class, args.baseline_type, args.frame_aggregation, args.modality, train_segments=T,
@@ -304,8 +324,17 @@ def main():
         chunked = (bool(stores) and eng.fused and not args.graph and Bs_g % world == 0 and Bt_g % world == 0 and
                    os.environ.get("TA3N_TRAIN_CHUNKS", "1") == "1")
         chunk = []
+        if args.train_meters:
+            eng.reset_meters()                   # the window is the epoch (enqueue only)
 
-        def log_line(i, lr_used, beta):
+        def meter_fields(words):
+            """The meter words of the job (behind the 10 loss scalars of `words`) as the line's fields."""
+            from ta3n_amd import _lib
+            m = _lib.decode_meters([int(round(x)) for x in words[10:10 + _lib.METER_WORDS]], words[10 + _lib.METER_WORDS:], world=world)
+            return format_train_meters(m, words[0], show_a=args.adv_DA != "none" and args.use_target != "none",
+                                       show_e=args.add_loss_DA != "none" and args.use_target != "none")
+
+        def log_line(i, lr_used, beta, summary=False):
             # one host sync every print_freq steps (the reference syncs 5-6x per step).  A rank's loss scalars are its
             # shard's sums divided by the GLOBAL counts: the job's losses are their sum over ranks.
             eng.check_exchange()                 # (peer all-reduce only: a rank that gave up waiting is reported here, not silently ignored)
@@ -315,6 +344,11 @@ def main():
             scal = torch.cat((eng.region("losses")[:6], torch.stack([eng.loss_s if eng.loss_s is not None else zero,
                                                                      eng.loss_c2 if eng.loss_c2 is not None else zero,
                                                                      es[0], es[1]]).to(torch.float32)))
+            if args.train_meters:                # counts and float64 loss sums ride in the same all-reduce, as float64 (counts stay exact)
+                from ta3n_amd import _lib
+                o = eng.plan.region("meter_counts")[0]
+                scal = torch.cat((scal.to(torch.float64), eng.ws[o:o + _lib.METER_WORDS].view(torch.int32).to(torch.float64),
+                                  eng.ws[o + 64:o + 64 + 2 * _lib.METER_SUMS].view(torch.float64)))
             if world > 1:
                 torch.distributed.all_reduce(scal)
             if rank == 0:
@@ -331,6 +365,10 @@ def main():
                 if eng.loss_e_shift is not None:        # MCD: the target rows' entropy term is the SECOND pass's (main.py:549, 559-562)
                     v[0] += v[8]
                     v[5] += v[9]
+                if args.train_meters:
+                    print(f"Train: [{epoch}]{' epoch' if summary else ''}[{i}/{steps_per_epoch}] lr {lr_used:.5f}\t{meter_fields(v)}{extra} "
+                          f"beta {beta[0]:.3f},{beta[1]:.3f},{beta[2]:.3f}", flush=True)
+                    return
                 print(f"Train: [{epoch}][{i}/{steps_per_epoch}] lr {lr_used:.5f} loss {v[0]:.4f} loss_c {v[1]:.4f} "
                       f"loss_a {v[2] + v[3] + v[4]:.4f} loss_e {v[5]:.4f}{extra} beta {beta[0]:.3f},{beta[1]:.3f},{beta[2]:.3f}", flush=True)
 
@@ -385,6 +423,8 @@ def main():
                 log_line(i, lr_used, beta)
         flush_chunk()
         eng.flush()                                                                   # the epoch's last update, before validation / checkpoint
+        if args.train_meters and steps_per_epoch > 0:
+            log_line(i, lr, beta, summary=True)                                       # the epoch's window, every step of it
         eng.check_exchange()
         eng.sync_buffers()                                                            # use_bn: every rank evaluates and saves replica 0's running statistics
         if epoch % max(args.eval_freq, 1) == 0 or epoch == args.epochs:                   # main.py:252-274
