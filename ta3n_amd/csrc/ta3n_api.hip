@@ -546,18 +546,46 @@ int ta3n_time_update_launches(ta3n_plan *p, const float *x, float *params, float
 
 static bool known_sampler(int sampler) { return sampler >= TA3N_SAMPLER_TEST && sampler <= TA3N_SAMPLER_TRAIN; }
 
+static int run_gather(const FeedJob &job, int T, int D, int64_t pair_delta, void *stream) {
+    if (launch_gather(job, T, D, pair_delta, static_cast<hipStream_t>(stream)) != 0)
+        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return TA3N_OK;
+}
+
+// The checks of every ta3n_gather_segments* entry point, in one order, and the FeedJob of an accepted call.  Stand-alone (into false): x
+// is the caller's `out`, T x D the caller's sizes.  Into a plan: T x D are the plan's, the rows go to videos [first_video, ...) of its
+// input x and of the input's twins in ws.  What else differs: a bf16 store needs D % 8 (an fp32 store D % 4 into a plan; stand-alone any
+// D, and alignment only where D % 4 == 0 lets the kernel copy float4), and only a bf16 store into a plan with twins may leave x null.
+static int gather_job(FeedJob &job, const ta3n_plan *p, bool into, bool bf16, const void *store, const int64_t *first_row,
+                      const int32_t *num_frames, const int32_t *labels, const int32_t *video_ids, int n_videos, int T, int D, int first_video,
+                      float *x, float *ws, int32_t *labels_out, int32_t *seg_out, int sampler, uint32_t seed, uint32_t step) {
+    if ((into && (!p || !ws)) || !store || !first_row || !num_frames || !video_ids || (!x && !(into && bf16))) return fail(TA3N_ERR_INVALID, "null argument");
+    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
+    if (into) {
+        T = p->geom.T; D = p->geom.D;
+        if (n_videos < 0 || first_video < 0 || first_video + n_videos > p->geom.B) return fail(TA3N_ERR_INVALID, "videos outside the batch");
+    } else if (n_videos < 0 || T <= 0 || D <= 0) return fail(TA3N_ERR_INVALID, "bad sizes");
+    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
+    const bool misaligned = !aligned16(store) || (x && !aligned16(x)) || (into && !aligned16(ws));
+    if (!into && !bf16) {
+        if ((D & 3) == 0 && misaligned) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
+    } else if ((D & (bf16 ? 7 : 3)) != 0 || misaligned)
+        return fail(TA3N_ERR_INVALID, bf16 ? "feature_dim % 8 and 16-byte alignment required" : "feature_dim % 4 and 16-byte alignment required");
+    const size_t row0 = into ? (size_t)first_video * T : 0;
+    float *twin = into && p->geom.o_x16 >= 0 ? ws + p->geom.o_x16 + row0 * D / 2 : nullptr;
+    if (!x && !twin) return fail(TA3N_ERR_INVALID, "a plan without bf16 twins needs the fp32 input rows (x)");
+    job = FeedJob{store, first_row, num_frames, labels, video_ids, x ? x + row0 * D : nullptr, twin, labels_out, seg_out, n_videos, bf16 ? 1 : 0,
+                  sampler, seed, step};
+    return TA3N_OK;
+}
+
 int ta3n_gather_segments_sampled(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                                  const int32_t *video_ids, int n_videos, int num_segments, int feature_dim, float *out,
                                  int32_t *labels_out, int32_t *segment_ids_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
-    if (!store || !first_row || !num_frames || !video_ids || !out) return fail(TA3N_ERR_INVALID, "null argument");
-    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
-    if (n_videos < 0 || num_segments <= 0 || feature_dim <= 0) return fail(TA3N_ERR_INVALID, "bad sizes");
-    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
-    if ((feature_dim & 3) == 0 && (!aligned16(store) || !aligned16(out))) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
-    if (launch_gather_segments(store, first_row, num_frames, labels, video_ids, n_videos, num_segments, feature_dim, out, labels_out,
-                               segment_ids_out, nullptr, static_cast<hipStream_t>(stream), 0, sampler, seed, step) != 0)
-        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return TA3N_OK;
+    FeedJob job;
+    const int rc = gather_job(job, nullptr, false, false, store, first_row, num_frames, labels, video_ids, n_videos, num_segments, feature_dim, 0,
+                              out, nullptr, labels_out, segment_ids_out, sampler, seed, step);
+    return rc != TA3N_OK ? rc : run_gather(job, num_segments, feature_dim, 0, stream);
 }
 
 int ta3n_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
@@ -570,64 +598,44 @@ int ta3n_gather_segments(const float *store, const int64_t *first_row, const int
 int ta3n_gather_segments_bf16(const void *store16, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
                               const int32_t *video_ids, int n_videos, int num_segments, int feature_dim, float *out,
                               int32_t *labels_out, int32_t *segment_ids_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
-    if (!store16 || !first_row || !num_frames || !video_ids || !out) return fail(TA3N_ERR_INVALID, "null argument");
-    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
-    if (n_videos < 0 || num_segments <= 0 || feature_dim <= 0) return fail(TA3N_ERR_INVALID, "bad sizes");
-    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
-    if ((feature_dim & 7) != 0 || !aligned16(store16) || !aligned16(out)) return fail(TA3N_ERR_INVALID, "feature_dim % 8 and 16-byte alignment required");
-    if (launch_gather_segments_bf16(store16, first_row, num_frames, labels, video_ids, n_videos, num_segments, feature_dim, out, labels_out,
-                                    nullptr, static_cast<hipStream_t>(stream), 0, sampler, seed, step, segment_ids_out) != 0)
-        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return TA3N_OK;
+    FeedJob job;
+    const int rc = gather_job(job, nullptr, false, true, store16, first_row, num_frames, labels, video_ids, n_videos, num_segments, feature_dim, 0,
+                              out, nullptr, labels_out, segment_ids_out, sampler, seed, step);
+    return rc != TA3N_OK ? rc : run_gather(job, num_segments, feature_dim, 0, stream);
+}
+
+// the two _into entry points with a sampler: the plan's T x D, no frame numbers
+static int gather_into(ta3n_plan *p, bool bf16, const void *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
+                       const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws, int32_t *labels_out, void *stream,
+                       int sampler, uint32_t seed, uint32_t step) {
+    FeedJob job;
+    const int rc = gather_job(job, p, true, bf16, store, first_row, num_frames, labels, video_ids, n_videos, 0, 0, first_video, x, ws, labels_out,
+                              nullptr, sampler, seed, step);
+    return rc != TA3N_OK ? rc : run_gather(job, p->geom.T, p->geom.D, p->geom.pair_delta, stream);
 }
 
 int ta3n_gather_segments_sampled_into(ta3n_plan *p, const float *store, const int64_t *first_row, const int32_t *num_frames,
                                       const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
                                       int32_t *labels_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
-    if (!p || !store || !first_row || !num_frames || !video_ids || !x || !ws) return fail(TA3N_ERR_INVALID, "null argument");
-    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
-    const Geom &g = p->geom;
-    if (n_videos < 0 || first_video < 0 || first_video + n_videos > g.B) return fail(TA3N_ERR_INVALID, "videos outside the batch");
-    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
-    if ((g.D & 3) != 0 || !aligned16(store) || !aligned16(x) || !aligned16(ws)) return fail(TA3N_ERR_INVALID, "feature_dim % 4 and 16-byte alignment required");
-    const size_t row0 = (size_t)first_video * g.T;
-    float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
-    if (launch_gather_segments(store, first_row, num_frames, labels, video_ids, n_videos, g.T, g.D, x + row0 * g.D, labels_out, nullptr,
-                               twin, static_cast<hipStream_t>(stream), g.pair_delta, sampler, seed, step) != 0)
-        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return TA3N_OK;
+    return gather_into(p, false, store, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out, stream, sampler, seed, step);
 }
 
 int ta3n_gather_segments_into(ta3n_plan *p, const float *store, const int64_t *first_row, const int32_t *num_frames,
                               const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
                               int32_t *labels_out, void *stream) {
-    return ta3n_gather_segments_sampled_into(p, store, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out, stream,
-                                             TA3N_SAMPLER_TEST, 0, 0);
+    return gather_into(p, false, store, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out, stream, TA3N_SAMPLER_TEST, 0, 0);
 }
 
 int ta3n_gather_segments_bf16_sampled_into(ta3n_plan *p, const void *store16, const int64_t *first_row, const int32_t *num_frames,
                                            const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
                                            int32_t *labels_out, void *stream, int sampler, uint32_t seed, uint32_t step) {
-    if (!p || !store16 || !first_row || !num_frames || !video_ids || !ws) return fail(TA3N_ERR_INVALID, "null argument");
-    if (labels_out && !labels) return fail(TA3N_ERR_INVALID, "labels_out needs labels");
-    const Geom &g = p->geom;
-    if (n_videos < 0 || first_video < 0 || first_video + n_videos > g.B) return fail(TA3N_ERR_INVALID, "videos outside the batch");
-    if (!known_sampler(sampler)) return fail(TA3N_ERR_INVALID, "sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
-    if ((g.D & 7) != 0 || !aligned16(store16) || (x && !aligned16(x)) || !aligned16(ws)) return fail(TA3N_ERR_INVALID, "feature_dim % 8 and 16-byte alignment required");
-    if (!x && g.o_x16 < 0) return fail(TA3N_ERR_INVALID, "a plan without bf16 twins needs the fp32 input rows (x)");
-    const size_t row0 = (size_t)first_video * g.T;
-    float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
-    if (launch_gather_segments_bf16(store16, first_row, num_frames, labels, video_ids, n_videos, g.T, g.D, x ? x + row0 * g.D : nullptr, labels_out,
-                                    twin, static_cast<hipStream_t>(stream), g.pair_delta, sampler, seed, step) != 0)
-        return fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return TA3N_OK;
+    return gather_into(p, true, store16, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out, stream, sampler, seed, step);
 }
 
 int ta3n_gather_segments_bf16_into(ta3n_plan *p, const void *store16, const int64_t *first_row, const int32_t *num_frames,
                                    const int32_t *labels, const int32_t *video_ids, int n_videos, int first_video, float *x, float *ws,
                                    int32_t *labels_out, void *stream) {
-    return ta3n_gather_segments_bf16_sampled_into(p, store16, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out,
-                                                  stream, TA3N_SAMPLER_TEST, 0, 0);
+    return gather_into(p, true, store16, first_row, num_frames, labels, video_ids, n_videos, first_video, x, ws, labels_out, stream, TA3N_SAMPLER_TEST, 0, 0);
 }
 
 int ta3n_eval_metrics(ta3n_plan *p, float *ws, int n_videos, int reset, void *stream) {
@@ -732,33 +740,9 @@ static int32_t *target_labels_out(const ta3n_plan *p, float *ws) {
     return (g.flags & TA3N_FLAG_TARGET_LABELS) ? reinterpret_cast<int32_t *>(ws + g.o_labels) + g.Bs : nullptr;
 }
 
-// One batch assembly of a multi-step call: rows [first_video, first_video + ids_per_step) of the input from a packed store.
-static int feed_step(ta3n_plan *p, const ta3n_feed *f, int step, int first_video, int cap, float *x, float *ws, int32_t *labels_out,
-                     hipStream_t s) {
-    const Geom &g = p->geom;
-    if (!f->store || !f->first_row || !f->num_frames || !f->video_ids) return fail(TA3N_ERR_INVALID, "ta3n_feed: null table");
-    if (f->ids_per_step < 0 || f->ids_per_step > cap) return fail(TA3N_ERR_INVALID, "ta3n_feed: ids_per_step exceeds the batch half");
-    if (labels_out && !f->labels) return fail(TA3N_ERR_INVALID, "ta3n_feed: the feed needs labels (the source feed; the target feed under TA3N_FLAG_TARGET_LABELS)");
-    if (!known_sampler(f->sampler)) return fail(TA3N_ERR_INVALID, "ta3n_feed: sampler must be TA3N_SAMPLER_TEST, _VAL or _TRAIN");
-    const int32_t *ids = f->video_ids + (size_t)step * f->ids_per_step;
-    const size_t row0 = (size_t)first_video * g.T;
-    float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
-    int rc;
-    if (f->bf16) {
-        if (!twin && !x) return fail(TA3N_ERR_INVALID, "ta3n_feed: a plan without bf16 twins needs the fp32 input rows");
-        rc = launch_gather_segments_bf16(f->store, f->first_row, f->num_frames, f->labels, ids, f->ids_per_step, g.T, g.D,
-                                         twin ? nullptr : x + row0 * g.D, labels_out, twin, s, g.pair_delta, f->sampler, f->seed,
-                                         f->step0 + (uint32_t)step);
-    } else {
-        rc = launch_gather_segments(static_cast<const float *>(f->store), f->first_row, f->num_frames, f->labels, ids, f->ids_per_step,
-                                    g.T, g.D, x + row0 * g.D, labels_out, nullptr, twin, s, g.pair_delta, f->sampler, f->seed,
-                                    f->step0 + (uint32_t)step);
-    }
-    return rc == 0 ? TA3N_OK : fail(TA3N_ERR_HIP, std::string("gather launch failed: ") + hipGetErrorString(hipGetLastError()));
-}
-
-// The same batch half as a job of the launch that opens a pipelined step (launch_sgd_open_feed): same checks, same destinations as feed_step.
-static int feed_job(ta3n_plan *p, const ta3n_feed *f, int step, int first_video, int cap, float *x, float *ws, int32_t *labels_out, FeedJob *job) {
+// The FeedJob of one batch half of step `step` of a multi-step call: ids_per_step videos from row first_video * T of the input on (and
+// of its twins; a bf16 store feeding twins writes no fp32 rows), drawn with the key step0 + step.  cap: the videos of the half.
+static int feed_job(const ta3n_plan *p, const ta3n_feed *f, int step, int first_video, int cap, float *x, float *ws, int32_t *labels_out, FeedJob &job) {
     const Geom &g = p->geom;
     if (!f->store || !f->first_row || !f->num_frames || !f->video_ids) return fail(TA3N_ERR_INVALID, "ta3n_feed: null table");
     if (f->ids_per_step < 0 || f->ids_per_step > cap) return fail(TA3N_ERR_INVALID, "ta3n_feed: ids_per_step exceeds the batch half");
@@ -767,12 +751,33 @@ static int feed_job(ta3n_plan *p, const ta3n_feed *f, int step, int first_video,
     const size_t row0 = (size_t)first_video * g.T;
     float *twin = g.o_x16 >= 0 ? ws + g.o_x16 + row0 * g.D / 2 : nullptr;
     if (f->bf16 && !twin && !x) return fail(TA3N_ERR_INVALID, "ta3n_feed: a plan without bf16 twins needs the fp32 input rows");
-    job->store = f->store; job->first_row = f->first_row; job->num_frames = f->num_frames; job->labels = f->labels;
-    job->video_ids = f->video_ids + (size_t)step * f->ids_per_step;
-    job->n_videos = f->ids_per_step; job->bf16 = f->bf16 ? 1 : 0;
-    job->out = (f->bf16 && twin) ? nullptr : x + row0 * g.D;      // (a bf16 store feeding twins writes no fp32 rows: feed_step)
-    job->twin = twin; job->labels_out = labels_out;
-    job->sampler = f->sampler; job->seed = f->seed; job->step = f->step0 + (uint32_t)step;      // (the draw's key: feed_step's)
+    job = FeedJob{f->store, f->first_row, f->num_frames, f->labels, f->video_ids + (size_t)step * f->ids_per_step,
+                  (f->bf16 && twin) ? nullptr : x + row0 * g.D, twin, labels_out, nullptr, f->ids_per_step, f->bf16 ? 1 : 0,
+                  f->sampler, f->seed, f->step0 + (uint32_t)step};
+    return TA3N_OK;
+}
+
+// Both halves of step `step` (an absent feed: a job without videos); every check of both comes before anything is launched
+static int feed_jobs(const ta3n_plan *p, const ta3n_feed *source, const ta3n_feed *target, int step, const float *x, float *ws, FeedJob jobs[2]) {
+    const Geom &g = p->geom;
+    int rc;
+    jobs[0] = jobs[1] = FeedJob{};
+    if (source && (rc = feed_job(p, source, step, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), jobs[0])) != TA3N_OK) return rc;
+    if (target && (rc = feed_job(p, target, step, g.Bs, g.Bt, const_cast<float *>(x), ws, target_labels_out(p, ws), jobs[1])) != TA3N_OK) return rc;
+    return TA3N_OK;
+}
+
+// ... assembled by one gather launch per half, for the steps that do not open with launch_sgd_open_feed
+static int gather_feeds(const ta3n_plan *p, const ta3n_feed *source, const ta3n_feed *target, int step, const float *x, float *ws, hipStream_t s) {
+    if (!source && !target) return TA3N_OK;
+    FeedJob jobs[2];
+    int rc = feed_jobs(p, source, target, step, x, ws, jobs);
+    for (int h = 0; h < 2 && rc == TA3N_OK; ++h) rc = run_gather(jobs[h], p->geom.T, p->geom.D, p->geom.pair_delta, s);
+    return rc;
+}
+
+static int check_feed_width(const ta3n_plan *p, const ta3n_feed *source, const ta3n_feed *target) {
+    if ((source || target) && (p->geom.D & 7) != 0) return fail(TA3N_ERR_INVALID, "ta3n_feed: feature_dim % 8 required");
     return TA3N_OK;
 }
 
@@ -787,9 +792,7 @@ static int enqueue_pipelined_step(ta3n_plan *p, const Ptrs &ptrs, float *params,
     // of the launch that opens the step (sgd_open_feed_kernel) - the two gathers as launches of their own cost the step two boundaries
     if (source || target) {
         FeedJob jobs[2];
-        std::memset(jobs, 0, sizeof(jobs));
-        if (source && (rc = feed_job(p, source, k, 0, g.Bs, const_cast<float *>(ptrs.x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), &jobs[0])) != TA3N_OK) return rc;
-        if (target && (rc = feed_job(p, target, k, g.Bs, g.Bt, const_cast<float *>(ptrs.x), ws, target_labels_out(p, ws), &jobs[1])) != TA3N_OK) return rc;
+        if ((rc = feed_jobs(p, source, target, k, ptrs.x, ws, jobs)) != TA3N_OK) return rc;
         if (!fused_norm && launch_grad_norm(g, grads, ws, s) != 0) return fail(TA3N_ERR_HIP, "grad-norm launch failed");
         if (launch_sgd_open_feed(g, params, grads, momentum, ws, 0, p->first_floats, fused_norm != 0, lr, momentum_coef, weight_decay, clip,
                                  PlanHyper(p, next).ptr(), jobs, s) != 0)
@@ -815,7 +818,7 @@ static int check_steps_job(ta3n_plan *p, const float *x, float *params, float *g
     if (!aligned16(x) || !aligned16(params) || !aligned16(grads) || !aligned16(momentum) || !aligned16(ws))
         return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (ta3n_has_pipelined_step(p) != 1) return fail(TA3N_ERR_INVALID, "no pipelined step for this configuration");
-    if ((source || target) && (p->geom.D & 7) != 0) return fail(TA3N_ERR_INVALID, "ta3n_feed: feature_dim % 8 required");
+    if (check_feed_width(p, source, target) != TA3N_OK) return TA3N_ERR_INVALID;
     if (comm && fused_norm) return fail(TA3N_ERR_INVALID, "with a communicator the norm is taken from the REDUCED gradients: fused_norm must be 0");
     return ensure_uploaded(p);
 }
@@ -1001,8 +1004,7 @@ int ta3n_train_steps_sharded(ta3n_plan *p, ta3n_comm *c, const float *x, float *
     Ptrs ptrs = make_ptrs(p, x, params, grads, ws);
     float lr = lr_pending;
     for (int k = 0; k < n_steps; ++k) {
-        if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
-        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, target_labels_out(p, ws), s)) != TA3N_OK) return rc;
+        if ((rc = gather_feeds(p, source, target, k, x, ws, s)) != TA3N_OK) return rc;
         // -- update of the step before (its gradients are reduce-scattered): norm of the own shards, one float per rank gathered,
         //    clip + Nesterov SGD on the own shards (1 / world of the optimiser pass), carrying this step's scalars
         if ((rc = ta3n_shard_sumsq(p, grads, ws, rank, world, stream)) != TA3N_OK) return rc;
@@ -1057,7 +1059,7 @@ int ta3n_train_steps_fused_update(ta3n_plan *p, const float *x, float *params, f
     if (n_steps == 0) return TA3N_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Geom &g = p->geom;
-    if ((source || target) && (g.D & 7) != 0) return fail(TA3N_ERR_INVALID, "ta3n_feed: feature_dim % 8 required");
+    if (check_feed_width(p, source, target) != TA3N_OK) return TA3N_ERR_INVALID;
     const bool twins = g.o_p16 >= 0;
     float *P[2] = {params, params_alt};
     float *T16[2] = {twins ? ws + g.o_p16 : nullptr, twins ? ws + g.o_p16b : nullptr};
@@ -1068,8 +1070,7 @@ int ta3n_train_steps_fused_update(ta3n_plan *p, const float *x, float *params, f
     if (launch_set_hyper(ws + g.o_hyper, PlanHyper(p, &hypers[0]).h, s) != 0) return fail(TA3N_ERR_HIP, "set_hyper launch failed");
     int cur = 0;
     for (int k = 0; k < n_steps; ++k) {
-        if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
-        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, target_labels_out(p, ws), s)) != TA3N_OK) return rc;
+        if ((rc = gather_feeds(p, source, target, k, x, ws, s)) != TA3N_OK) return rc;
         // forward, heads, backward on P[cur]; every gradient tile writes its block of P[1 - cur] (and its twins)
         Ptrs ptrs = make_ptrs(p, x, P[cur], grads, ws, cur);
         SgdSide side;
@@ -1295,18 +1296,16 @@ int ta3n_train_steps_adam(ta3n_plan *p, const float *x, float *params, float *gr
     if (!x || !hypers) return fail(TA3N_ERR_INVALID, "null argument");
     if (!aligned16(x)) return fail(TA3N_ERR_INVALID, "buffers must be 16-byte aligned");
     if (ta3n_has_fused_step(p) != 1) return fail(TA3N_ERR_INVALID, "no fused step for this configuration");
-    if ((source || target) && (p->geom.D & 7) != 0) return fail(TA3N_ERR_INVALID, "ta3n_feed: feature_dim % 8 required");
+    if (check_feed_width(p, source, target) != TA3N_OK) return TA3N_ERR_INVALID;
     float ss, bc;
     if ((rc = ta3n_adam_scalars(step_pending, lr_pending, beta1, beta2, &ss, &bc)) != TA3N_OK) return rc;
     if ((rc = ensure_uploaded(p)) != TA3N_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Geom &g = p->geom;
     Ptrs ptrs = make_ptrs(p, x, params, grads, ws);
     float lr = lr_pending;
     for (int k = 0; k < n_steps; ++k) {
         // the batch of step k (its input rows were last read by the final launch of step k - 1, already enqueued)
-        if (source && (rc = feed_step(p, source, k, 0, g.Bs, const_cast<float *>(x), ws, reinterpret_cast<int32_t *>(ws + g.o_labels), s)) != TA3N_OK) return rc;
-        if (target && (rc = feed_step(p, target, k, g.Bs, g.Bt, const_cast<float *>(x), ws, target_labels_out(p, ws), s)) != TA3N_OK) return rc;
+        if ((rc = gather_feeds(p, source, target, k, x, ws, s)) != TA3N_OK) return rc;
         // the update of the step before as update number step_pending + k, carrying this step's scalars; then the step's own launches
         if ((rc = enqueue_adam(p, params, grads, exp_avg, exp_avg_sq, ws, 0, p->live_floats, fused_norm, lr, beta1, beta2, eps, weight_decay,
                                clip, step_pending + k, &hypers[k], s)) != TA3N_OK) return rc;

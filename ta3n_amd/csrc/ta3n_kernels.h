@@ -318,18 +318,23 @@ int launch_sgd_live(const Geom &g, float *params, const float *grads, float *mom
 int launch_adam_range(const Geom &g, float *params, const float *grads, float *exp_avg, float *exp_avg_sq, float *ws, int64_t begin,
                       int64_t end, bool fused_norm, float step_size, float bc2_sqrt, double beta1, double beta2, float eps, float wd,
                       float clip, const Hyper *next, hipStream_t stream);
-// One batch half of the launch that opens a pipelined step together with its batch assembly (sgd_open_feed_kernel): device pointers of a packed
-// feature store, this step's video ids, where the rows go (fp32 rows / bf16 twin rows; either may be null) - n_videos = 0: nothing to assemble
+// One gather of the device batch assembly - a ta3n_gather_segments* call, or one batch half of a step's feed: device pointers of a packed
+// feature store (fp32 rows, or bf16 rows where bf16 != 0), the video ids, where the rows go (fp32 rows / bf16 twin rows, either may be
+// null; labels and 1-based frame numbers where asked for), and the sampler with the key of its draw.  n_videos = 0: nothing to assemble
 struct FeedJob {
     const void *store;
     const int64_t *first_row;
     const int32_t *num_frames, *labels, *video_ids;
     float *out, *twin;
-    int32_t *labels_out;
+    int32_t *labels_out, *seg_out;
     int32_t n_videos, bf16;
     int32_t sampler;             // TA3N_SAMPLER_*; seed and step key the train sampler's draw (sample_offset)
     uint32_t seed, step;
 };
+__host__ __device__ inline int feed_rows(const FeedJob &job, int T) { return job.n_videos > 0 ? job.n_videos * T : 0; }
+// one workgroup per output row (gather_kernel); pair_delta: the plan's distance from a twin's hi plane to its lo plane, 0 for none
+int launch_gather(const FeedJob &job, int T, int D, int64_t pair_delta, hipStream_t stream);
+// the launch that opens a pipelined step together with its batch assembly (sgd_open_feed_kernel): the update's workgroups, then the rows of feeds[0], feeds[1]
 int launch_sgd_open_feed(const Geom &g, float *params, const float *grads, float *momentum, float *ws, int64_t begin, int64_t end,
                          bool fused_norm, float lr, float mu, float wd, float clip, const Hyper *next, const FeedJob feeds[2], hipStream_t stream);
 int launch_shard_sumsq(const Geom &g, const float *grads, float *ws, int64_t a0, int64_t a1, int64_t b0, int64_t b1, int rank, hipStream_t stream);
@@ -338,15 +343,6 @@ int launch_eval_metrics(const Geom &g, float *ws, int n, int reset, hipStream_t 
 int launch_score(const Geom &g, const Ptrs &ptrs, const ScoreArgs &a, int n, int reset, hipStream_t stream);
 // TA3N_FLAG_TRAIN_METERS (ta3n_meters.hip): one step's loss slots, source accuracy and domain accuracy added to the two meter regions
 int launch_train_meters(const Geom &g, const Ptrs &ptrs, const MetersArgs &a, hipStream_t stream);
-int launch_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
-                           const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, int32_t *seg_out,
-                           float *out_twin, hipStream_t stream, int64_t pair_delta = 0, int sampler = 0, uint32_t seed = 0, uint32_t step = 0);
-
-int launch_gather_segments_bf16(const void *store16, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
-                                const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, float *out_twin,
-                                hipStream_t stream, int64_t pair_delta = 0, int sampler = 0, uint32_t seed = 0, uint32_t step = 0,
-                                int32_t *seg_out = nullptr);
-
 
 }  // namespace ta3n
 

@@ -695,21 +695,9 @@ __host__ __device__ __forceinline__ int sample_offset(int sampler, int nf, int T
     const int avg = nf / T;
     return avg > 0 ? x * avg + (int)sampler_draw(seed, step, slot, (uint32_t)x, (uint32_t)avg) : 0;
 }
-__device__ __forceinline__ void gather_row_f32(int row, const float *__restrict__ store, const int64_t *__restrict__ first_row,
-                                               const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
-                                               const int32_t *__restrict__ video_ids, int T, int D,
-                                               float *__restrict__ out, int32_t *__restrict__ labels_out,
-                                               int32_t *__restrict__ seg_out, uint2 *__restrict__ out16, int64_t pair_delta,
-                                               int sampler, uint32_t seed, uint32_t step) {
-    const int v = row / T, x = row - v * T;
-    const int vid = video_ids[v];
-    const int nf = num_frames[vid];
-    const int off = sample_offset(sampler, nf, T, x, seed, step, (uint32_t)v);      // (v: the slot - rows count from the call's first video)
-    if (threadIdx.x == 0) {
-        if (seg_out) seg_out[row] = off + 1;                    // the reference's ids are 1-based (img_00001.t7)
-        if (labels_out && x == 0) labels_out[v] = labels[vid];
-    }
-    const float *__restrict__ src = store + (size_t)(first_row[vid] + off) * D;
+// The fp32 copy of one row (FeedJob::bf16 == 0): the fp32 row and, where the plan keeps them (TA3N_FLAG_BF16_STORE), its bf16 twin planes
+__device__ __forceinline__ void copy_row_f32(const float *__restrict__ src, int row, int D, float *__restrict__ out,
+                                             uint2 *__restrict__ out16, int64_t pair_delta) {
     float *__restrict__ dst = out + (size_t)row * D;
     if ((D & 3) == 0) {
         const float4 *__restrict__ s4 = reinterpret_cast<const float4 *>(src);
@@ -728,34 +716,11 @@ __device__ __forceinline__ void gather_row_f32(int row, const float *__restrict_
         for (int i = threadIdx.x; i < D; i += 256) dst[i] = src[i];
     }
 }
-__global__ __launch_bounds__(256) void gather_segments_kernel(const float *__restrict__ store, const int64_t *__restrict__ first_row,
-                                                              const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
-                                                              const int32_t *__restrict__ video_ids, int T, int D,
-                                                              float *__restrict__ out, int32_t *__restrict__ labels_out,
-                                                              int32_t *__restrict__ seg_out, uint2 *__restrict__ out16, int64_t pair_delta,
-                                                              int sampler, uint32_t seed, uint32_t step) {
-    gather_row_f32((int)blockIdx.x, store, first_row, num_frames, labels, video_ids, T, D, out, labels_out, seg_out, out16, pair_delta,
-                   sampler, seed, step);
-}
-
-// The same batch assembly from a bf16 packed store ("fp16/bf16 memory-mapped blob"): a quarter of the
-// bytes of the fp32 store + twin path when the step reads bf16 twins (2 B in, 2 B out per element; the fp32 rows are
-// written only if the caller wants them).  One workgroup per output row; D % 8 == 0.
-__device__ __forceinline__ void gather_row_bf16(int row, const uint4 *__restrict__ store, const int64_t *__restrict__ first_row,
-                                                const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
-                                                const int32_t *__restrict__ video_ids, int T, int D,
-                                                float4 *__restrict__ out, int32_t *__restrict__ labels_out,
-                                                int32_t *__restrict__ seg_out, uint4 *__restrict__ out16, int64_t pair_delta,
-                                                int sampler, uint32_t seed, uint32_t step) {
-    const int v = row / T, x = row - v * T;
-    const int vid = video_ids[v];
-    const int nf = num_frames[vid];
-    const int off = sample_offset(sampler, nf, T, x, seed, step, (uint32_t)v);
-    if (threadIdx.x == 0) {
-        if (seg_out) seg_out[row] = off + 1;
-        if (labels_out && x == 0) labels_out[v] = labels[vid];
-    }
-    const uint4 *__restrict__ src = store + (size_t)(first_row[vid] + off) * (D / 8);
+// The same from a bf16 packed store ("fp16/bf16 memory-mapped blob"): a quarter of the bytes of the fp32 store +
+// twin path when the step reads bf16 twins (2 B in, 2 B out per element; the fp32 rows are written only if the caller wants them).
+// D % 8 == 0.
+__device__ __forceinline__ void copy_row_bf16(const uint4 *__restrict__ src, int row, int D, float4 *__restrict__ out,
+                                              uint4 *__restrict__ out16, int64_t pair_delta) {
     for (int i = threadIdx.x; i < D / 8; i += 256) {
         const uint4 q = src[i];
         if (out16) {
@@ -770,14 +735,26 @@ __device__ __forceinline__ void gather_row_bf16(int row, const uint4 *__restrict
         }
     }
 }
-__global__ __launch_bounds__(256) void gather_segments_bf16_kernel(const uint4 *__restrict__ store, const int64_t *__restrict__ first_row,
-                                                                   const int32_t *__restrict__ num_frames, const int32_t *__restrict__ labels,
-                                                                   const int32_t *__restrict__ video_ids, int T, int D,
-                                                                   float4 *__restrict__ out, int32_t *__restrict__ labels_out,
-                                                                   int32_t *__restrict__ seg_out, uint4 *__restrict__ out16, int64_t pair_delta,
-                                                                   int sampler, uint32_t seed, uint32_t step) {
-    gather_row_bf16((int)blockIdx.x, store, first_row, num_frames, labels, video_ids, T, D, out, labels_out, seg_out, out16, pair_delta,
-                    sampler, seed, step);
+// Output row `row` of one gather (FeedJob), by one workgroup: the frame its sampler selects, the frame number and the label where asked
+// for, then the copy body of the store's format.  pair_delta: 0 where the job writes no lo plane.
+__device__ __forceinline__ void gather_row(const FeedJob &job, int row, int T, int D, int64_t pair_delta) {
+    const int v = row / T, x = row - v * T;
+    const int vid = job.video_ids[v];
+    const int nf = job.num_frames[vid];
+    const int off = sample_offset(job.sampler, nf, T, x, job.seed, job.step, (uint32_t)v);      // (v: the slot - rows count from the call's first video)
+    if (threadIdx.x == 0) {
+        if (job.seg_out) job.seg_out[row] = off + 1;                    // the reference's ids are 1-based (img_00001.t7)
+        if (job.labels_out && x == 0) job.labels_out[v] = job.labels[vid];
+    }
+    const size_t src_row = (size_t)(job.first_row[vid] + off);
+    if (job.bf16)
+        copy_row_bf16(static_cast<const uint4 *>(job.store) + src_row * (D / 8), row, D, reinterpret_cast<float4 *>(job.out),
+                      reinterpret_cast<uint4 *>(job.twin), pair_delta);
+    else
+        copy_row_f32(static_cast<const float *>(job.store) + src_row * D, row, D, job.out, reinterpret_cast<uint2 *>(job.twin), pair_delta);
+}
+__global__ __launch_bounds__(256) void gather_kernel(FeedJob job, int T, int D, int64_t pair_delta) {
+    gather_row(job, (int)blockIdx.x, T, D, pair_delta);
 }
 
 // Validation metrics of main.validate / test_models.py (reference main.py:707-735, 809-822; test_models.py:155-198)
@@ -879,45 +856,23 @@ __global__ __launch_bounds__(256) void adam_range_kernel(Geom g, float *__restri
 
 // The launch that opens a pipelined step WITH its batch assembly (ta3n_train_steps with feeds): workgroups [0, sgd_blocks) are
 // sgd_range_kernel's - the previous step's update of the shared frame FC, this step's scalars - and the rest assemble the step's batch, one
-// input row each (gather_row_*: the source half's rows, then the target half's).  The two jobs touch disjoint memory (parameters / momentum /
+// input row each (gather_row: the source half's rows, then the target half's).  The two jobs touch disjoint memory (parameters / momentum /
 // scalars against input rows / labels) and both must be done before the step's first GEMM launch: as launches of their own the two gathers
 // cost the step two boundaries (fresh-batch step +8 us over the resident-batch step at the headline shape).
-struct FeedHalf {
-    const void *store;
-    const int64_t *first_row;
-    const int32_t *num_frames, *labels, *video_ids;
-    float *out;                  // fp32 input rows of this half (nullptr: a bf16 store feeding a plan that reads twins only)
-    int32_t *labels_out;         // nullptr: the target half without TA3N_FLAG_TARGET_LABELS
-    float *twin;                 // bf16 twin rows of this half (nullptr: the plan keeps none)
-    int32_t rows, bf16;          // ids_per_step * T; the store holds bf16
-    int32_t sampler;             // TA3N_SAMPLER_* and the key of its draw (sample_offset)
-    uint32_t seed, step;
-};
-struct FeedPair {
-    FeedHalf half[2];
-    int64_t pair_delta;
-    int32_t T, D;
-};
 __global__ __launch_bounds__(256) void sgd_open_feed_kernel(Geom g, float *__restrict__ params, const float *__restrict__ grads,
                                                             float *__restrict__ mom, float *__restrict__ ws, int i0, int i1, int norm_off,
                                                             int norm_n, float lr, float mu, float wd, float clip, Hyper next, int has_next,
-                                                            int sgd_blocks, FeedPair fp) {
+                                                            int sgd_blocks, FeedJob source, FeedJob target) {
     __shared__ float red[8];
     if ((int)blockIdx.x < sgd_blocks) {
         update_range(g, params, grads, ws, i0, i1, norm_off, norm_n, clip, SgdRule{{mom}, lr, mu, wd}, next, has_next, sgd_blocks, red);
         return;
     }
     int row = (int)blockIdx.x - sgd_blocks;
-    const int h = row < fp.half[0].rows ? 0 : 1;
-    if (h) row -= fp.half[0].rows;
-    const FeedHalf &f = fp.half[h];
-    if (f.bf16)
-        gather_row_bf16(row, static_cast<const uint4 *>(f.store), f.first_row, f.num_frames, f.labels, f.video_ids, fp.T, fp.D,
-                        reinterpret_cast<float4 *>(f.out), f.labels_out, nullptr, reinterpret_cast<uint4 *>(f.twin), f.twin ? fp.pair_delta : 0,
-                        f.sampler, f.seed, f.step);
-    else
-        gather_row_f32(row, static_cast<const float *>(f.store), f.first_row, f.num_frames, f.labels, f.video_ids, fp.T, fp.D,
-                       f.out, f.labels_out, nullptr, reinterpret_cast<uint2 *>(f.twin), f.twin ? fp.pair_delta : 0, f.sampler, f.seed, f.step);
+    const int rows0 = feed_rows(source, g.T);
+    const FeedJob &f = row < rows0 ? source : target;
+    if (row >= rows0) row -= rows0;
+    gather_row(f, row, g.T, g.D, f.twin ? g.pair_delta : 0);
 }
 
 // Closes a fused-update step (gemm_tiles with SgdSide::p_new: every gradient tile already applied the Nesterov step to its own
@@ -1491,22 +1446,9 @@ int launch_sgd(const Geom &g, float *params, const float *grads, float *momentum
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int launch_gather_segments(const float *store, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
-                           const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, int32_t *seg_out,
-                           float *out_twin, hipStream_t stream, int64_t pair_delta, int sampler, uint32_t seed, uint32_t step) {
-    if (n_videos <= 0) return 0;
-    hipLaunchKernelGGL(gather_segments_kernel, dim3(n_videos * T), dim3(256), 0, stream, store, first_row, num_frames, labels, video_ids,
-                       T, D, out, labels_out, seg_out, reinterpret_cast<uint2 *>(out_twin), out_twin ? pair_delta : 0, sampler, seed, step);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int launch_gather_segments_bf16(const void *store16, const int64_t *first_row, const int32_t *num_frames, const int32_t *labels,
-                                const int32_t *video_ids, int n_videos, int T, int D, float *out, int32_t *labels_out, float *out_twin,
-                                hipStream_t stream, int64_t pair_delta, int sampler, uint32_t seed, uint32_t step, int32_t *seg_out) {
-    if (n_videos <= 0) return 0;
-    hipLaunchKernelGGL(gather_segments_bf16_kernel, dim3(n_videos * T), dim3(256), 0, stream, static_cast<const uint4 *>(store16), first_row,
-                       num_frames, labels, video_ids, T, D, reinterpret_cast<float4 *>(out), labels_out, seg_out,
-                       reinterpret_cast<uint4 *>(out_twin), out_twin ? pair_delta : 0, sampler, seed, step);
+int launch_gather(const FeedJob &job, int T, int D, int64_t pair_delta, hipStream_t stream) {
+    if (job.n_videos <= 0) return 0;
+    hipLaunchKernelGGL(gather_kernel, dim3(feed_rows(job, T)), dim3(256), 0, stream, job, T, D, job.twin ? pair_delta : 0);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1560,19 +1502,9 @@ int launch_sgd_open_feed(const Geom &g, float *params, const float *grads, float
     const int i0 = (int)(begin / 4), i1 = (int)(end / 4);
     const int blocks = std::max(update_blocks(i0, i1), 1);      // (block 0 carries the step's scalars even when the range is empty)
     const NormSource ns = norm_source(g, fused_norm);
-    FeedPair fp;
-    std::memset(&fp, 0, sizeof(fp));
-    fp.T = g.T; fp.D = g.D; fp.pair_delta = g.pair_delta;
-    for (int h = 0; h < 2; ++h) {
-        const FeedJob &j = feeds[h];
-        FeedHalf &f = fp.half[h];
-        f.store = j.store; f.first_row = j.first_row; f.num_frames = j.num_frames; f.labels = j.labels; f.video_ids = j.video_ids;
-        f.out = j.out; f.labels_out = j.labels_out; f.twin = j.twin; f.rows = j.n_videos > 0 ? j.n_videos * g.T : 0; f.bf16 = j.bf16;
-        f.sampler = j.sampler; f.seed = j.seed; f.step = j.step;
-    }
-    const int rows = fp.half[0].rows + fp.half[1].rows;
+    const int rows = feed_rows(feeds[0], g.T) + feed_rows(feeds[1], g.T);
     hipLaunchKernelGGL(sgd_open_feed_kernel, dim3(blocks + rows), dim3(256), 0, stream, g, params, grads, momentum, ws, i0, i1, ns.off, ns.n,
-                       lr, mu, wd, clip, next_or_zero(next), next ? 1 : 0, blocks, fp);
+                       lr, mu, wd, clip, next_or_zero(next), next ? 1 : 0, blocks, feeds[0], feeds[1]);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

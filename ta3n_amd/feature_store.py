@@ -138,12 +138,8 @@ class FeatureStore:
         assert engine.D == self.feature_dim
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        if self.bf16:      # the rows go into the input's bf16 twin as they are; fp32 rows only for an engine that does not read twins
-            _lib.check(self._L.ta3n_gather_segments_bf16_sampled_into(engine.plan.handle, p(self.store), p(self.first_row), p(self.num_frames),
-                                                                      p(self.labels), p(ids), ids.numel(), int(first_video),
-                                                                      None if engine.bf16_store else p(engine.X), p(engine.ws), p(labels_out),
-                                                                      stream, *key), "ta3n_gather_segments_bf16_sampled_into")
-            return
-        _lib.check(self._L.ta3n_gather_segments_sampled_into(engine.plan.handle, p(self.store), p(self.first_row), p(self.num_frames),
-                                                             p(self.labels), p(ids), ids.numel(), int(first_video), p(engine.X), p(engine.ws),
-                                                             p(labels_out), stream, *key), "ta3n_gather_segments_sampled_into")
+        fn = "ta3n_gather_segments_bf16_sampled_into" if self.bf16 else "ta3n_gather_segments_sampled_into"
+        # a bf16 store's rows go into the input's bf16 twin as they are; fp32 rows only for an engine that does not read twins
+        x = None if self.bf16 and engine.bf16_store else p(engine.X)
+        _lib.check(getattr(self._L, fn)(engine.plan.handle, p(self.store), p(self.first_row), p(self.num_frames), p(self.labels), p(ids),
+                                        ids.numel(), int(first_video), x, p(engine.ws), p(labels_out), stream, *key), fn)

@@ -29,7 +29,7 @@ TIE_BITS = (0x3F808000, 0x3F818000, 0x3F80C000, 0x3F808001, 0x3F7FFFFF, 0x3F7F80
 EXP_MIN, EXP_MAX = -100, 126
 
 F32_VECTOR_WIDTHS = (4, 36, 1020, 1024, 1028, 2048, 4096)      # D / 4 = 255, 256, 257 around the 256-thread row loop; 2 and 4 trips
-F32_SCALAR_WIDTHS = (1, 37, 257, 1030)                         # D % 4 != 0: the element-wise copy of gather_row_f32 (ta3n_gather_segments only)
+F32_SCALAR_WIDTHS = (1, 37, 257, 1030)                         # D % 4 != 0: the element-wise copy of gather_row's fp32 body (ta3n_gather_segments only)
 BF16_WIDTHS = (8, 2040, 2048, 2056, 4096)                      # D / 8 = 255, 256, 257; 2 trips
 INDEX_SEGMENTS = (2, 7, 16, 33, 64)                            # segment counts beside the golden file's 3, 5, 9, 12, 25
 LONG_CLIPS = (1000, 9999, 100003)

@@ -1,4 +1,4 @@
-"""Device batch assembly at the widths and schedules training runs: gather_segments_kernel / gather_segments_bf16_kernel
+"""Device batch assembly at the widths and schedules training runs: gather_kernel, both copy bodies of gather_row
 (ta3n_gather_segments, ta3n_gather_segments_into, ta3n_gather_segments_bf16_into), the batch rows of the launch that opens a pipelined
 step (sgd_open_feed_kernel under TrainEngine.train_steps(feeds=...)) and ta3n_train_steps_adam's gathers, bit for bit against the CPU
 reference of tests/gather_cases.py (rows by the oracle's Python sampler, twin planes by torch's own bf16 conversion) - at feature widths
@@ -7,11 +7,16 @@ at first_video > 0, the segment arithmetic at 2 .. 64 segments, schedules long e
 Every buffer a gather writes is preset to a sentinel, so a row, tail element or plane that was not written - or was written where it
 should not be - shows.  All comparisons are on bit patterns (int32 / int16 views): -0.0 is not +0.0, and nothing is a tolerance."""
 import ctypes as C
+import json
+import os
+import sys
 
 import pytest
 import torch
 
 import gather_cases as gc
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_gather_refusals as mg  # noqa: E402
 from ta3n_amd import _lib
 from ta3n_amd.engine import TrainEngine
 from ta3n_amd.feature_store import FeatureStore
@@ -338,3 +343,29 @@ def test_adam_steps_with_feeds_equal_per_step_gathers():
     _same_state(a, b, "Adam: parameters, exp_avg, exp_avg_sq, losses, batch")
     _assert_last_batch(b, TINY, "f32", False, cases, tables)
     assert a["M"].ne(0).any() and a["V"].ne(0).any()
+
+
+# ---- g. what a ta3n_feed is refused for, before anything is launched ----
+def test_feed_refusals_precede_every_launch_of_the_call():
+    """ta3n_train_steps and ta3n_train_steps_adam with n_steps = 1 and a source feed that breaks one rule per call (more ids than the
+    batch half, a null first_row, no labels, sampler 3): TA3N_ERR_INVALID with the text recorded in tests/golden/gather_refusals.json
+    before the feed checks were merged, and - the refusal comes before the first launch of step 0 in both entry points (the pipelined
+    step checks both feeds before its norm pass; the Adam loop assembles the source half first) - X, both twin planes and P keep their
+    bits."""
+    with open(mg.JSON_PATH) as f:
+        golden = {(e, v): (rc, text) for e, v, rc, text in json.load(f)["feeds"]}
+    case = gc.case(TINY[2], TINY[3], seed=1, train=True)
+    stores = (case.store(), case.store())
+    tables = tuple(gc.id_table(len(case), 1, n, seed=11 + i).cuda() for i, n in enumerate(TINY[:2]))
+    for entry in mg.FEED_ENTRIES:
+        eng = TrainEngine(*TINY, dropout_i=0.5, dropout_v=0.5, optimizer="Adam" if entry.endswith("adam") else "SGD", **ENGINES["pair"])
+        eng.load_state(synth_state({n: s for n, _, s, _ in eng.plan.params}, seed=7))
+        _preset(eng)
+        before = _buffers(eng, "pair") + (_bits(eng.P),)
+        for violation in mg.FEED_CASES:
+            got = mg.ask_feed(eng, stores, tables, entry, violation)
+            print(entry, violation, got)
+            assert got[0] == -1 and got == tuple(golden[entry, violation]), (entry, violation)
+            after = _buffers(eng, "pair") + (_bits(eng.P),)      # (synchronises)
+            for name, a, b in zip(("X", "hi plane", "lo plane", "P"), before, after):
+                assert torch.equal(a, b), (entry, violation, name)
